@@ -4,9 +4,14 @@
 One step = one forward + one inverse 2^24-point BN254 Fr NTT (BASELINE.json configs[2], the
 k = 24 size the metric is quoted on), data resident in HBM.  `value` = NTT Fr-ops/s with
 Fr-ops = 3 * (n/2) * log2(n) per transform.  The MSM leg (2^20 random
-scalars/points, configs[1]) is timed separately and reported under "msm".
+scalars/points, configs[1]) is timed separately with `--full` and reported under "msm".
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: set-up, warm-up, the K timed NTT steps, the result line.  `--full` adds everything
+else this file measures (the from-idle repeat of the K steps, the MSM legs, the create_proof legs, the C++ host, the
+multi-rank replicas, the CPU baselines).  `--dump-outputs DIR` writes what the last timed step computed to DIR/*.npy (a
+fixed, seeded sample of rows; every 254-bit element as its eight 32-bit Montgomery limb halves in float64, exact).
 
 N > 1: one process per GPU (torchrun), every rank runs the same per-column workload on its own
 device (independent polynomials: no data-path collective) -> "scaling": "weak"; the timing is
@@ -139,6 +144,11 @@ def main():
     ap.add_argument("--wide-k22", type=int, default=1, help="1: also run the wide circuit at 2^22 rows (the zkWasm size), resident mode only")
     ap.add_argument("--cpu-prove-k", type=int, default=22, help="CPU create_proof baseline: mini-PLONK with 2^k rows on the host cores (0 = skip)")
     ap.add_argument("--k24", type=int, default=1, help="1: also run the k = 24 legs (MSM 2^24, create_proof k = 24) the metric is quoted at")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (from-idle NTT, MSM, create_proof, C++ host, replicas, CPU baselines); "
+                         "the options above that select those legs apply only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -263,6 +273,8 @@ def main():
     spin(ntt_step)
     for _ in range(args.warmup):
         ntt_step()
+    # --dump-outputs: the timed steps' input (every step maps x to itself), kept to recompute the forward half of a step
+    x_in = a.clone() if args.dump_outputs and rank == 0 else None
     barrier()
     t0 = time.perf_counter()
     check(L.h2_timer_start(stream), "timer")
@@ -280,18 +292,38 @@ def main():
         elapsed = float(t.item())
     fr_ops_per_transform = 3 * (n // 2) * log_n
     value = world * args.steps * 2 * fr_ops_per_transform / elapsed
-    # ... and the same K steps FROM IDLE (a prover is called from idle): one second of sleep, no spin-up, no warm-up
-    time.sleep(1.0)
-    barrier()
-    i0 = time.perf_counter()
-    for _ in range(args.steps):
-        ntt_step()
-    barrier()
-    idle_elapsed = time.perf_counter() - i0
-    if dist is not None:
-        t = torch.tensor([idle_elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        idle_elapsed = float(t.item())
+    if x_in is not None:
+        # ntt_roundtrip: the array the last timed step returned, inverse(forward(x)); ntt_forward: the forward half of a
+        # step, h2_dev_ntt of the same input recomputed once here (the transform is deterministic).  The same 2^17 rows
+        # (or all of them) from a fixed seed; each Montgomery limb as two exact 32-bit halves, low first
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        rows = np.sort(np.random.default_rng(0x48414C4F32).choice(n, min(n, 1 << 17), replace=False))
+        rows_t = torch.from_numpy(rows).to(dev)
+
+        def dump(name, t):
+            u = t.index_select(0, rows_t).cpu().numpy().view(np.uint64)
+            halves = np.stack([u & np.uint64(0xFFFFFFFF), u >> np.uint64(32)], axis=-1).reshape(len(rows), 8)
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), halves.astype(np.float64))
+
+        dump("ntt_roundtrip", a)
+        check(L.h2_dev_ntt(x_in.data_ptr(), tmp.data_ptr(), vp(w_f), log_n, stream), "h2_dev_ntt")
+        torch.cuda.synchronize()
+        dump("ntt_forward", x_in)
+        del x_in, rows_t
+    idle_elapsed = None
+    if args.full:
+        # ... and the same K steps FROM IDLE (a prover is called from idle): one second of sleep, no spin-up, no warm-up
+        time.sleep(1.0)
+        barrier()
+        i0 = time.perf_counter()
+        for _ in range(args.steps):
+            ntt_step()
+        barrier()
+        idle_elapsed = time.perf_counter() - i0
+        if dist is not None:
+            t = torch.tensor([idle_elapsed], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            idle_elapsed = float(t.item())
 
     # roofline of the dominant kernel (k_ntt_pass): algorithmic bytes per SURVEY.md 8(d) =
     # 64 * n * ceil(log_n / 12) per transform, spread over the passes this build launches per transform
@@ -342,9 +374,10 @@ def main():
         "warmup": args.warmup,
         "spin_up_s": SPIN_S,
         "ms_per_step": elapsed / args.steps * 1e3,
-        "ms_per_step_from_idle": idle_elapsed / args.steps * 1e3,
+        "ms_per_step_from_idle": idle_elapsed / args.steps * 1e3 if idle_elapsed is not None else None,
         "clock_note": "`value` / `ms_per_step`: the K timed steps at the device's steady clock (spin_up_s of the same step, untimed, "
-                      "before the W warm-up steps); `ms_per_step_from_idle`: the same K steps after one idle second, nothing before them",
+                      "before the W warm-up steps); `ms_per_step_from_idle` (--full): the same K steps after one idle second, nothing "
+                      "before them",
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -543,7 +576,7 @@ def main():
             leg = leg.get(name) if isinstance(leg, dict) else None
         return leg
 
-    if not args.no_msm:
+    if args.full and not args.no_msm:
         for key, mlog, msteps, mbatch, what in (
                 ("msm", args.msm_log_n, args.msm_steps, 8, "BASELINE configs[1]: 2^%d BN254 G1 MSM, uniform 254-bit scalars, resident in HBM" % args.msm_log_n),
                 ("msm_k24", 24 if (args.k24 and args.msm_log_n != 24) else 0, 3, 0,
@@ -869,7 +902,7 @@ def main():
     # there would leave the others waiting inside RCCL for good, and the line above would never be printed: a watchdog
     # thread prints what has been measured and ends the process when a leg overruns its budget.
     watchdog_done = None
-    if world > 1:
+    if world > 1 and args.full:
         import threading
 
         watchdog_done = threading.Event()
@@ -887,7 +920,7 @@ def main():
 
         threading.Thread(target=watchdog, daemon=True).start()
 
-    if args.wide_k:
+    if args.full and args.wide_k:
         try:
             out["create_proof_wide"] = wide_leg(args.wide_k, args.wide_quads, 2)
         except Exception as e:  # noqa: BLE001 - the primary (NTT) line must still be printed
@@ -895,7 +928,7 @@ def main():
         torch.cuda.empty_cache()
         headline["create_proof_wide_k%d_seconds" % args.wide_k] = seconds_of(out["create_proof_wide"], "resident" if dist is None else "sharded", "seconds")
         headline["create_proof_wide_k%d_compact_witness_seconds" % args.wide_k] = seconds_of(out["create_proof_wide"], "resident_compact_witness", "seconds")
-    if args.wide_k22 and args.wide_k != 22 and dist is None:      # (N = 1 only: 8 GiB of witness per rank and a fifth proof leg
+    if args.full and args.wide_k22 and args.wide_k != 22 and dist is None:      # (N = 1 only: 8 GiB of witness per rank and a fifth proof leg
         #                                                              would eat the multi-rank legs' time budget for no new information)
         # the zkWasm-sized leg: 64 advice columns x 2^22 rows (8 GiB of 32-byte cells; 2 GiB handed over compact)
         try:
@@ -907,7 +940,7 @@ def main():
         headline["create_proof_wide_k22_compact_witness_seconds"] = seconds_of(out["create_proof_wide_k22"], "resident_compact_witness", "seconds")
 
     for key, kk, steps in (("create_proof", args.prove_k, args.prove_steps), ("create_proof_k24", 24 if args.k24 else 0, 2)):
-        if not kk or (key == "create_proof_k24" and args.prove_k == 24):
+        if not args.full or not kk or (key == "create_proof_k24" and args.prove_k == 24):
             continue
         try:
             leg = prove_leg(kk, steps, verify=True)
@@ -921,7 +954,7 @@ def main():
         headline["create_proof_k%d_evaluate_h_alu_frac" % kk] = seconds_of(out[key], "evaluate_h", "roofline", "alu", "frac")
     # the same k = 22 proof from a host that is not Python: tools/h2prove (plain C++ over the C ABI alone, a process of its own;
     # its bytes are pinned by tests/test_gpu_h2prove.py) -- seconds next to prover.py's
-    if world == 1 and args.prove_k and "error" not in out.get("create_proof", {"error": 1}):
+    if args.full and world == 1 and args.prove_k and "error" not in out.get("create_proof", {"error": 1}):
         try:
             import subprocess
 
@@ -940,7 +973,7 @@ def main():
             out["create_proof"]["h2prove_cxx"] = {"error": "%s: %s" % (type(e).__name__, e)}
     # N > 1: the same circuit as INDEPENDENT proofs, one per GPU (prover.Device.replica: a singleton group, no collective on
     # the data path) -- the throughput a node reaches when there are at least N proofs to make, next to the latency form above
-    if world > 1 and args.prove_k and "error" not in out.get("create_proof", {"error": 1}):
+    if args.full and world > 1 and args.prove_k and "error" not in out.get("create_proof", {"error": 1}):
         try:
             from halo2_gpu_specific_amd import circuits, prover
             from halo2_gpu_specific_amd.rng import ProverRng
@@ -980,7 +1013,7 @@ def main():
         watchdog_done.set()
 
     # ---------------------------------------------------------------- CPU baseline (rank 0, N = 1 only)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             from h2util import Oracle  # the oracle is only the timed CPU baseline here, never the product path
 

@@ -28,7 +28,7 @@ def run_bench(args, env_extra, timeout):
 
 @pytest.mark.gpu
 def test_bare_gpus_2_starts_two_ranks():
-    p, _ = run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--k24", "0", "--prove-k", "12", "--wide-k", "10",
+    p, _ = run_bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--k24", "0", "--prove-k", "12", "--wide-k", "10",
                       "--wide-quads", "2", "--log-n", "16", "--msm-log-n", "14", "--no-cpu-baseline"],
                      {"H2_BENCH_BACKEND": "gloo"}, 600)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -49,7 +49,7 @@ def test_bare_gpus_2_starts_two_ranks():
     assert head["create_proof_k12_seconds"] == line["create_proof"]["seconds"] and head["msm_g1_adds_per_s"] > 0
     assert head["create_proof_wide_k10_seconds"] == wide["sharded"]["seconds"]
     # the same circuits on one rank: the sharded proofs carry the same bytes
-    q, _ = run_bench(["--gpus", "1", "--steps", "1", "--warmup", "1", "--k24", "0", "--prove-k", "0", "--wide-k", "10",
+    q, _ = run_bench(["--full", "--gpus", "1", "--steps", "1", "--warmup", "1", "--k24", "0", "--prove-k", "0", "--wide-k", "10",
                       "--wide-quads", "2", "--log-n", "16", "--no-msm", "--no-cpu-baseline"], {}, 600)
     assert q.returncode == 0, q.stderr[-2000:]
     one = json.loads(q.stdout.strip().splitlines()[-1])
@@ -79,3 +79,35 @@ def test_launcher_reports_failed_ranks_without_a_gpu():
     assert p.returncode != 0
     assert "rank 0 exited" in p.stderr and "rank 1 exited" in p.stderr
     assert p.stdout.strip() == ""       # no result line from a failed run
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_timed_transform(tmp_path, oracle):
+    """--dump-outputs on a 2^12-point run (every row sampled): float64 files of exact 32-bit halves; ntt_forward is the
+    oracle's best_fft of the seeded input bench.py draws, ntt_roundtrip is that input again"""
+    import numpy as np
+    import torch
+
+    from h2util import R_MOD, fr_mont
+
+    log_n, n = 12, 1 << 12
+    p, _ = run_bench(["--gpus", "1", "--log-n", str(log_n), "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path)], {}, 300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 1 and line["ms_per_step"] > 0
+    got = {}
+    for name in ("ntt_forward", "ntt_roundtrip"):
+        h = np.load(tmp_path / (name + ".npy"))
+        assert h.dtype == np.float64 and h.shape == (n, 8), (name, h.dtype, h.shape)
+        assert (h >= 0).all() and (h < 2**32).all() and (h == np.floor(h)).all(), name
+        u = h.astype(np.uint64)
+        got[name] = u[:, 0::2] | (u[:, 1::2] << np.uint64(32))
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0x48414C4F32 + 1)                                  # bench.py's seed for rank 0
+    x = torch.randint(-(2**63), 2**63 - 1, (n, 4), dtype=torch.int64, device="cuda", generator=g)
+    x[:, 3] &= 0x1FFFFFFFFFFFFFFF
+    x = x.cpu().numpy().view(np.uint64)
+    assert np.array_equal(got["ntt_roundtrip"], x)
+    root = 0x03DDB9F5166D18B798865EA93DD31F743215CF6DD39329C8D34F1ED960C37C9C
+    omega = fr_mont(pow(root, 1 << (28 - log_n), R_MOD))
+    assert np.array_equal(got["ntt_forward"], oracle.best_fft(x, omega, log_n))

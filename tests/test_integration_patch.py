@@ -1,93 +1,94 @@
 """The Rust side of the drop-in as verifiable source (VERDICT r1 #8 / missing #4): integration/hip.rs (the `extern "C"`
 shim) and integration/halo2_proofs_hip.patch (the `hip` cargo feature re-targeting the reference's call sites).
-No Rust toolchain exists here, so "verifiable" means: the patch applies cleanly to a scratch copy of the reference
-(`git apply --check`), every `extern "C"` name in hip.rs is an exported symbol of libhalo2_hip.so with the header's
-argument count, and the patch is what tools/make_hip_patch.py generates from the reference today."""
+There is no Rust toolchain, so "verifiable" means: the patch's new modules are the committed shims byte for byte and
+are wired in, every `extern "C"` name in hip.rs is an exported symbol of libhalo2_hip.so with the header's argument count,
+and the Rust mirror of the evaluate_h descriptor has the C layout.  That the patch applies to the reference tree (and is
+what tools/make_hip_patch.py generates from it) needs that tree, which is not part of this repository."""
 import os
 import re
-import shutil
 import subprocess
-
-import pytest
 
 from h2util import ROOT
 
-REF = "/root/reference"
 PATCH = os.path.join(ROOT, "integration", "halo2_proofs_hip.patch")
 HIP_RS = os.path.join(ROOT, "integration", "hip.rs")
 EVAL_HIP_RS = os.path.join(ROOT, "integration", "evaluation_hip.rs")
 RESIDENT_RS = os.path.join(ROOT, "integration", "hip_resident.rs")
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "halo2_proofs")), reason="the reference tree is not on this machine")
 
 
-def _files_in_patch():
+NEW_MODULES = {"halo2_proofs/src/hip.rs": HIP_RS, "halo2_proofs/src/hip_resident.rs": RESIDENT_RS,
+               "halo2_proofs/src/plonk/evaluation_hip.rs": EVAL_HIP_RS}
+ANY = 'any(feature = "cuda", feature = "hip")'
+
+
+def _patched_regions():
+    """{path: the text of the file after the patch, as far as the patch shows it}: every hunk's context and added lines,
+    hunk after hunk (a line of its own between two hunks, so that no pattern spans them)"""
+    regions, rel, hunk = {}, None, None
     with open(PATCH) as f:
-        return sorted({l[6:].strip() for l in f if l.startswith("--- a/")})
+        for line in f:
+            if line.startswith("+++ b/"):
+                rel = line[6:].strip()
+                regions[rel] = []
+            elif line.startswith("--- "):
+                rel, hunk = None, None
+            elif line.startswith("@@") and rel:
+                hunk = []
+                regions[rel].append(hunk)
+            elif hunk is not None and line[:1] in (" ", "+"):
+                hunk.append(line[1:])
+    return {rel: "\x00\n".join("".join(h) for h in hunks) for rel, hunks in regions.items()}
 
 
-@needs_ref
-def test_patch_applies_to_the_reference(tmp_path):
-    for rel in _files_in_patch():
-        src = os.path.join(REF, rel)
-        if os.path.exists(src):
-            dst = tmp_path / rel
-            dst.parent.mkdir(parents=True, exist_ok=True)
-            shutil.copy(src, dst)
-    res = subprocess.run(["git", "apply", "--check", "--verbose", PATCH], cwd=tmp_path, capture_output=True, text=True)
+def test_patch_creates_the_shims_and_wires_the_call_sites(tmp_path):
+    """what the patch does to the reference, read from the patch itself: its new modules (each one hunk from an empty file)
+    applied to empty files are the committed shims byte for byte, and the patched regions of the reference's files hold
+    the feature, the module declarations, the hip dispatch of every call site and the registration / guard calls of the
+    resident polynomials"""
+    for rel in NEW_MODULES:
+        (tmp_path / rel).parent.mkdir(parents=True, exist_ok=True)
+        (tmp_path / rel).write_text("")
+    res = subprocess.run(["git", "apply", "--verbose"] + ["--include=" + rel for rel in NEW_MODULES] + [PATCH], cwd=tmp_path,
+                         capture_output=True, text=True)
     assert res.returncode == 0, res.stderr
-    res = subprocess.run(["git", "apply", PATCH], cwd=tmp_path, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    # the new module is the committed shim, byte for byte, and the feature is wired
-    assert (tmp_path / "halo2_proofs/src/hip.rs").read_text() == open(HIP_RS).read()
-    # round 4: the device-resident containers (DevicePolynomial / DeviceParams / DeviceColumns) as a second module
-    assert (tmp_path / "halo2_proofs/src/hip_resident.rs").read_text() == open(RESIDENT_RS).read()
-    assert '#[cfg(feature = "hip")]\npub mod hip_resident;' in (tmp_path / "halo2_proofs/src/lib.rs").read_text()
-    assert "hip = []" in (tmp_path / "halo2_proofs/Cargo.toml").read_text()
-    arith = (tmp_path / "halo2_proofs/src/arithmetic.rs").read_text()
+    for rel, shim in NEW_MODULES.items():
+        assert (tmp_path / rel).read_text() == open(shim).read(), rel
+    got = _patched_regions()
+    src = lambda rel: got["halo2_proofs/src/" + rel]  # noqa: E731
+    assert '#[cfg(feature = "hip")]\npub mod hip_resident;' in src("lib.rs")
+    assert "hip = []" in got["halo2_proofs/Cargo.toml"]
+    arith = src("arithmetic.rs")
     for fn in ("gpu_multiexp_single_gpu_with_bound", "gpu_multiexp_bound", "gpu_multiexp_bound_and_fft", "gpu_fft", "gpu_ifft"):
         assert re.search(r'#\[cfg\(feature = "hip"\)\]\npub fn %s<' % fn, arith), fn
-    assert arith.count('any(feature = "cuda", feature = "hip")') == 2          # both dispatchers
-    # round 3: the rest of SURVEY.md 8(b) -- evaluate_h / evaluate_with_theta, the coset transforms, GWC batching, the
-    # struct shapes, Params registration
-    any_ = 'any(feature = "cuda", feature = "hip")'
-    assert (tmp_path / "halo2_proofs/src/plonk/evaluation_hip.rs").read_text() == open(EVAL_HIP_RS).read()
-    plonk = (tmp_path / "halo2_proofs/src/plonk.rs").read_text()
+    assert arith.count(ANY) == 2                                                                # both dispatchers
+    plonk = src("plonk.rs")
     assert '#[cfg(feature = "hip")]\nmod evaluation_hip;' in plonk
-    assert plonk.count(any_) == 5 and 'feature = "cuda")]' not in plonk.replace(any_, "")     # plonk.rs:226-240
-    ev = (tmp_path / "halo2_proofs/src/plonk/evaluation.rs").read_text()
-    assert '#[cfg(not(%s))]\n    pub(in crate::plonk) fn evaluate_h(' % any_ in ev                # the CPU twin leaves
+    assert plonk.count(ANY) == 5 and 'feature = "cuda")]' not in plonk.replace(ANY, "")      # plonk.rs:226-240
+    ev = src("plonk/evaluation.rs")
+    assert '#[cfg(not(%s))]\n    pub(in crate::plonk) fn evaluate_h(' % ANY in ev                # the CPU twin leaves
     assert ev.count("super::evaluation_hip::evaluate_lc(") == 2                                 # evaluate, evaluate_with_theta
-    dom = (tmp_path / "halo2_proofs/src/poly/domain.rs").read_text()
+    dom = src("poly/domain.rs")
     for call in ("crate::hip::coeff_to_extended(", "crate::hip::extended_to_coeff(", "crate::hip::divide_by_vanishing_poly("):
         assert dom.count(call) == 1, call
-    com = (tmp_path / "halo2_proofs/src/poly/commitment.rs").read_text()
+    com = src("poly/commitment.rs")
     assert com.count("crate::hip::register_params(&params.g, &params.g_lagrange);") == 2        # unsafe_setup, read
     assert "impl<C: CurveAffine> Drop for Params<C>" in com
-    gwc = (tmp_path / "halo2_proofs/src/poly/multiopen/gwc/prover.rs").read_text()
-    assert "crate::hip::lincomb(&polys, &coeffs)" in gwc
-    prover = (tmp_path / "halo2_proofs/src/plonk/prover.rs").read_text()
+    assert "crate::hip::lincomb(&polys, &coeffs)" in src("poly/multiopen/gwc/prover.rs")
+    prover = src("plonk/prover.rs")
     assert "crate::hip::device_count().to_string()" in prover
-    # resident polynomials (round 6): the proving key's coefficient forms are registered at the end of both keygen functions
-    # and unregistered by Drop; a proof's advice polynomials by an RAII guard in both create_proof functions
-    keygen = (tmp_path / "halo2_proofs/src/plonk/keygen.rs").read_text()
+    # resident polynomials: the proving key's coefficient forms are registered at the end of both keygen functions and
+    # unregistered by Drop; a proof's advice polynomials by an RAII guard in both create_proof functions
+    keygen = src("plonk/keygen.rs")
     assert keygen.count("crate::hip::register_proving_key(&pk);") == 2 and keygen.count("    Ok(pk)\n}") == 2
     assert "impl<C: CurveAffine> Drop for ProvingKey<C>" in plonk and "crate::hip::unregister_proving_key(self);" in plonk
     assert prover.count("let _hip_advice_polys = crate::hip::RegisteredPolys::new(") == 2
     hip = open(HIP_RS).read()
     for name in ("h2_poly_register", "h2_poly_unregister", "pub fn register_proving_key", "pub struct RegisteredPolys", "impl Drop for RegisteredPolys"):
         assert name in hip, name
+    # no `feature = "cuda"` gate left alone in the patched regions of the prover's files
     for rel in ("plonk/keygen.rs", "plonk/permutation.rs", "plonk/permutation/keygen.rs", "plonk/permutation/prover.rs", "plonk/prover.rs"):
-        text = (tmp_path / "halo2_proofs/src" / rel).read_text()
-        left = [l for l in text.splitlines() if 'feature = "cuda"' in l and any_ not in l]
-        assert left == (['            #[cfg(feature = "cuda")]'] if rel == "plonk/prover.rs" else []), (rel, left)
-
-
-@needs_ref
-def test_patch_is_what_the_generator_emits(tmp_path):
-    want = open(PATCH).read()
-    res = subprocess.run(["python3", os.path.join(ROOT, "tools", "make_hip_patch.py"), REF], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    assert open(PATCH).read() == want, "integration/halo2_proofs_hip.patch is stale: re-run tools/make_hip_patch.py"
+        left = [l for l in src(rel).splitlines() if 'feature = "cuda"' in l and ANY not in l]
+        assert left == [], (rel, left)
 
 
 def test_shim_declares_only_exported_symbols_with_the_header_arity():

@@ -14,8 +14,8 @@ for L in 16 18 20 22 24; do ./tools/h2bench msmt $L 254 3; done > "$out/msm_tabl
 for H in 8 2; do H2BENCH_HOT=$H ./tools/h2bench msmt 24 254 2; done >> "$out/msm_table.txt" 2>&1
 rocprofv3 --kernel-trace -d "$out/p_t24" -o t -- ./tools/h2bench msmt 24 254 2 > /dev/null 2>&1
 python3 tools/experiments/split_summary.py "$(find "$out/p_t24" -name '*results.db' | head -1)" > "$out/msm_table_2p24_kernels.txt"
-python3 bench.py > "$out/bench_line.json" 2> "$out/bench.err"
-rocprofv3 --kernel-trace --stats -d "$out/p_bench" -o bench -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline > "$out/bench_line_profiled.json" 2>/dev/null
+python3 bench.py --full > "$out/bench_line.json" 2> "$out/bench.err"
+rocprofv3 --kernel-trace --stats -d "$out/p_bench" -o bench -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > "$out/bench_line_profiled.json" 2>/dev/null
 python3 tools/rocprof_summary.py "$(find "$out/p_bench" -name '*results.db' | head -1)" "$out/bench_kernel_stats.txt" > /dev/null
 CMD="./tools/h2bench ntt 24 2 msm 20 254 2 eval 25 2"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$out/p_f" -o f -- $CMD > /dev/null 2>&1
@@ -27,7 +27,7 @@ python3 tools/prove_bench.py 24 3 > "$out/create_proof_k24.txt" 2>&1
 python3 tools/lookup_bench.py 18 > "$out/lookup_k18.txt" 2>&1
 # round 3: the NTT leg alone under the profiler (the k_ntt_pass average the roofline quotes), its SQ counters, the wide circuit
 # (--wide-k22 0 too: round 5's run lacked it and its "NTT-only" summary held a whole wide k = 22 proof)
-rocprofv3 --kernel-trace --stats -d "$out/p_ntt" -o ntt -- python3 bench.py --steps 20 --warmup 5 --no-msm --prove-k 0 --k24 0 --wide-k 0 --wide-k22 0 --no-cpu-baseline > "$out/bench_ntt_only_line.json" 2>/dev/null
+rocprofv3 --kernel-trace --stats -d "$out/p_ntt" -o ntt -- python3 bench.py --full --steps 20 --warmup 5 --no-msm --prove-k 0 --k24 0 --wide-k 0 --wide-k22 0 --no-cpu-baseline > "$out/bench_ntt_only_line.json" 2>/dev/null
 python3 tools/rocprof_summary.py "$(find "$out/p_ntt" -name '*results.db' | head -1)" "$out/bench_ntt_only_kernel_stats.txt" > /dev/null
 if grep -q "k_acc_slice\|h2_evalh_gen\|k_msm" "$out/bench_ntt_only_kernel_stats.txt"; then
     echo "collect_profiles.sh: bench_ntt_only_kernel_stats.txt is NOT NTT-only (MSM / evaluate_h kernels in it): a leg was left on" >&2
@@ -56,6 +56,6 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$out/p_e3" -o e -- python3 tools/e
 python3 tools/evalh_bench.py 20 30 40 > "$out/evalh_gate_sets.txt" 2>&1
 python3 tools/evalh_bench.py 20 60 200 >> "$out/evalh_gate_sets.txt" 2>&1
 # the multi-rank flow of the default bench, dry-run with four gloo ranks sharing the GPU (communication per phase, replicas leg)
-H2_BENCH_BACKEND=gloo python3 bench.py --gpus 4 --steps 3 --warmup 1 --no-cpu-baseline > "$out/bench_line_gloo4_dry_run.json" 2> "$out/bench_gloo4.err"
+H2_BENCH_BACKEND=gloo python3 bench.py --full --gpus 4 --steps 3 --warmup 1 --no-cpu-baseline > "$out/bench_line_gloo4_dry_run.json" 2> "$out/bench_gloo4.err"
 rm -rf "$out"/p_*
 ls -la "$out"

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT"; out=gpurun_out/b8; mkdir -p $out
 tag=$1; runs=$2; shift 2
 for i in $(seq 1 $runs); do
-  H2_BENCH_BACKEND=gloo timeout 400 python3 bench.py --gpus 8 --steps 2 --warmup 1 --k24 0 --prove-k 0 --wide-k 12 --log-n 18 --no-cpu-baseline "$@" > $out/${tag}_$i.json 2> $out/${tag}_$i.err
+  H2_BENCH_BACKEND=gloo timeout 400 python3 bench.py --full --gpus 8 --steps 2 --warmup 1 --k24 0 --prove-k 0 --wide-k 12 --log-n 18 --no-cpu-baseline "$@" > $out/${tag}_$i.json 2> $out/${tag}_$i.err
   python3 - <<PY
 import json
 try:

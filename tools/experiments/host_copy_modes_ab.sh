@@ -7,7 +7,7 @@ for mode in "H2_HOST_COPY_THREADS=0" "H2_HOST_COPY_THREADS=0 H2_HOST_SERIAL_COPI
     echo "== $mode"
     env $mode python tools/experiments/pageable_intt_probe.py 2>&1 | grep "torch clone\|those again\|4 threads\|again"
     env $mode python tools/experiments/hostapi_wide.py 20 pageable 2>&1 | grep "host-slice (pageable)"
-    env $mode python bench.py --no-msm --no-cpu-baseline --wide-k 0 --wide-k22 0 --k24 0 --cpu-prove-k 0 --steps 3 2>/dev/null | python -c "
+    env $mode python bench.py --full --no-msm --no-cpu-baseline --wide-k 0 --wide-k22 0 --k24 0 --cpu-prove-k 0 --steps 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); h=d['create_proof']['host_slice_api']
 print('mini-PLONK k = 22: pageable %.3f s (in library calls %.3f)  pinned %.3f s  pageable phases %s' % (h['pageable']['seconds'], h['pageable']['seconds_inside_library_calls'], h['pinned']['seconds'], h['pageable']['phases_ms']))"
