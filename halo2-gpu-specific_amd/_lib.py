@@ -121,6 +121,12 @@ SYMBOLS = {
     "h2_dev_logup_multiplicity_bits": (ctypes.c_int, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp, _vp]),
     "h2_dev_logup_counts": (ctypes.c_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, _vp, _sz, _vp]),
     "h2_dev_logup_emit": (ctypes.c_int, [_vp, _sz, _sz, _vp, _vp]),
+    "h2_check_scratch_bytes": (_sz, [_sz]),
+    "h2_dev_check_nonzero_rows": (ctypes.c_int, [_vp, _sz, _vp, _vp, _vp]),
+    "h2_dev_check_gates": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _sz, _vp]),
+    "h2_dev_check_lookup": (ctypes.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, _u32, _u32, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "h2_dev_check_shuffle": (ctypes.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "h2_dev_check_copies": (ctypes.c_int, [_vp, _sz, _vp, _vp, _sz, _u32, _vp, _vp, _sz, _vp]),
     "h2_dev_fixed_base_mul": (ctypes.c_int, [_vp, _vp, _sz, _vp, _vp]),
     "h2_dev_points_decompress": (ctypes.c_int, [_vp, _sz, _vp, _vp]),
     "h2_dev_points_compress": (ctypes.c_int, [_vp, _sz, _vp, _vp]),

@@ -6,6 +6,7 @@
 #include <sys/mman.h>
 #include <thread>
 
+#include "check.hpp"
 #include "common.hpp"
 #include "evalh.hpp"
 #include "msm.hpp"
@@ -1821,6 +1822,73 @@ int h2_dev_evaluate_h(const h2_evalh_desc* desc, void* d_values, void* stream) {
         DeviceCtx* ctx = current_ctx();
         std::lock_guard<std::mutex> g(ctx->mu);  // the interpreter work space is per device
         return evalh_device(ctx, desc, (Fr*)d_values, pick_stream(ctx, stream), true);
+    });
+}
+
+// ------------------------------------------------------------------ witness checks (check.hip)
+size_t h2_check_scratch_bytes(size_t n) { return check_scratch_bytes(n); }
+
+static bool check_out_ok(const uint64_t* d_count, const h2_check_record* d_records, size_t cap, uint32_t circuit) {
+    return d_count && (d_records || cap == 0) && circuit < (1u << 24);
+}
+
+int h2_dev_check_nonzero_rows(const void* d_values, size_t usable_rows, uint32_t* d_rows, uint64_t* d_row_count, void* stream) {
+    if (!d_values || !d_rows || !d_row_count) return bad("h2_dev_check_nonzero_rows: null argument");
+    if (usable_rows >= 0x7fffffffu) return bad("h2_dev_check_nonzero_rows: bad sizes");
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return check_nonzero_rows_launch((const Fr*)d_values, usable_rows, d_rows, d_row_count, pick_stream(ctx, stream));
+    });
+}
+
+int h2_dev_check_gates(const h2_evalh_desc* desc, const uint32_t* d_rows, const uint64_t* d_row_count, uint32_t circuit,
+                       uint64_t* d_count, h2_check_record* d_records, size_t cap, void* stream) {
+    if (!desc || !d_rows || !d_row_count || !check_out_ok(d_count, d_records, cap, circuit))
+        return bad("h2_dev_check_gates: null argument");
+    if (int rc = check_gates_args(desc)) return rc;
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return check_gates_launch(ctx, desc, d_rows, d_row_count, circuit, d_count, d_records, cap, pick_stream(ctx, stream));
+    });
+}
+
+int h2_dev_check_lookup(const void* d_table, const void* const* d_inputs, const uint32_t* tags, size_t n_inputs,
+                        size_t usable_rows, size_t n, uint32_t lookup_index, uint32_t circuit, void* d_scratch,
+                        size_t scratch_bytes, uint64_t* d_count, h2_check_record* d_records, size_t cap, void* stream) {
+    if (!d_table || !d_scratch || (n_inputs && (!d_inputs || !tags)) || !check_out_ok(d_count, d_records, cap, circuit))
+        return bad("h2_dev_check_lookup: null argument");
+    for (size_t j = 0; j < n_inputs; j++)
+        if (!d_inputs[j]) return bad("h2_dev_check_lookup: null input");
+    if (int rc = check_columns_args("h2_dev_check_lookup", usable_rows, n, scratch_bytes)) return rc;
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return check_lookup_launch((const Fr*)d_table, (const Fr* const*)d_inputs, tags, n_inputs, usable_rows, n, lookup_index,
+                                   circuit, d_scratch, scratch_bytes, d_count, d_records, cap, pick_stream(ctx, stream));
+    });
+}
+
+int h2_dev_check_shuffle(const void* d_input, const void* d_shuffle, size_t usable_rows, size_t n, uint32_t group, uint32_t unit,
+                         uint32_t circuit, void* d_scratch, size_t scratch_bytes, uint64_t* d_count, h2_check_record* d_records,
+                         size_t cap, void* stream) {
+    if (!d_input || !d_shuffle || !d_scratch || !check_out_ok(d_count, d_records, cap, circuit))
+        return bad("h2_dev_check_shuffle: null argument");
+    if (int rc = check_columns_args("h2_dev_check_shuffle", usable_rows, n, scratch_bytes)) return rc;
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return check_shuffle_launch((const Fr*)d_input, (const Fr*)d_shuffle, usable_rows, n, group, unit, circuit, d_scratch,
+                                    scratch_bytes, d_count, d_records, cap, pick_stream(ctx, stream));
+    });
+}
+
+int h2_dev_check_copies(const void* const* d_columns, size_t n_columns, const uint32_t* d_map_col, const uint32_t* d_map_row,
+                        size_t n, uint32_t circuit, uint64_t* d_count, h2_check_record* d_records, size_t cap, void* stream) {
+    if ((n_columns && (!d_columns || !d_map_col || !d_map_row)) || !check_out_ok(d_count, d_records, cap, circuit))
+        return bad("h2_dev_check_copies: null argument");
+    if (int rc = check_copies_args(n_columns, n)) return rc;
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return check_copies_launch((const Fr* const*)d_columns, n_columns, d_map_col, d_map_row, n, circuit, d_count, d_records, cap,
+                                   pick_stream(ctx, stream));
     });
 }
 

@@ -10,20 +10,6 @@
 
 namespace h2 {
 
-static constexpr uint32_t SLOT_EMPTY = 0xffffffffu;
-
-__device__ __forceinline__ uint32_t key_hash(const Fr& k) {
-    uint32_t h = 0x9e3779b9u;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        h ^= k.l[i];
-        h *= 0x85ebca6bu;
-        h ^= h >> 13;
-    }
-    h *= 0xc2b2ae35u;
-    return h ^ (h >> 16);
-}
-
 __global__ void __launch_bounds__(256) k_logup_build(const Fr* table, uint32_t usable, uint32_t mask, uint32_t* slots) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= usable) return;
@@ -108,13 +94,21 @@ __global__ void __launch_bounds__(256) k_logup_emit(const uint32_t* count, uint3
     }
 }
 
-static uint32_t table_capacity(size_t usable) {
+uint32_t logup_table_capacity(size_t usable) {
     uint32_t cap = 64;
     while ((size_t)cap < 2 * usable) cap <<= 1;
     return cap;
 }
 
-size_t logup_scratch_bytes(size_t n) { return ((size_t)table_capacity(n) + n + 64) * sizeof(uint32_t); }
+void logup_build_launch(const Fr* d_table, size_t usable, uint32_t* d_slots, uint32_t cap, hipStream_t stream) {
+    H2_HIP(hipMemsetAsync(d_slots, 0xff, (size_t)cap * 4, stream));
+    if (usable)
+        hipLaunchKernelGGL(k_logup_build, dim3((unsigned)((usable + 255) / 256)), dim3(256), 0, stream, d_table, (uint32_t)usable,
+                           cap - 1, d_slots);
+    H2_HIP(hipGetLastError());
+}
+
+size_t logup_scratch_bytes(size_t n) { return ((size_t)logup_table_capacity(n) + n + 64) * sizeof(uint32_t); }
 
 int logup_multiplicity_launch(const Fr* d_table, const Fr* const* d_inputs, size_t n_inputs, size_t usable, size_t n,
                               Fr* d_m, void* d_scratch, size_t scratch_bytes, hipStream_t stream, uint32_t* max_count_out) {
@@ -126,7 +120,7 @@ int logup_multiplicity_launch(const Fr* d_table, const Fr* const* d_inputs, size
         set_last_error("h2_dev_logup_multiplicity: scratch too small (h2_logup_scratch_bytes)");
         return H2_ERR_INVALID;
     }
-    const uint32_t cap = table_capacity(usable), mask = cap - 1;
+    const uint32_t cap = logup_table_capacity(usable), mask = cap - 1;
     uint32_t* slots = (uint32_t*)d_scratch;
     uint32_t* count = slots + cap;
     uint32_t* miss = count + n;
@@ -167,7 +161,7 @@ int logup_counts_launch(const Fr* d_table, const Fr* const* d_inputs, size_t n_i
         set_last_error("h2_dev_logup_counts: scratch too small (h2_logup_scratch_bytes)");
         return H2_ERR_INVALID;
     }
-    const uint32_t cap = table_capacity(usable), mask = cap - 1;
+    const uint32_t cap = logup_table_capacity(usable), mask = cap - 1;
     uint32_t* slots = (uint32_t*)d_scratch;
     H2_HIP(hipMemsetAsync(slots, 0xff, (size_t)cap * 4, stream));
     H2_HIP(hipMemsetAsync(d_counts, 0, (n + 1) * 4, stream));

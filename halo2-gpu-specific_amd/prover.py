@@ -17,6 +17,7 @@ stream.  There is no CPU path in this file: without the library or a GPU it rais
 import ctypes
 import hashlib
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -1312,19 +1313,9 @@ def create_proof_with_shplonk(device, params, pk, advice, rng, timings=None, ins
 _ANY = {"advice": ev.ANY_ADVICE, "fixed": ev.ANY_FIXED, "instance": ev.ANY_INSTANCE}
 
 
-def _compress(D, dom, program, theta, fixed, advice, instance, rows=None):
-    """evaluate_with_theta (plonk/evaluation.rs:2330-2398): the theta-compression of an expression list over the
-    n-point Lagrange domain = the evaluator program with y := theta and extended_k := k.  The descriptor of a program
-    is built once per device and re-bound to the columns / theta of each call (building it costs ~0.1 ms of host time,
-    a k = 18 proof compresses eight expression lists).  `rows` = (first, count): only these rows are computed (one rank's
-    share of a proof dealt by rows); the result is a full-size vector valid there."""
+def _compress_desc(D, dom, program, theta, fixed, advice, instance, rows=None):
+    """the base-domain evaluate_h descriptor of a compression program (`_compress`), bound to these columns and theta"""
     g, parts = program
-    # the pure-column fast path of the reference (plonk/evaluation.rs:2266-2276): ONE expression that is a plain query at the
-    # current rotation compresses to the column itself -- no kernel, no copy (the callers only read the result; an advice column
-    # keeps its Lagrange values until the quotient phase turns it into coefficients, after every lookup pass has consumed them)
-    if len(parts) == 1 and not g.calculations and parts[0].kind in (ev.VS_FIXED, ev.VS_ADVICE, ev.VS_INSTANCE) and \
-            g.rotations[parts[0].rot] == 0 and os.environ.get("H2_COMPRESS_PURE", "1") != "0":
-        return {ev.VS_FIXED: fixed, ev.VS_ADVICE: advice, ev.VS_INSTANCE: instance}[parts[0].kind][parts[0].index]
     cache = D.__dict__.setdefault("_compress_descs", {})
     pointers = dict(fixed=[t.data_ptr() for t in fixed], advice=[t.data_ptr() for t in advice],
                     instance=[t.data_ptr() for t in instance])
@@ -1342,6 +1333,23 @@ def _compress(D, dom, program, theta, fixed, advice, instance, rows=None):
             delta=fr_to_mont_limbs(DELTA), zeta=fr_to_mont_limbs(ZETA), extended_omega=fr_to_mont_limbs(dom.omega),
             row_begin=rows[0] if rows is not None else 0, row_count=rows[1] if rows is not None else 0, **pointers)
         cache[(id(program), dom.k)] = (program, b)
+    return b
+
+
+def _compress(D, dom, program, theta, fixed, advice, instance, rows=None):
+    """evaluate_with_theta (plonk/evaluation.rs:2330-2398): the theta-compression of an expression list over the
+    n-point Lagrange domain = the evaluator program with y := theta and extended_k := k.  The descriptor of a program
+    is built once per device and re-bound to the columns / theta of each call (building it costs ~0.1 ms of host time,
+    a k = 18 proof compresses eight expression lists).  `rows` = (first, count): only these rows are computed (one rank's
+    share of a proof dealt by rows); the result is a full-size vector valid there."""
+    g, parts = program
+    # the pure-column fast path of the reference (plonk/evaluation.rs:2266-2276): ONE expression that is a plain query at the
+    # current rotation compresses to the column itself -- no kernel, no copy (the callers only read the result; an advice column
+    # keeps its Lagrange values until the quotient phase turns it into coefficients, after every lookup pass has consumed them)
+    if len(parts) == 1 and not g.calculations and parts[0].kind in (ev.VS_FIXED, ev.VS_ADVICE, ev.VS_INSTANCE) and \
+            g.rotations[parts[0].rot] == 0 and os.environ.get("H2_COMPRESS_PURE", "1") != "0":
+        return {ev.VS_FIXED: fixed, ev.VS_ADVICE: advice, ev.VS_INSTANCE: instance}[parts[0].kind][parts[0].index]
+    b = _compress_desc(D, dom, program, theta, fixed, advice, instance, rows)
     out = D.empty(dom.n)
     check(D.L.h2_dev_evaluate_h(ctypes.byref(b.desc), out.data_ptr(), D.stream), "h2_dev_evaluate_h (compress)")
     return out
@@ -1403,6 +1411,32 @@ def complete_range_check_witness(cs, n, advice, first_unassigned=None):
         if companion.ndim == 2:
             companion[:usable, 1:] = 0
     return advice
+
+
+def _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, copy_range_columns=False):
+    """The witness intake of create_proof_ext: (advice_sets, instance_sets), one list per circuit instance, with the
+    range-checked columns completed (complete_range_check_witness, in place on the caller's columns unless
+    `copy_range_columns`, which completes copies of them instead)."""
+    multi = len(advice) > 0 and isinstance(advice[0], (list, tuple))
+    advice_sets = [list(a) for a in advice] if multi else [list(advice)]
+    instance_sets = [list(i) for i in instances] if multi else [list(instances)]
+    if len(instance_sets) != len(advice_sets):
+        raise ValueError("InvalidInstances")
+    nadv = len(advice_sets[0])
+    if any(len(a) != nadv for a in advice_sets):
+        raise ValueError("every circuit instance needs the same advice columns")
+    if cs.range_checks:
+        if montgomery:
+            raise ValueError("range-check witness completion needs canonical advice columns")
+        fu = first_unassigned if isinstance(first_unassigned, (list, tuple)) else [first_unassigned] * len(advice_sets)
+        for a, f in zip(advice_sets, fu):                     # prover.rs:1699-1783: plant the range, sort the companion
+            if copy_range_columns:
+                for origin, sort, _, _, _ in cs.range_checks:
+                    for c in (origin, sort):
+                        if isinstance(a[c], np.ndarray):
+                            a[c] = a[c].copy()
+            complete_range_check_witness(cs, n, a, f)
+    return advice_sets, instance_sets
 
 
 def create_proof_from_witness(device, params, pk, witness, rng, use_gwc=True, timings=None, instances=()):
@@ -1487,20 +1521,8 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
                 points_[i] = g1_add_affine(a_, b_)
         return points_
 
-    multi = len(advice) > 0 and isinstance(advice[0], (list, tuple))
-    advice_sets = [list(a) for a in advice] if multi else [list(advice)]
-    instance_sets = [list(i) for i in instances] if multi else [list(instances)]
-    if len(instance_sets) != len(advice_sets):
-        raise ValueError("InvalidInstances")
+    advice_sets, instance_sets = _witness_sets(cs, n, advice, instances, montgomery, first_unassigned)
     ncirc, nadv = len(advice_sets), len(advice_sets[0])
-    if any(len(a) != nadv for a in advice_sets):
-        raise ValueError("every circuit instance needs the same advice columns")
-    if cs.range_checks:
-        if montgomery:
-            raise ValueError("range-check witness completion needs canonical advice columns")
-        fu = first_unassigned if isinstance(first_unassigned, (list, tuple)) else [first_unassigned] * len(advice_sets)
-        for a, f in zip(advice_sets, fu):                     # prover.rs:1699-1783: plant the range, sort the companion
-            complete_range_check_witness(cs, n, a, f)
     advice = [col for a in advice_sets for col in a]          # circuit-major: the order every phase walks them in
     # The residency of the key was decided at keygen for ONE circuit instance; advice, product and lookup polynomials scale
     # with the number of instances.  A key judged 'extended' whose multi-instance proof does not fit runs this proof by the
@@ -2272,3 +2294,203 @@ def _shplonk(D, params, transcript, queries, polys, n):
             raise AssertionError("shplonk: l(u) != 0")   # the reference's must_be_zero (prover.rs:213-214)
         D.kate_division_ranges(l_x, n, u, pong)
     transcript.write_point(D.msm(pong, params.g, n))
+
+
+# ---- checking a witness: MockProver::run(..).verify() (dev.rs:932-1340) on the device ------------------------------------
+CHECK_GATE, CHECK_LOOKUP, CHECK_SHUFFLE, CHECK_COPY = 0, 1, 2, 3      # h2_check_record.kind & 0xff (include/halo2_hip.h)
+# MockProver's VerifyFailure variants (dev.rs), with the index of the circuit instance in `circuit`
+ConstraintNotSatisfied = namedtuple("ConstraintNotSatisfied", "gate_index gate_name poly_index row circuit")
+Lookup = namedtuple("Lookup", "name lookup_index input_set_index input_fail_index row circuit")
+Shuffle = namedtuple("Shuffle", "name group_index shuffle_index row circuit")
+Permutation = namedtuple("Permutation", "column row circuit")
+
+
+def check_failures(cs, records):
+    """h2_check_records -- (kind, index, sub, row) rows, kind = H2_CHECK_* | circuit << 8 -- as MockProver's failures, in the
+    order MockProver chains them: circuit by circuit; gates, lookups, shuffles, then the permutation; within a kind by index,
+    sub-index and row."""
+    gate_of = [(gi, name, pi) for gi, (name, polys) in enumerate(cs.gates) for pi in range(len(polys))]
+    keyed = []
+    for kind, index, sub, row in sorted({tuple(int(v) for v in r) for r in records},
+                                        key=lambda r: (r[0] >> 8, r[0] & 0xFF, r[1], r[2], r[3])):
+        circuit, k = kind >> 8, kind & 0xFF
+        if k == CHECK_GATE:
+            gi, name, pi = gate_of[index]
+            keyed.append(ConstraintNotSatisfied(gi, name, pi, row, circuit))
+        elif k == CHECK_LOOKUP:
+            keyed.append(Lookup(cs.lookups[index][0], index, sub >> 16, sub & 0xFFFF, row, circuit))
+        elif k == CHECK_SHUFFLE:
+            keyed.append(Shuffle(cs.shuffles[index][sub][0], index, sub, row, circuit))
+        elif k == CHECK_COPY:
+            keyed.append(Permutation(cs.perm_columns[index], row, circuit))
+        else:
+            raise ValueError("check: unknown record kind %d" % kind)
+    return keyed
+
+
+def _check_scalar(seed, what):
+    """a non-zero field element drawn from the caller's seed (the screen's y, the compressions' theta)"""
+    h = hashlib.blake2b(b"halo2 check_witness " + what + int(seed).to_bytes(16, "little", signed=True), digest_size=64)
+    return int.from_bytes(h.digest(), "little") % (R_MOD - 1) + 1
+
+
+def check_witness(device, pk, advice, instances=(), seed=0, max_failures=1024, montgomery=False, first_unassigned=None,
+                  timings=None):
+    """Checks a witness against the circuit of `pk` on the device, as MockProver::run(..).verify() does (dev.rs:932-1340), and
+    returns (failures, total): `failures` the first max_failures of them (check_failures: named tuples with MockProver's field
+    names, sorted as MockProver chains its errors), `total` the exact number of failures.
+
+    The witness is taken as create_proof_ext takes it -- canonical (n, 4) columns, Montgomery ones with montgomery=True,
+    compact 1-D columns, device tensors, several circuit instances as a list of column lists with one instance list each --
+    and is not modified: range-checked columns are completed on copies (complete_range_check_witness; its ValueError
+    propagates) and no blinding value is written.  Under a multi-rank Device the check runs on this rank's GPU alone.
+
+      gates     every polynomial of every gate at the usable rows: all of them Horner-folded in a random y (from `seed`) in one
+                base-domain evaluation, then the rows where that is non-zero interpreted polynomial by polynomial
+      lookups   every input tuple (theta-compressed, theta from `seed`) of every usable row in the usable rows of its table; a
+                row reports its first missing (set, input)
+      shuffles  the input rows whose compressed value occurs a different number of times on the two sides (MockProver reports
+                rows of its sorted tuples instead, an order compression destroys)
+      copies    every cell of every permutation column, all n rows, against the cell its cycle maps it to
+    A reported failure is always real; a real one is missed with probability <= (parts or tuple length) x n / r < 2^-200.
+
+    Out of scope: MockProver's CellNotAssigned and ConstraintPoisoned (a dense witness has no unassigned cells; cells in rows
+    >= usable are read as the caller supplied them), gate rows in the blinding region, any change to create_proof*, and the
+    Rust shims under integration/.  `timings` (a dict): filled with the seconds of each phase (synchronising between them)."""
+    import time
+
+    D, L, torch = device, device.L, device.torch
+    cs, dom = pk.cs, pk.domain
+    n = dom.n
+    usable = n - (cs.blinding_factors() + 1)
+    advice_sets, instance_sets = _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, copy_range_columns=True)
+    cap = max(int(max_failures), 0)
+    y, theta = _check_scalar(seed, b"y"), _check_scalar(seed, b"theta")
+    t_last = [time.perf_counter()]
+
+    def phase(name):
+        if timings is not None:
+            D.sync()
+            now = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + now - t_last[0]
+            t_last[0] = now
+
+    # one device block for the count and every record: [u64 count, pad][cap x 16 B]; one download at the end
+    with torch.cuda.stream(D.tstream):
+        blob = torch.zeros(4 * (cap + 1), dtype=torch.int32, device=D.dev)
+        rows_list = torch.empty(max(usable, 1), dtype=torch.int32, device=D.dev)
+        row_count = torch.zeros(1, dtype=torch.int64, device=D.dev)
+    out = (blob.data_ptr(), blob.data_ptr() + 16, cap)
+    scratch = None
+    gate_prog = pk.__dict__.get("_check_gate_program")
+    if gate_prog is None:
+        gate_prog = pk._check_gate_program = compile_compress([p for _, polys in cs.gates for p in polys])
+    ncols = len(cs.perm_columns)
+    if ncols:
+        map_col, map_row = pk.mapping
+        with torch.cuda.stream(D.tstream):
+            maps = torch.from_numpy(np.concatenate([np.ascontiguousarray(c, dtype=np.uint32) for c in list(map_col) + list(map_row)])
+                                    .view(np.int32)).to(D.dev)
+    for ci, (adv_in, inst_in) in enumerate(zip(advice_sets, instance_sets)):
+        if len(adv_in) != cs.num_advice:
+            raise ValueError("check_witness: %d advice columns for a circuit of %d" % (len(adv_in), cs.num_advice))
+        if len(inst_in) != cs.num_instance:
+            raise ValueError("InvalidInstances")
+        adv = []
+        for col in adv_in:
+            t, arrived = D.upload_async(col)          # a copy on the device: the caller's column is only read
+            if arrived is not None:
+                D.tstream.wait_event(arrived)
+            if montgomery:
+                check(L.h2_dev_batch_unmont(t.data_ptr(), n, D.stream), "h2_dev_batch_unmont")
+            check(L.h2_dev_batch_mont(t.data_ptr(), n, D.stream), "h2_dev_batch_mont")
+            adv.append(t)
+        inst = []
+        for vals in inst_in:
+            if len(vals) > usable:
+                raise ValueError("InstanceTooLarge")
+            t = D.zeros(n)
+            D.set_rows(t, 0, list(vals))
+            inst.append(t)
+        phase("upload")
+        fixed = pk.fixed_values
+        if gate_prog[1]:
+            screen = _compress(D, dom, gate_prog, y, fixed, adv, inst)
+            with torch.cuda.stream(D.tstream):
+                row_count.zero_()
+            check(L.h2_dev_check_nonzero_rows(screen.data_ptr(), usable, rows_list.data_ptr(), row_count.data_ptr(), D.stream),
+                  "h2_dev_check_nonzero_rows")
+            phase("screen")
+            b = _compress_desc(D, dom, gate_prog, y, fixed, adv, inst)
+            check(L.h2_dev_check_gates(ctypes.byref(b.desc), rows_list.data_ptr(), row_count.data_ptr(), ci, *out, D.stream),
+                  "h2_dev_check_gates")
+            del screen
+            phase("localise")
+
+        def compress(program):
+            return _compress(D, dom, program, theta, fixed, adv, inst)
+
+        if cs.lookups or cs.shuffles:
+            nbytes = L.h2_check_scratch_bytes(n)
+            scratch = D.scratch(nbytes)
+        for li, (table_prog, set_progs) in enumerate(pk.lookup_programs):
+            table = compress(table_prog)
+            inputs, tags = [], []
+            for si, progs in enumerate(set_progs):
+                for ii, pr in enumerate(progs):
+                    inputs.append(compress(pr))
+                    tags.append(si << 16 | ii)
+            ptrs = (_vp * len(inputs))(*[c.data_ptr() for c in inputs])
+            check(L.h2_dev_check_lookup(table.data_ptr(), ptrs, (ctypes.c_uint32 * len(tags))(*tags), len(inputs), usable, n, li,
+                                        ci, scratch.data_ptr(), nbytes, *out, D.stream), "h2_dev_check_lookup")
+        phase("lookups")
+        for gi, group in enumerate(pk.shuffle_programs):
+            for ui, (ip, sp) in enumerate(group):
+                inp, shf = compress(ip), compress(sp)         # (both held: a freed vector's memory is reused at once)
+                check(L.h2_dev_check_shuffle(inp.data_ptr(), shf.data_ptr(), usable, n, gi, ui, ci, scratch.data_ptr(), nbytes,
+                                             *out, D.stream), "h2_dev_check_shuffle")
+        phase("shuffles")
+        if ncols:
+            colvals = {"advice": adv, "fixed": fixed, "instance": inst}
+            with torch.cuda.stream(D.tstream):
+                col_ptrs = torch.tensor([colvals[kd][i].data_ptr() for kd, i in cs.perm_columns], dtype=torch.int64).to(D.dev)
+            check(L.h2_dev_check_copies(col_ptrs.data_ptr(), ncols, maps.data_ptr(), maps.data_ptr() + ncols * n * 4, n, ci,
+                                        *out, D.stream), "h2_dev_check_copies")
+        phase("copies")
+        del adv, inst
+    with torch.cuda.stream(D.tstream):
+        host = blob.cpu().numpy().view(np.uint32)
+    phase("download")
+    return check_result(cs, host, cap)
+
+
+def check_result(cs, words, cap):
+    """(failures, total) of check_witness's downloaded block: u32 words = [u64 count, 2 pad][cap records of 4]; when the
+    count exceeds cap only the first cap slots hold records"""
+    total = int(np.ascontiguousarray(words[:2]).view(np.uint64)[0])
+    return check_failures(cs, words[4:4 + 4 * cap].reshape(-1, 4)[:min(total, cap)]), total
+
+
+def _describe_failure(f):
+    where = "circuit %d: " % f.circuit if f.circuit else ""
+    if isinstance(f, ConstraintNotSatisfied):
+        return "%sgate %d '%s' polynomial %d is not satisfied at row %d" % (where, f.gate_index, f.gate_name, f.poly_index, f.row)
+    if isinstance(f, Lookup):
+        return "%slookup %d '%s' (input set %d, input %d): row %d is not in the table" % (
+            where, f.lookup_index, f.name, f.input_set_index, f.input_fail_index, f.row)
+    if isinstance(f, Shuffle):
+        return "%sshuffle '%s' (group %d, unit %d): the value of row %d is not shuffled" % (
+            where, f.name, f.group_index, f.shuffle_index, f.row)
+    return "%scopy constraint of %s column %d broken at row %d" % (where, f.column[0], f.column[1], f.row)
+
+
+def assert_satisfied(device, pk, advice, instances=(), seed=0, max_failures=1024, montgomery=False, first_unassigned=None,
+                     shown=10):
+    """MockProver::assert_satisfied (dev.rs:1354-1370): check_witness, raising ValueError with the first `shown` failures
+    (gate, lookup or column name and row) and the total when there is any"""
+    failures, total = check_witness(device, pk, advice, instances, seed, max_failures, montgomery, first_unassigned)
+    if total:
+        lines = [_describe_failure(f) for f in failures[:shown]]
+        more = total - len(lines)
+        raise ValueError("the witness does not satisfy circuit '%s': %d failure(s)\n  %s%s" % (
+            pk.cs.name, total, "\n  ".join(lines), "\n  ... and %d more" % more if more > 0 else ""))

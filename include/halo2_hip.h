@@ -588,6 +588,49 @@ int h2_dev_widen_u64(const void *d_src, size_t n, void *d_dst, void *stream);
 int h2_dev_max_scalar_bits(const void *const *d_cols, size_t count, size_t n, void *d_words, uint32_t *out_bits,
                            void *stream);
 
+/* ---- checking a witness (MockProver::verify, dev.rs:932-1340) on the device ----------------------------------------------
+ * Each failure is one record; kind = H2_CHECK_* | circuit << 8 (the caller's circuit-instance index, < 2^24):
+ *   (GATE, part, 0, row)              gate polynomial `part` (gate by gate, then polynomial by polynomial) is non-zero at row
+ *   (LOOKUP, lookup, tag, row)        the first compressed input of the row that is absent from the table: tag = set << 16 | input
+ *   (SHUFFLE, group, unit, row)       the input value of the row occurs a different number of times among the two sides'
+ *                                     usable rows (the reference reports rows of its sorted tuples instead: dev.rs:1209-1262,
+ *                                     an order that compression destroys)
+ *   (COPY, column, 0, row)            value(column, row) != value(mapping(column, row))
+ * Every entry adds to a caller-zeroed device u64 *d_count and appends to a caller-owned device buffer of `cap` records: one
+ * agent-scope atomic per wave, a record written only when its slot is < cap -- the count is exact after the buffer fills,
+ * which records were kept then is not specified.  One buffer may collect every check of a witness: one download.
+ * Rows checked: the usable rows (< usable_rows) for gates, lookups and shuffles; all n rows for copies.
+ * A reported failure is always real.  The gate screen (all parts Horner-folded in a random y) and a compressed lookup /
+ * shuffle tuple (folded in a random theta) miss a real failure with probability <= (parts or tuple length) x n / r < 2^-200
+ * (Schwartz-Zippel); copies and single-column lookups are exact.
+ * Every entry is asynchronous on `stream` and returns H2_ERR_INVALID for bad arguments without touching the device. */
+typedef struct { uint32_t kind, index, sub, row; } h2_check_record;
+enum { H2_CHECK_GATE = 0, H2_CHECK_LOOKUP = 1, H2_CHECK_SHUFFLE = 2, H2_CHECK_COPY = 3 };
+/* device scratch (bytes) of h2_dev_check_lookup / h2_dev_check_shuffle for columns of n rows */
+size_t h2_check_scratch_bytes(size_t n);
+/* The screen's compaction: appends every row r < usable_rows with d_values[r] != 0 to d_rows (room for usable_rows u32) and
+ * counts them in the caller-zeroed u64 *d_row_count (the list is in no particular order). */
+int h2_dev_check_nonzero_rows(const void *d_values, size_t usable_rows, uint32_t *d_rows, uint64_t *d_row_count, void *stream);
+/* The localisation: the gate program of `desc` (extended_k == k, no permutation, lookup or shuffle part; device column pointers,
+ * as h2_dev_evaluate_h) interpreted at the d_rows listed by h2_dev_check_nonzero_rows only, every value part tested on its own.
+ * Work space is the library's (as h2_dev_evaluate_h's interpreter). */
+int h2_dev_check_gates(const h2_evalh_desc *desc, const uint32_t *d_rows, const uint64_t *d_row_count, uint32_t circuit,
+                       uint64_t *d_count, h2_check_record *d_records, size_t cap, void *stream);
+/* One lookup: the first usable_rows rows of the compressed table d_table against the compressed input columns d_inputs (HOST
+ * array of n_inputs device pointers, in (set, input) order) with their HOST tags (set << 16 | input). */
+int h2_dev_check_lookup(const void *d_table, const void *const *d_inputs, const uint32_t *tags, size_t n_inputs,
+                        size_t usable_rows, size_t n, uint32_t lookup_index, uint32_t circuit, void *d_scratch,
+                        size_t scratch_bytes, uint64_t *d_count, h2_check_record *d_records, size_t cap, void *stream);
+/* One shuffle unit: its compressed input and shuffle columns. */
+int h2_dev_check_shuffle(const void *d_input, const void *d_shuffle, size_t usable_rows, size_t n, uint32_t group, uint32_t unit,
+                         uint32_t circuit, void *d_scratch, size_t scratch_bytes, uint64_t *d_count, h2_check_record *d_records,
+                         size_t cap, void *stream);
+/* The copy constraints: d_columns = DEVICE array of the n_columns permutation columns' device pointers; d_map_col / d_map_row:
+ * device u32, n_columns x n each (the cycle mapping, column-major: entry c n + r).  A mapping entry outside the columns is
+ * reported as a failure of its cell. */
+int h2_dev_check_copies(const void *const *d_columns, size_t n_columns, const uint32_t *d_map_col, const uint32_t *d_map_row,
+                        size_t n, uint32_t circuit, uint64_t *d_count, h2_check_record *d_records, size_t cap, void *stream);
+
 /* ---- synthetic workload (bench.py / tests; not a reference entry point) --------------------- */
 /* n deterministic valid G1Affine points (try-and-increment on y^2 = x^3 + 3) into d_out (n x 64 B). */
 int h2_dev_random_points(uint64_t seed, size_t n, void *d_out, void *stream);
