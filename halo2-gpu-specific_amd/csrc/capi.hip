@@ -9,6 +9,7 @@
 #include "check.hpp"
 #include "common.hpp"
 #include "evalh.hpp"
+#include "g1ntt.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
 #include "poly.hpp"
@@ -884,6 +885,18 @@ int h2_dev_fixed_base_mul(const void* d_scalars, const void* d_table, size_t n, 
         DeviceCtx* ctx = current_ctx();
         return fixed_base_mul_launch((const Fr*)d_scalars, (const uint64_t*)d_table, n, (uint64_t*)d_points,
                                      pick_stream(ctx, stream));
+    });
+}
+
+size_t h2_g1_ntt_scratch_bytes(uint32_t log_n) { return g1_ntt_scratch_bytes(log_n); }
+
+int h2_dev_g1_ntt(const void* d_in, void* d_out, uint32_t log_n, int inverse, void* d_scratch, size_t scratch_bytes,
+                  void* stream) {
+    if (int rc = g1_ntt_args(d_in, d_out, log_n, inverse, d_scratch, scratch_bytes)) return rc;
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return g1_ntt_launch(ctx, (const uint64_t*)d_in, (uint64_t*)d_out, log_n, inverse == 1, d_scratch,
+                             pick_stream(ctx, stream));
     });
 }
 

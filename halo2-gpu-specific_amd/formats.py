@@ -39,28 +39,52 @@ def params_write(device, params, path, additional_data=b""):
         f.write(additional_data)
 
 
-def params_read(device, path):
-    """Params::read -> (Params with both tables resident on the device, additional_data)"""
+def _points_read(device, f, n):
+    """the next n compressed points of `f`, decompressed on the device"""
     torch = device.torch
+    raw = np.frombuffer(f.read(32 * n), dtype=np.uint8)
+    if raw.size != 32 * n:
+        raise IOError("truncated params file")
+    with torch.cuda.stream(device.tstream):
+        d_raw = torch.from_numpy(raw.copy()).to(device.dev)
+        pts = torch.empty((n, 8), dtype=torch.int64, device=device.dev)
+    check(device.L.h2_dev_points_decompress(d_raw.data_ptr(), n, pts.data_ptr(), device.stream), "h2_dev_points_decompress")
+    return pts
+
+
+def params_read(device, path, k=None):
+    """Params::read -> (Params with both tables resident on the device, additional_data).
+    `k` below the file's: the parameters of 2^k rows from the same setup -- only the first 2^k points of g are read and
+    decompressed (the g of a smaller k is a prefix), g_lagrange is derived from them (Params.from_powers: the basis is not
+    a prefix), the rest of the file is skipped; additional_data ([s]G2) does not depend on k and comes back unchanged.
+    `k` above the file's raises ValueError; None or the file's own k reads the file as it is."""
     with open(path, "rb") as f:
-        (k,) = struct.unpack("<I", f.read(4))
-        n = 1 << k
-        tables = []
-        for _ in range(2):
-            raw = np.frombuffer(f.read(32 * n), dtype=np.uint8)
-            if raw.size != 32 * n:
-                raise IOError("truncated params file")
-            with torch.cuda.stream(device.tstream):
-                d_raw = torch.from_numpy(raw.copy()).to(device.dev)
-                pts = torch.empty((n, 8), dtype=torch.int64, device=device.dev)
-            check(device.L.h2_dev_points_decompress(d_raw.data_ptr(), n, pts.data_ptr(), device.stream),
-                  "h2_dev_points_decompress")
-            tables.append(pts)
+        (file_k,) = struct.unpack("<I", f.read(4))
+        if k is not None and k > file_k:
+            raise ValueError("params file %s holds k = %d, cannot give k = %d" % (path, file_k, k))
+        if k is not None and k < file_k:
+            g = _points_read(device, f, 1 << k)
+            f.seek(4 + 64 * (1 << file_k))             # past the rest of g and all of g_lagrange
+            additional = _additional_read(f)
+            return Params.from_powers(device, k, g), additional
+        n = 1 << file_k
+        tables = [_points_read(device, f, n) for _ in range(2)]
         (alen,) = struct.unpack("<I", f.read(4))
         additional = f.read(alen)
         if len(additional) != alen:
             raise IOError("truncated params file")
-    return Params(device, k, tables[0], tables[1]), additional
+    return Params(device, file_k, tables[0], tables[1]), additional
+
+
+def _additional_read(f):
+    head = f.read(4)
+    if len(head) != 4:
+        raise IOError("truncated params file")
+    (alen,) = struct.unpack("<I", head)
+    additional = f.read(alen)
+    if len(additional) != alen:
+        raise IOError("truncated params file")
+    return additional
 
 
 def witness_store(path, k, columns):

@@ -920,6 +920,19 @@ def sharding_description(device):
             "row range; lookup inputs compressed by rows, multiplicities all-reduced as integer counts" % device.group_size)
 
 
+def g1_ntt(device, points, k, inverse):
+    """h2_dev_g1_ntt on a (2^k, 8) device tensor of affine Montgomery points -> a new tensor: inverse = True gives
+    n^-1 sum_j w^(-ij) points[j] (the Lagrange basis from the powers), False sum_j w^(ij) points[j]; w = Domain(k, _).omega"""
+    D, torch = device, device.torch
+    n = 1 << k
+    with torch.cuda.stream(D.tstream):
+        out = torch.empty((n, 8), dtype=torch.int64, device=D.dev)
+        scratch = torch.empty(D.L.h2_g1_ntt_scratch_bytes(k), dtype=torch.uint8, device=D.dev)
+    check(D.L.h2_dev_g1_ntt(points.data_ptr(), out.data_ptr(), k, int(bool(inverse)), scratch.data_ptr(), scratch.numel(),
+                            D.stream), "h2_dev_g1_ntt")
+    return out
+
+
 def _forget_tables(L, ptrs):
     for ptr in ptrs:
         L.h2_dev_bases_forget(ptr)
@@ -1019,6 +1032,32 @@ class Params:
         g_lagrange = fixed_base(t)
         D.sync()
         return Params(D, k, g, g_lagrange)
+
+    @staticmethod
+    def from_powers(device, k, g, tables=None):
+        """Params from the powers g[i] = [s^i] G alone -- an SRS from a ceremony, or the prefix of a larger one: g_lagrange =
+        n^-1 sum_j w^(-ij) g[j] (= [L_i(s)] G) by the G1 NTT on the device (h2_dev_g1_ntt).  g: (2^k, 8) u64 affine Montgomery,
+        numpy or a device tensor (kept as it is); the shifted-base tables as the constructor builds them."""
+        n = 1 << k
+        if isinstance(g, np.ndarray):
+            g = device.upload(np.ascontiguousarray(g, dtype=np.uint64))
+        if tuple(g.shape) != (n, 8):
+            raise ValueError("from_powers: g has shape %s, expected (%d, 8)" % (tuple(g.shape), n))
+        g_lagrange = g1_ntt(device, g, k, inverse=True)
+        device.sync()
+        return Params(device, k, g, g_lagrange, tables)
+
+    def downsize(self, device, k):
+        """The parameters of 2^k rows, k <= self.k: g is a COPY of the first 2^k rows of this g (the library keys the
+        shifted-base tables of a base set by its device address, so a view would collide with this object's entry) and
+        g_lagrange is derived from it (from_powers).  k == self.k returns self."""
+        if not 0 <= k <= self.k:
+            raise ValueError("downsize: k = %d outside 0..%d" % (k, self.k))
+        if k == self.k:
+            return self
+        with device.torch.cuda.stream(device.tstream):
+            g = self.g[: 1 << k].clone()
+        return Params.from_powers(device, k, g)
 
     @staticmethod
     def synthetic(device, k, seed=0x48414C4F32):

@@ -318,6 +318,22 @@ int h2_dev_fixed_base_mul(const void *d_scalars, const void *d_table, size_t n, 
 int h2_dev_points_decompress(const void *d_bytes, size_t n, void *d_points, void *stream);
 int h2_dev_points_compress(const void *d_points, size_t n, void *d_bytes, void *stream);
 
+/* The NTT over G1: n = 2^log_n points (0 <= log_n <= 28), affine Montgomery (64 B each, identity = (0,0)), natural order
+ * in and out.  The Lagrange basis of an SRS from its powers alone -- g_lagrange[i] = [L_i(s)] G from g[i] = [s^i] G, what
+ * Params::unsafe_setup computes from s itself (poly/commitment.rs:85-112) -- and its inverse:
+ *   inverse = 1:  d_out[i] = n^-1 sum_j w^(-ij) d_in[j]
+ *   inverse = 0:  d_out[i] = sum_j w^(ij) d_in[j]
+ * w = ROOT_OF_UNITY^(2^(28 - log_n)), the omega of EvaluationDomain::new for 2^log_n rows (poly/domain.rs:44-149).  Every
+ * result is the exact group element (identity inputs and cancellations included), normalised to affine.
+ * d_scratch: device memory of at least h2_g1_ntt_scratch_bytes(log_n) bytes (128 B per point; 0 for log_n > 28), caller-owned
+ * and free again when the work on `stream` has run.  d_out may equal d_in.  Asynchronous on `stream`; the first call for a
+ * (log_n, direction) builds the twiddle tables of the field NTT's plan for w (or w^-1) and shares them with it.  Returns
+ * H2_ERR_INVALID, without touching the device, for log_n > 28, inverse not 0 or 1, a null pointer or too small a scratch.
+ * (The reference has no such entry point: its setup keeps s.) */
+size_t h2_g1_ntt_scratch_bytes(uint32_t log_n);
+int h2_dev_g1_ntt(const void *d_in, void *d_out, uint32_t log_n, int inverse, void *d_scratch, size_t scratch_bytes,
+                  void *stream);
+
 /* ---- evaluate_h: the quotient numerator h(X) on the extended coset ------------------------------
  * Evaluator::evaluate_h -- plonk/evaluation.rs:778-1226 (CPU twin) / :1229-1985 (cuda).
  * The Rust side flattens its `Evaluator` (plonk/evaluation.rs:270-296) into this plain descriptor:
