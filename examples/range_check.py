@@ -4,8 +4,8 @@ holds the same values sorted, a degree-4 gate (starts at min, ends at max, neigh
 shuffle between the two -- 65535 random values, k = 18, on one MI355X.  `create_proof` completes the witness as the
 reference does (plonk/prover.rs:1699-1783): the range is planted in the unused cells and the companion is sorted.
 
-The verifier is the big-integer one the tests use (tests/ref_plonk.py: test infrastructure, not product code), fed the
-verifying key the device keygen produced.
+The verifier is the product's (halo2-gpu-specific_amd/verifier.py): the verifying half of the key the device keygen
+produced, two device MSMs and the BN254 pairing check on the host.
 
 usage: python examples/range_check.py [k >= 17] [proofs]"""
 import os
@@ -14,13 +14,12 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # before HIP initialises (halo2-gpu-specific_amd/__init__.py says why)
 import torch  # noqa: E402  (first: the library binds to torch's HIP runtime)
 
 torch.cuda.init()
 
-from halo2_gpu_specific_amd import circuits, prover  # noqa: E402
+from halo2_gpu_specific_amd import circuits, prover, verifier  # noqa: E402
 from halo2_gpu_specific_amd.rng import ProverRng  # noqa: E402
 
 k = int(sys.argv[1]) if len(sys.argv) > 1 else 18
@@ -44,11 +43,7 @@ for rep in range(reps):
     print("create_proof: %.1f ms, %d bytes %s" % ((time.perf_counter() - t0) * 1e3, len(proof),
                                                  {a: round(b * 1e3, 1) for a, b in timings.items()}))
 
-import ref_plonk as rp  # noqa: E402
-
-vk = rp.Keys()
-vk.cs, vk.dom, vk.s = rp.range_check_class(0, 0xFFFF, 2), rp.Domain(k, cs.degree()), S
-vk.fixed_commitments, vk.perm_commitments, vk.transcript_repr = pk.fixed_commitments, pk.perm_commitments, pk.transcript_repr
-ok = rp.verify_proof(vk, proof)
-print("verify_proof:", ok)
+t0 = time.perf_counter()
+ok = verifier.verify_proof_with_shplonk(D, verifier.ParamsVerifier.from_params(params), verifier.VerifyingKey.from_proving_key(pk), proof)
+print("verify_proof: %s in %.1f ms" % (ok, (time.perf_counter() - t0) * 1e3))
 assert ok

@@ -2,8 +2,9 @@
 (3 advice columns a, b, c with equality, 4 fixed columns sm, sa, sb, sc, one gate a*sa + b*sb + a*b*sm - c*sc,
 2^(k-4) multiply / add pairs with two copy constraints each, witness a = 5), on one MI355X.
 
-The prover is the product path (halo2-gpu-specific_amd/prover.py over libhalo2_hip.so: there is no CPU fallback); the
-verifier is the independent big-integer one the tests use (tests/ref_plonk.py: test infrastructure, not product code).
+Prover and verifier are the product path (halo2-gpu-specific_amd/prover.py and verifier.py over libhalo2_hip.so: there is no
+CPU fallback): the verifier's MSMs run on the device, its BN254 pairing check on the host, and nothing of it knows the
+setup's toxic scalar -- only the [s]G2 that `unsafe_setup` hands to the ParamsVerifier.
 
 usage: python examples/simple_example_2.py [k] [gwc|shplonk]"""
 import os
@@ -12,13 +13,12 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # before HIP initialises (halo2-gpu-specific_amd/__init__.py says why)
 import torch  # noqa: E402  (first: the library binds to torch's HIP runtime)
 
 torch.cuda.init()
 
-from halo2_gpu_specific_amd import circuits, prover  # noqa: E402
+from halo2_gpu_specific_amd import circuits, prover, verifier  # noqa: E402
 from halo2_gpu_specific_amd.rng import ProverRng  # noqa: E402
 
 k = int(sys.argv[1]) if len(sys.argv) > 1 else 8
@@ -37,19 +37,15 @@ proof = prover.create_proof_ext(D, params, pk, advice, ProverRng(), use_gwc)
 D.sync()
 print("create_proof (%s): %.1f ms, %d bytes" % ("GWC" if use_gwc else "SHPLONK", (time.perf_counter() - t0) * 1e3, len(proof)))
 
-if k <= 12:   # the reference-side check is pure Python: seconds at k = 8, minutes beyond 2^12 rows
-    import ref_plonk as rp
-
-    adv_r, fixed_r, copies_r = rp.MiniPlonk.synthesize(k)
-    rpk = rp.keygen(rp.MiniPlonk, k, S, fixed_r, copies_r)
-    ok = rp.verify_proof(rpk, proof, use_gwc=use_gwc)
-    tampered = bytearray(proof)
-    tampered[40] ^= 1
-    try:
-        bad = rp.verify_proof(rpk, bytes(tampered), use_gwc=use_gwc)
-    except AssertionError:     # the flipped byte no longer decodes to a curve point / canonical scalar
-        bad = False
-    print("verify_proof: %s;  tampered proof: %s" % (ok, bad))
-    assert ok and not bad
-else:
-    print("verify_proof: skipped (k > 12); tests/test_gpu_plonk.py verifies k = 16 .. 24 through the trapdoor opening check")
+vparams = verifier.ParamsVerifier.from_params(params)               # Params::verifier: k, g1, g2, [s]G2, g_lagrange
+vk = verifier.VerifyingKey.from_proving_key(pk)
+timings = {}
+t0 = time.perf_counter()
+ok = verifier.verify_proof_ext(D, vparams, vk, proof, (), use_gwc, timings=timings)
+print("verify_proof: %s in %.1f ms %s" % (ok, (time.perf_counter() - t0) * 1e3, {a: round(b * 1e3, 2) for a, b in timings.items()}))
+tampered = bytearray(proof)
+tampered[40] ^= 1
+why = {}
+bad = verifier.verify_proof_ext(D, vparams, vk, bytes(tampered), (), use_gwc, report=why)
+print("tampered proof: %s (%s)" % (bad, why.get("error")))
+assert ok and not bad

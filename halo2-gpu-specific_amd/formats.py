@@ -10,8 +10,15 @@
                  u32 columns | column i at byte offset 4 + (i << (k + 5)): n x 32 B raw (Montgomery) Fr
                  -- consumed by create_proof_from_witness (plonk/prover.rs:916-1500)
 
-The point encoding (x little-endian, y parity in bit 7 of byte 31, identity = zeros) is this build's convention:
+  verifier params  ParamsVerifier::{write, read}  poly/commitment.rs:392-433
+                 u32 k | u32 public_inputs_size | 32 B g1 | 64 B g2 | 64 B s_g2 | public_inputs_size x 32 B g_lagrange
+
+The G1 point encoding (x little-endian, y parity in bit 7 of byte 31, identity = zeros) is this build's convention:
 pairing_bn256@30b052f is not available to check against ("parity unpinned").
+The G2 encoding -- the SRS file's additional_data ([s]G2) and the two G2 points of a verifier-params file -- is the same
+convention extended to Fq2 = Fq[u] / (u^2 + 1): 64 bytes, x.c0 then x.c1 little-endian, bit 7 of byte 63 = the parity of the
+canonical y.c0 (of y.c1 when y.c0 is zero: y and -y always differ in that bit), identity = zeros; equally unpinned.  The
+codec is the library's (h2_g2_compress / h2_g2_decompress, pairing.py); decompression also checks the order-r subgroup.
 """
 import struct
 
@@ -24,7 +31,8 @@ from .transcript import point_to_bytes
 
 
 def params_write(device, params, path, additional_data=b""):
-    """Params::write.  additional_data: the compressed [s]G2 of the setup (opaque here)."""
+    """Params::write.  additional_data: the compressed [s]G2 of the setup (`params_additional_data`; 64 bytes, the G2
+    encoding described above) -- what verifier.ParamsVerifier.from_params takes back from `params_read`."""
     torch = device.torch
     with open(path, "wb") as f:
         f.write(struct.pack("<I", params.k))
@@ -74,6 +82,64 @@ def params_read(device, path, k=None):
         if len(additional) != alen:
             raise IOError("truncated params file")
     return Params(device, file_k, tables[0], tables[1]), additional
+
+
+def params_additional_data(params):
+    """the additional_data `params_write` should carry for a verifier: the compressed [s]G2 of Params.unsafe_setup"""
+    from .pairing import g2_compress
+
+    return g2_compress(params.s_g2)
+
+
+def params_verifier_write(pv, path, device=None):
+    """ParamsVerifier::write (poly/commitment.rs:392-404).  The Lagrange points are compressed on the host unless they live
+    on a device and `device` is given (h2_dev_points_compress)."""
+    from .pairing import g2_compress
+
+    size = pv.public_inputs_size
+    with open(path, "wb") as f:
+        f.write(struct.pack("<II", pv.k, size))
+        f.write(point_to_bytes(pv.g1) + g2_compress(pv.g2) + g2_compress(pv.s_g2))
+        if device is not None and not isinstance(pv.g_lagrange, np.ndarray) and size:
+            torch = device.torch
+            with torch.cuda.stream(device.tstream):
+                out = torch.empty((size, 32), dtype=torch.uint8, device=device.dev)
+            check(device.L.h2_dev_points_compress(pv.g_lagrange.data_ptr(), size, out.data_ptr(), device.stream),
+                  "h2_dev_points_compress")
+            with torch.cuda.stream(device.tstream):
+                f.write(out.cpu().numpy().tobytes())
+        else:
+            from .transcript import _MONT_INV_Q, Q_MOD
+
+            raw = np.ascontiguousarray(pv.lagrange_host()[:size], dtype=np.uint64).tobytes()
+            for i in range(size):
+                x, y = (int.from_bytes(raw[64 * i + 32 * j:64 * i + 32 * j + 32], "little") * _MONT_INV_Q % Q_MOD for j in range(2))
+                f.write(point_to_bytes(None if x == 0 and y == 0 else (x, y)))
+
+
+def params_verifier_read(path, device=None):
+    """ParamsVerifier::read (poly/commitment.rs:406-433) -> verifier.ParamsVerifier.  With a `device` the Lagrange points
+    are decompressed there and stay resident; without one they are decompressed on the host (public inputs are few) and
+    uploaded when a device first commits to them.  IOError / ValueError for a file that is cut short or holds a bad point."""
+    from .pairing import g1_limbs, g2_decompress
+    from .transcript import point_from_bytes
+    from .verifier import ParamsVerifier
+
+    with open(path, "rb") as f:
+        head = f.read(8 + 32 + 64 + 64)
+        if len(head) != 168:
+            raise IOError("truncated verifier params file")
+        k, size = struct.unpack("<II", head[:8])
+        g1, g2, s_g2 = point_from_bytes(head[8:40]), g2_decompress(head[40:104]), g2_decompress(head[104:168])
+        if device is not None and size:
+            g_lagrange = _points_read(device, f, size)
+        else:
+            raw = f.read(32 * size)
+            if len(raw) != 32 * size:
+                raise IOError("truncated verifier params file")
+            g_lagrange = np.array([g1_limbs(point_from_bytes(raw[32 * i:32 * i + 32])) for i in range(size)],
+                                  dtype=np.uint64).reshape(size, 8)
+    return ParamsVerifier(k, s_g2, g_lagrange, size, g1=g1, g2=g2)
 
 
 def _additional_read(f):

@@ -1031,7 +1031,11 @@ class Params:
         D.eval_op(0, t, t, c=-multiplier)                                       # multiplier * w^i / (s - w^i)
         g_lagrange = fixed_base(t)
         D.sync()
-        return Params(D, k, g, g_lagrange)
+        params = Params(D, k, g, g_lagrange)
+        from .pairing import g2_mul_generator
+
+        params.s_g2 = g2_mul_generator(s)       # additional_data of the setup (:113-116): what a ParamsVerifier needs of s
+        return params
 
     @staticmethod
     def from_powers(device, k, g, tables=None):

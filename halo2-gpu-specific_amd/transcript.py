@@ -125,3 +125,71 @@ class Blake2bWrite:
 
     def finalize(self):
         return bytes(self.writer)
+
+
+class TranscriptError(ValueError):
+    """A proof stream that cannot be read: a point that does not decompress, a scalar that is not below r, a proof that
+    ends early or has bytes left over.  The verifier turns it into a rejection (plonk/error.rs `Error::Transcript`)."""
+
+
+def point_from_bytes(b):
+    """the inverse of point_to_bytes; TranscriptError when the 32 bytes are no curve point"""
+    if len(b) != 32:
+        raise TranscriptError("truncated point")
+    if b == bytes(32):
+        return None
+    sign = b[31] >> 7
+    x = int.from_bytes(bytes(b[:31]) + bytes([b[31] & 0x7F]), "little")
+    if x >= Q_MOD:
+        raise TranscriptError("point: x is not below q")
+    rhs = (x * x * x + 3) % Q_MOD
+    y = pow(rhs, (Q_MOD + 1) // 4, Q_MOD)
+    if y * y % Q_MOD != rhs:
+        raise TranscriptError("point: x^3 + 3 has no square root")
+    if (y & 1) != sign:
+        y = Q_MOD - y
+    return (x, y)
+
+
+class Blake2bRead:
+    """transcript.rs:70-150: the verifier's side of Blake2bWrite over the bytes of a proof"""
+
+    def __init__(self, proof):
+        self.state = hashlib.blake2b(digest_size=64, person=b"Halo2-Transcript")
+        self.reader = bytes(proof)
+        self.pos = 0
+
+    squeeze_challenge_scalar = Blake2bWrite.squeeze_challenge_scalar
+    common_scalar = Blake2bWrite.common_scalar
+
+    def common_point(self, P):
+        if P is None:
+            raise TranscriptError("cannot write points at infinity to the transcript")
+        Blake2bWrite.common_point(self, P)
+
+    def _take(self):
+        chunk = self.reader[self.pos:self.pos + 32]
+        if len(chunk) != 32:
+            raise TranscriptError("the proof ends after %d bytes" % len(self.reader))
+        self.pos += 32
+        return chunk
+
+    def read_point(self):
+        P = point_from_bytes(self._take())
+        self.common_point(P)
+        return P
+
+    def read_scalar(self):
+        v = int.from_bytes(self._take(), "little")
+        if v >= R_MOD:
+            raise TranscriptError("scalar is not below r")
+        self.common_scalar(v)
+        return v
+
+    def remaining(self):
+        """bytes of the proof not read yet (a verifier that is done expects 0)"""
+        return len(self.reader) - self.pos
+
+    def expect_end(self):
+        if self.remaining():
+            raise TranscriptError("%d trailing bytes in the proof" % self.remaining())

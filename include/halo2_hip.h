@@ -647,6 +647,25 @@ int h2_dev_check_shuffle(const void *d_input, const void *d_shuffle, size_t usab
 int h2_dev_check_copies(const void *const *d_columns, size_t n_columns, const uint32_t *d_map_col, const uint32_t *d_map_row,
                         size_t n, uint32_t circuit, uint64_t *d_count, h2_check_record *d_records, size_t cap, void *stream);
 
+/* ---- the verifier's pairing and G2 (host only: no entry below touches a device) ---------------
+ * What the reference takes from the pairing_bn256 crate on the verifier side.  G1: 64 B affine Montgomery, identity (0,0).
+ * G2 (the twist y^2 = x^3 + 3/(9+u) over Fq2 = Fq[u]/(u^2+1)): 128 B = x.c0, x.c1, y.c0, y.c1 in Montgomery form,
+ * identity all zeros.  Every entry validates what it is given and returns H2_ERR_INVALID (never crashes) for a coordinate
+ * that is not a canonical residue, a point off its curve and, where said, a G2 point outside the order-r subgroup. */
+/* *ok = (prod_i e(P_i, Q_i) == 1), one shared final exponentiation; an identity on either side contributes 1.  The
+ * decision of the verifier's `PairMSM`: e(left, [s]G2) e(-right, G2) == 1 (poly/multiopen.rs:29-55 `Decider`,
+ * plonk/verifier.rs:496-507, poly/msm.rs:72-101).  G2 points are checked for the subgroup. */
+int h2_pairing_check(const uint64_t *g1_xy, const uint64_t *g2_xy, size_t pairs, int *ok);
+/* out_xy = [scalar] G2 for the plain (not Montgomery) little-endian scalar < r: the `s_g2` that Params::unsafe_setup
+ * writes as additional_data (poly/commitment.rs:113-116).  A scalar of r or above is H2_ERR_INVALID. */
+int h2_g2_mul_generator(const uint64_t scalar[4], uint64_t out_xy[16]);
+/* The 64-byte G2 encoding of the SRS file's additional_data and of ParamsVerifier::{write, read} (poly/commitment.rs:392-433):
+ * x.c0 then x.c1, 32 bytes little-endian each, bit 7 of byte 63 = the parity of the canonical y.c0 (of y.c1 when y.c0 is
+ * zero), identity = zeros -- the G1 convention above extended to Fq2, and like it a convention of this build.  Compress
+ * checks the curve equation; decompress also checks the subgroup. */
+int h2_g2_compress(const uint64_t xy[16], uint8_t out[64]);
+int h2_g2_decompress(const uint8_t in[64], uint64_t out_xy[16]);
+
 /* ---- synthetic workload (bench.py / tests; not a reference entry point) --------------------- */
 /* n deterministic valid G1Affine points (try-and-increment on y^2 = x^3 + 3) into d_out (n x 64 B). */
 int h2_dev_random_points(uint64_t seed, size_t n, void *d_out, void *stream);
