@@ -63,10 +63,6 @@ int dev_extended_to_coeff_impl(DeviceCtx* ctx, Fr* d_a, Fr* d_tmp, uint32_t exte
                         have_lock);
 }
 
-// A host vector that a call only READS: the device copy of a range registered with h2_poly_register (uploaded once per device:
-// the proving key's coefficient forms, a proof's final polynomials), or nullptr -- the caller then uploads as the reference does.
-const Fr* resident_operand(DeviceCtx* ctx, const uint64_t* host, size_t n) { return host ? poly_resident(ctx, host, n) : nullptr; }
-
 // Elementwise host-slice operations over long vectors run as a pipeline of chunks on three streams of the slot: chunk c + 1
 // crosses PCIe on the copy stream while the kernel of chunk c runs on the compute stream and the result of chunk c - 1 leaves
 // on the third -- the two directions of the link at once, instead of upload-all -> compute -> download-all on one stream.
@@ -130,6 +126,13 @@ bool use_pipeline(size_t size, std::initializer_list<const void*> host) {
         if (!host_pinned(p)) return false;
     return true;
 }
+// One early exit for a failed launch (the *_launch functions have set h2_last_error).
+#define H2_TRY(expr)                        \
+    do {                                    \
+        const int h2_rc_ = (expr);          \
+        if (h2_rc_ != H2_OK) return h2_rc_; \
+    } while (0)
+
 // A result vector in ORDINARY host memory that nobody has touched yet -- what every operation of the reference's data flow
 // returns: a fresh `Vec` -- faults its pages in one by one under the device-to-host copy, on the runtime's single staging thread:
 // 21 ms for the 128 MiB of a k = 22 vector against 2.5 ms on the link (tools/experiments/hostreg_probe.py).  The pages of the
@@ -142,42 +145,162 @@ bool use_pipeline(size_t size, std::initializer_list<const void*> host) {
 #ifndef MADV_POPULATE_WRITE
 #define MADV_POPULATE_WRITE 23
 #endif
-struct Prefault {
-    std::vector<std::thread> workers;
-    Prefault() = default;
-    Prefault(void* dst, size_t bytes) { start(dst, bytes); }
-    void start(void* dst, size_t bytes) {
-        static const int threads = [] {
-            const char* e = getenv("H2_HOST_PREFAULT");
-            const int v = e ? atoi(e) : 4;
-            return v < 0 ? 0 : (v > 32 ? 32 : v);
-        }();
-        if (!threads || !dst || bytes < ((size_t)4 << 20) || host_pinned(dst)) return;
-        const uintptr_t page = 4096, lo = ((uintptr_t)dst + page - 1) & ~(page - 1), hi = ((uintptr_t)dst + bytes) & ~(page - 1);
-        if (hi <= lo) return;
-        // huge pages where the kernel grants them (transparent_hugepage = madvise or always): 512 times fewer faults to take
-        (void)madvise((void*)lo, hi - lo, MADV_HUGEPAGE);
-        const size_t pages = (hi - lo) / page, per = (((pages + threads - 1) / threads) + 511) & ~(size_t)511;   // slices of whole 2 MiB
-        for (int t = 0; t < threads; t++) {
-            const size_t first = (size_t)t * per, count = first < pages ? std::min(per, pages - first) : 0;
-            if (!count) break;
-            char* at = (char*)lo + first * page;
-            workers.emplace_back([at, count] {
-                static const bool populate = getenv("H2_HOST_PREFAULT_POPULATE") && atoi(getenv("H2_HOST_PREFAULT_POPULATE")) != 0;
-                if (populate && madvise(at, count * page, MADV_POPULATE_WRITE) == 0) return;
-                for (size_t i = 0; i < count; i++) {   // (the value written is the one read)
-                    volatile char* q = at + i * page;
-                    *q = *q;
-                }
-            });
+// The RESULT of one host-slice call: `n` elements that the call writes to the caller's vector `host`.  `inputs`: every host
+// vector the call reads.  A result that is one of them (an in-place call; h2_permutation_terms' num / den when they are
+// multiplied into) has its pages already and is left alone; any other is prefaulted from here on.  Every way from device
+// memory to `host` joins the touch threads first -- their `*q = *q` is a non-atomic read-then-write of a byte, and one that ran
+// after a copy would put a stale byte over downloaded data -- and a result that is never written joins when it goes.
+class HostResult {
+    struct Prefault {
+        std::vector<std::thread> workers;
+        void start(void* dst, size_t bytes) {
+            static const int threads = [] {
+                const char* e = getenv("H2_HOST_PREFAULT");
+                const int v = e ? atoi(e) : 4;
+                return v < 0 ? 0 : (v > 32 ? 32 : v);
+            }();
+            if (!threads || !dst || bytes < ((size_t)4 << 20) || host_pinned(dst)) return;
+            const uintptr_t page = 4096, lo = ((uintptr_t)dst + page - 1) & ~(page - 1), hi = ((uintptr_t)dst + bytes) & ~(page - 1);
+            if (hi <= lo) return;
+            // huge pages where the kernel grants them (transparent_hugepage = madvise or always): 512 times fewer faults to take
+            (void)madvise((void*)lo, hi - lo, MADV_HUGEPAGE);
+            const size_t pages = (hi - lo) / page, per = (((pages + threads - 1) / threads) + 511) & ~(size_t)511;   // slices of whole 2 MiB
+            for (int t = 0; t < threads; t++) {
+                const size_t first = (size_t)t * per, count = first < pages ? std::min(per, pages - first) : 0;
+                if (!count) break;
+                char* at = (char*)lo + first * page;
+                workers.emplace_back([at, count] {
+                    static const bool populate = getenv("H2_HOST_PREFAULT_POPULATE") && atoi(getenv("H2_HOST_PREFAULT_POPULATE")) != 0;
+                    if (populate && madvise(at, count * page, MADV_POPULATE_WRITE) == 0) return;
+                    for (size_t i = 0; i < count; i++) {   // (the value written is the one read)
+                        volatile char* q = at + i * page;
+                        *q = *q;
+                    }
+                });
+            }
         }
+        void join() {
+            for (std::thread& w : workers) w.join();
+            workers.clear();
+        }
+        ~Prefault() { join(); }
+    };
+
+    uint64_t* host_;
+    size_t n_;
+    Prefault pf_;
+    friend class ChunkSink;
+    void put(size_t off, size_t len, const Fr* d_src, hipStream_t s) {
+        pf_.join();
+        host_download(host_ + 4 * off, d_src, len * sizeof(Fr), s);
     }
-    void join() {
-        for (std::thread& w : workers) w.join();
-        workers.clear();
+
+public:
+    HostResult(uint64_t* host, size_t n, const void* const* inputs, size_t n_inputs) : host_(host), n_(n) {
+        for (size_t i = 0; i < n_inputs; i++)
+            if (inputs[i] == (const void*)host) return;
+        pf_.start(host, n * sizeof(Fr));
     }
-    ~Prefault() { join(); }
+    HostResult(uint64_t* host, size_t n, std::initializer_list<const void*> inputs = {}) : HostResult(host, n, inputs.begin(), inputs.size()) {}
+    // the whole result from device memory; the stream has drained when this returns: the call may return its status
+    int write(const Fr* d_src, hipStream_t s) {
+        put(0, n_, d_src, s);
+        H2_HIP(hipStreamSynchronize(s));
+        return H2_OK;
+    }
+    // for a callee that copies into the vector itself (evalh_host, evalh_host_coeffs): joined here, just before that call
+    uint64_t* handed_over() {
+        pf_.join();
+        return host_;
+    }
 };
+
+// What `down` of HostCall::chunked is handed instead of a stream: rows [off, off + len) of a result, from device memory.
+// Only chunked makes one, and chunked drains the stream behind it.
+class ChunkSink {
+    hipStream_t s_;
+    friend class HostCall;
+    explicit ChunkSink(hipStream_t s) : s_(s) {}
+
+public:
+    void operator()(HostResult& r, size_t off, size_t len, const Fr* d_src) const { r.put(off, len, d_src, s_); }
+};
+
+// The scope of one host-slice call: a slot of the device pool is leased for as long as it lives (one in-flight call per slot;
+// the calling thread is on the slot's device), and the call's operands reach the device through it.
+class HostCall {
+    DeviceLease lease_;
+
+public:
+    DeviceCtx* const ctx;
+    const hipStream_t stream;      // the slot's compute stream
+    HostCall() : ctx(lease_.ctx), stream(lease_.ctx->stream) {}
+
+    // A host vector that a call only READS: the device copy of a range registered with h2_poly_register (uploaded once per
+    // device: the proving key's coefficient forms, a proof's final polynomials), or nullptr -- the caller then uploads as the
+    // reference does.
+    const Fr* resident(const uint64_t* host, size_t n) const { return host ? poly_resident(ctx, host, n) : nullptr; }
+    // `bytes` of any host data into the staging buffer
+    void* upload(DevBuf& buf, const void* host, size_t bytes) {
+        void* d = buf.get(bytes);
+        host_upload(d, host, bytes, stream);
+        return d;
+    }
+    // a read-only operand of n elements: where it lies on the device when registered, else uploaded into the staging buffer
+    const Fr* in(DevBuf& buf, const uint64_t* host, size_t n) {
+        const Fr* d = resident(host, n);
+        return d ? d : (const Fr*)upload(buf, host, n * sizeof(Fr));
+    }
+    // `count` read-only operands of n elements each: the registered ones where they lie, the others side by side in ONE staging
+    // buffer (`extra` bytes longer), a host vector that is named several times once
+    std::vector<const Fr*> in_packed(DevBuf& buf, const uint64_t* const* hosts, size_t count, size_t n, size_t extra = 0) {
+        std::vector<const Fr*> d(count);
+        std::map<const uint64_t*, size_t> staged;        // host vector -> its slot in the upload block
+        for (size_t j = 0; j < count; j++) {
+            d[j] = resident(hosts[j], n);
+            if (!d[j]) staged.emplace(hosts[j], staged.size());
+        }
+        if (staged.empty() && !extra) return d;
+        Fr* up = (Fr*)buf.get(staged.size() * n * sizeof(Fr) + extra);
+        for (auto& kv : staged) host_upload(up + kv.second * n, kv.first, n * sizeof(Fr), stream);
+        for (size_t j = 0; j < count; j++)
+            if (!d[j]) d[j] = up + staged[hosts[j]] * n;
+        return d;
+    }
+
+    // An elementwise operation over `total` elements, stated once as `up` / `run` / `down` (each enqueues rows [off, off + len)
+    // in staging slot `slot`; `run` returns the launch's status): chunk by chunk through pipeline_chunks, or in one piece on the
+    // compute stream.  The caller sizes its staging for the form it chose: chunk = pipelined ? PIPE_CHUNK : total.
+    template <class Up, class Run, class Down>
+    int chunked(size_t total, bool pipelined, Up up, Run run, Down down) {
+        if (pipelined) {
+            int rc = H2_OK;
+            pipeline_chunks(ctx, total, up,
+                [&](size_t off, size_t len, int slot, hipStream_t st) {
+                    int r = run(off, len, slot, st);
+                    if (r != H2_OK) rc = r;
+                },
+                [&](size_t off, size_t len, int slot, hipStream_t st) { down(off, len, slot, ChunkSink(st)); });
+            return rc;
+        }
+        up(0, total, 0, stream);
+        H2_TRY(run(0, total, 0, stream));
+        down(0, total, 0, ChunkSink(stream));
+        H2_HIP(hipStreamSynchronize(stream));
+        return H2_OK;
+    }
+};
+
+// h2_ntt / h2_intt / h2_intt_to / h2_msm_intt: the 2^log_n elements at `src` transformed into `d_a` (buf_a; scratch: buf_b),
+// every output times `divisor` when there is one, and written to the result
+int host_ntt(HostCall& call, HostResult& res, const Fr* src, Fr* d_a, const uint64_t omega[4], const uint64_t* divisor, uint32_t log_n) {
+    Fr* d_t = (Fr*)call.ctx->buf_b.get(sizeof(Fr) << log_n);
+    Fr post3[3];
+    if (divisor) post3[0] = post3[1] = post3[2] = fr_from_u64x4(divisor);
+    H2_TRY(dev_ntt_impl(call.ctx, src, d_a, d_t, 1u << log_n, omega, log_n, nullptr, divisor ? post3 : nullptr, call.stream, true));
+    return res.write(d_a, call.stream);
+}
+const char* const BAD_LOG_N = "log_n exceeds the 2-adicity of Fr (S = 28)";
 
 void fr_to_u64x4(const Fr& v, uint64_t out[4]) {
     for (int i = 0; i < 4; i++) out[i] = (uint64_t)v.l[2 * i] | ((uint64_t)v.l[2 * i + 1] << 32);
@@ -337,37 +460,23 @@ size_t h2_library_memory_bytes(void) {
 // ------------------------------------------------------------------ NTT, host buffers
 int h2_ntt(uint64_t* a, const uint64_t omega[4], uint32_t log_n) {
     if (!a || !omega) return bad("h2_ntt: null argument");
+    if (log_n > 28) return bad(BAD_LOG_N);
     return guarded([&] {
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        size_t bytes = sizeof(Fr) << log_n;
-        Fr* d_a = (Fr*)ctx->buf_a.get(bytes);
-        Fr* d_t = (Fr*)ctx->buf_b.get(bytes);
-        host_upload(d_a, a, bytes, ctx->stream);
-        int rc = dev_ntt_impl(ctx, d_a, d_a, d_t, 1u << log_n, omega, log_n, nullptr, nullptr, ctx->stream, true);
-        if (rc != H2_OK) return rc;
-        host_download(a, d_a, bytes, ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        HostCall call;
+        HostResult res(a, (size_t)1 << log_n, {a});
+        Fr* d_a = (Fr*)call.upload(call.ctx->buf_a, a, sizeof(Fr) << log_n);
+        return host_ntt(call, res, d_a, d_a, omega, nullptr, log_n);
     });
 }
 
 int h2_intt(uint64_t* a, const uint64_t omega_inv[4], const uint64_t divisor[4], uint32_t log_n) {
     if (!a || !omega_inv || !divisor) return bad("h2_intt: null argument");
+    if (log_n > 28) return bad(BAD_LOG_N);
     return guarded([&] {
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        size_t bytes = sizeof(Fr) << log_n;
-        Fr* d_a = (Fr*)ctx->buf_a.get(bytes);
-        Fr* d_t = (Fr*)ctx->buf_b.get(bytes);
-        Fr d = fr_from_u64x4(divisor);
-        Fr post3[3] = {d, d, d};
-        host_upload(d_a, a, bytes, ctx->stream);
-        int rc = dev_ntt_impl(ctx, d_a, d_a, d_t, 1u << log_n, omega_inv, log_n, nullptr, post3, ctx->stream, true);
-        if (rc != H2_OK) return rc;
-        host_download(a, d_a, bytes, ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        HostCall call;
+        HostResult res(a, (size_t)1 << log_n, {a});
+        Fr* d_a = (Fr*)call.upload(call.ctx->buf_a, a, sizeof(Fr) << log_n);
+        return host_ntt(call, res, d_a, d_a, omega_inv, divisor, log_n);
     });
 }
 
@@ -375,26 +484,12 @@ int h2_intt(uint64_t* a, const uint64_t omega_inv[4], const uint64_t divisor[4],
 // column): the values are read where they are, the coefficients written to `out` -- no host copy of the column first
 int h2_intt_to(const uint64_t* a, uint64_t* out, const uint64_t omega_inv[4], const uint64_t divisor[4], uint32_t log_n) {
     if (!a || !out || !omega_inv || !divisor) return bad("h2_intt_to: null argument");
+    if (log_n > 28) return bad(BAD_LOG_N);
     return guarded([&] {
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        size_t bytes = sizeof(Fr) << log_n;
-        Prefault pf((const void*)out == (const void*)a ? nullptr : out, bytes);
-        Fr* d_a = (Fr*)ctx->buf_a.get(bytes);
-        Fr* d_t = (Fr*)ctx->buf_b.get(bytes);
-        Fr d = fr_from_u64x4(divisor);
-        Fr post3[3] = {d, d, d};
-        const Fr* src = resident_operand(ctx, a, (size_t)1 << log_n);
-        if (!src) {
-            host_upload(d_a, a, bytes, ctx->stream);
-            src = d_a;
-        }
-        int rc = dev_ntt_impl(ctx, src, d_a, d_t, 1u << log_n, omega_inv, log_n, nullptr, post3, ctx->stream, true);
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(out, d_a, bytes, ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        HostCall call;
+        HostResult res(out, (size_t)1 << log_n, {a});
+        Fr* d_a = (Fr*)call.ctx->buf_a.get(sizeof(Fr) << log_n);
+        return host_ntt(call, res, call.in(call.ctx->buf_a, a, (size_t)1 << log_n), d_a, omega_inv, divisor, log_n);
     });
 }
 
@@ -402,26 +497,19 @@ int h2_coeff_to_extended(const uint64_t* coeffs, uint64_t* out, uint32_t k, uint
                          const uint64_t g_coset[4], const uint64_t g_coset_inv[4], const uint64_t extended_omega[4]) {
     if (!coeffs || !out || !g_coset || !g_coset_inv || !extended_omega) return bad("h2_coeff_to_extended: null argument");
     if (extended_k < k) return bad("h2_coeff_to_extended: extended_k < k");
+    if (extended_k > 28) return bad(BAD_LOG_N);
     return guarded([&] {
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        size_t in_bytes = sizeof(Fr) << k, ext_bytes = sizeof(Fr) << extended_k;
-        Prefault pf(out, ext_bytes);
-        Fr* d_in = (Fr*)ctx->buf_a.get(ext_bytes);
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        HostResult res(out, (size_t)1 << extended_k, {coeffs});
+        size_t ext_bytes = sizeof(Fr) << extended_k;
+        Fr* d_in = (Fr*)ctx->buf_a.get(ext_bytes);      // (the coefficients are staged at its start)
         Fr* d_t = (Fr*)ctx->buf_b.get(ext_bytes);
         // into_coset = true: coset_powers = [g_coset, g_coset_inv] (domain.rs:383-385)
         Fr pre3[3] = {fr_from_u64x4(g_coset), fr_from_u64x4(g_coset), fr_from_u64x4(g_coset_inv)};
-        const Fr* src = resident_operand(ctx, coeffs, (size_t)1 << k);
-        if (!src) {
-            host_upload(d_in, coeffs, in_bytes, ctx->stream);
-            src = d_in;
-        }
-        int rc = dev_ntt_impl(ctx, src, d_in, d_t, 1u << k, extended_omega, extended_k, pre3, nullptr, ctx->stream, true);
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(out, d_in, ext_bytes, ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        const Fr* src = call.in(ctx->buf_a, coeffs, (size_t)1 << k);
+        H2_TRY(dev_ntt_impl(ctx, src, d_in, d_t, 1u << k, extended_omega, extended_k, pre3, nullptr, call.stream, true));
+        return res.write(d_in, call.stream);
     });
 }
 
@@ -430,22 +518,18 @@ int h2_extended_to_coeff(const uint64_t* a, uint64_t* out, size_t out_len, uint3
                          const uint64_t extended_omega_inv[4], const uint64_t extended_ifft_divisor[4]) {
     if (!a || !out || !g_coset || !g_coset_inv || !extended_omega_inv || !extended_ifft_divisor)
         return bad("h2_extended_to_coeff: null argument");
+    if (extended_k > 28) return bad(BAD_LOG_N);
     if (out_len > ((size_t)1 << extended_k)) return bad("h2_extended_to_coeff: out_len exceeds the extended domain");
     return guarded([&] {
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        HostResult res(out, out_len, {a});
         size_t ext_bytes = sizeof(Fr) << extended_k;
-        Prefault pf(out == a ? nullptr : out, out_len * sizeof(Fr));
-        Fr* d_a = (Fr*)ctx->buf_a.get(ext_bytes);
+        Fr* d_a = (Fr*)call.upload(ctx->buf_a, a, ext_bytes);
         Fr* d_t = (Fr*)ctx->buf_b.get(ext_bytes);
-        host_upload(d_a, a, ext_bytes, ctx->stream);
-        int rc = dev_extended_to_coeff_impl(ctx, d_a, d_t, extended_k, g_coset, g_coset_inv, extended_omega_inv,
-                                            extended_ifft_divisor, ctx->stream, true);
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(out, d_a, out_len * sizeof(Fr), ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        H2_TRY(dev_extended_to_coeff_impl(ctx, d_a, d_t, extended_k, g_coset, g_coset_inv, extended_omega_inv,
+                                          extended_ifft_divisor, call.stream, true));
+        return res.write(d_a, call.stream);
     });
 }
 
@@ -453,33 +537,16 @@ int h2_extended_to_coeff(const uint64_t* a, uint64_t* out, size_t out_len, uint3
 static int host_batch_mont(uint64_t* a, size_t n, bool to_mont) {
     if (!a && n) return bad("h2_batch_mont: null argument");
     return guarded([&] {
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        size_t bytes = n * sizeof(Fr);
         if (n == 0) return (int)H2_OK;
-        if (use_pipeline(n, {a})) {
-            Fr* slots = (Fr*)ctx->buf_a.get(2 * PIPE_CHUNK * sizeof(Fr));
-            int rc = H2_OK;
-            pipeline_chunks(ctx, n,
-                [&](size_t off, size_t len, int slot, hipStream_t st) {
-                    host_upload(slots + slot * PIPE_CHUNK, a + 4 * off, len * sizeof(Fr), st);
-                },
-                [&](size_t, size_t len, int slot, hipStream_t st) {
-                    int r = batch_mont_launch(slots + slot * PIPE_CHUNK, len, to_mont, st);
-                    if (r != H2_OK) rc = r;
-                },
-                [&](size_t off, size_t len, int slot, hipStream_t st) {
-                    host_download(a + 4 * off, slots + slot * PIPE_CHUNK, len * sizeof(Fr), st);
-                });
-            return rc;
-        }
-        Fr* d_a = (Fr*)ctx->buf_a.get(bytes);
-        host_upload(d_a, a, bytes, ctx->stream);
-        int rc = batch_mont_launch(d_a, n, to_mont, ctx->stream);
-        if (rc != H2_OK) return rc;
-        host_download(a, d_a, bytes, ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        HostCall call;
+        HostResult res(a, n, {a});
+        const bool pipe = use_pipeline(n, {a});
+        const size_t chunk = pipe ? PIPE_CHUNK : n;
+        Fr* slots = (Fr*)call.ctx->buf_a.get((pipe ? 2 * PIPE_CHUNK : n) * sizeof(Fr));
+        return call.chunked(n, pipe,
+            [&](size_t off, size_t len, int slot, hipStream_t st) { host_upload(slots + slot * chunk, a + 4 * off, len * sizeof(Fr), st); },
+            [&](size_t, size_t len, int slot, hipStream_t st) { return batch_mont_launch(slots + slot * chunk, len, to_mont, st); },
+            [&](size_t off, size_t len, int slot, const ChunkSink& to) { to(res, off, len, slots + slot * chunk); });
     });
 }
 int h2_batch_mont(uint64_t* a, size_t n) { return host_batch_mont(a, n, true); }
@@ -490,92 +557,48 @@ int h2_eval_op(int op, uint64_t* res, const uint64_t* l, const uint64_t* r, int3
                const uint64_t c[4]) {
     if (!res) return bad("h2_eval_op: null result");
     return guarded([&] {
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        size_t bytes = size * sizeof(Fr);
         if (size == 0) return (int)H2_OK;
-        const Fr* res_l = resident_operand(ctx, l, size);
-        const Fr* res_r = resident_operand(ctx, r, size);
-        if (l_rot == 0 && r_rot == 0 && use_pipeline(size, {res, res_l ? nullptr : (const void*)l, res_r ? nullptr : (const void*)r})) {
-            // no rotation: element i depends on element i of the operands only -- chunk by chunk, both directions of PCIe at once
-            Fr* sl = (l && !res_l) ? (Fr*)ctx->buf_b.get(2 * PIPE_CHUNK * sizeof(Fr)) : nullptr;
-            Fr* sr = (r && !res_r) ? (Fr*)ctx->buf_c.get(2 * PIPE_CHUNK * sizeof(Fr)) : nullptr;
-            Fr* so = (Fr*)ctx->buf_a.get(2 * PIPE_CHUNK * sizeof(Fr));
-            int rc = H2_OK;
-            pipeline_chunks(ctx, size,
-                [&](size_t off, size_t len, int slot, hipStream_t st) {
-                    if (sl) host_upload(sl + slot * PIPE_CHUNK, l + 4 * off, len * sizeof(Fr), st);
-                    if (sr) host_upload(sr + slot * PIPE_CHUNK, r + 4 * off, len * sizeof(Fr), st);
-                },
-                [&](size_t off, size_t len, int slot, hipStream_t st) {
-                    const Fr* pl = !l ? nullptr : (res_l ? res_l + off : sl + slot * PIPE_CHUNK);
-                    const Fr* pr = !r ? nullptr : (res_r ? res_r + off : sr + slot * PIPE_CHUNK);
-                    int rr = eval_op_launch(op, so + slot * PIPE_CHUNK, pl, pr, 0, 0, len, c, st);
-                    if (rr != H2_OK) rc = rr;
-                },
-                [&](size_t off, size_t len, int slot, hipStream_t st) {
-                    host_download(res + 4 * off, so + slot * PIPE_CHUNK, len * sizeof(Fr), st);
-                });
-            return rc;
-        }
-        Prefault pf((const void*)res == (const void*)l || (const void*)res == (const void*)r ? nullptr : res, bytes);
-        Fr* d_res = (Fr*)ctx->buf_a.get(bytes);
-        const Fr* d_l = res_l;
-        const Fr* d_r = res_r;
-        if (l && !d_l) {
-            Fr* up = (Fr*)ctx->buf_b.get(bytes);
-            host_upload(up, l, bytes, ctx->stream);
-            d_l = up;
-        }
-        if (r && !d_r) {
-            Fr* up = (Fr*)ctx->buf_c.get(bytes);
-            host_upload(up, r, bytes, ctx->stream);
-            d_r = up;
-        }
-        int rc = eval_op_launch(op, d_res, d_l, d_r, l_rot, r_rot, size, c, ctx->stream);
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(res, d_res, bytes, ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        HostResult out(res, size, {l, r});
+        const Fr* res_l = call.resident(l, size);
+        const Fr* res_r = call.resident(r, size);
+        // no rotation: element i depends on element i of the operands only -- chunk by chunk, both directions of PCIe at once
+        const bool pipe = l_rot == 0 && r_rot == 0 &&
+                          use_pipeline(size, {res, res_l ? nullptr : (const void*)l, res_r ? nullptr : (const void*)r});
+        const size_t chunk = pipe ? PIPE_CHUNK : size, stage_bytes = (pipe ? 2 * PIPE_CHUNK : size) * sizeof(Fr);
+        Fr* so = (Fr*)ctx->buf_a.get(stage_bytes);
+        Fr* sl = (l && !res_l) ? (Fr*)ctx->buf_b.get(stage_bytes) : nullptr;
+        Fr* sr = (r && !res_r) ? (Fr*)ctx->buf_c.get(stage_bytes) : nullptr;
+        return call.chunked(size, pipe,
+            [&](size_t off, size_t len, int slot, hipStream_t st) {
+                if (sl) host_upload(sl + slot * chunk, l + 4 * off, len * sizeof(Fr), st);
+                if (sr) host_upload(sr + slot * chunk, r + 4 * off, len * sizeof(Fr), st);
+            },
+            [&](size_t off, size_t len, int slot, hipStream_t st) {
+                const Fr* pl = !l ? nullptr : (res_l ? res_l + off : sl + slot * chunk);
+                const Fr* pr = !r ? nullptr : (res_r ? res_r + off : sr + slot * chunk);
+                return eval_op_launch(op, so + slot * chunk, pl, pr, l_rot, r_rot, len, c, st);
+            },
+            [&](size_t off, size_t len, int slot, const ChunkSink& to) { to(out, off, len, so + slot * chunk); });
     });
 }
 
 int h2_divide_by_vanishing_poly(uint64_t* a, size_t size, const uint64_t* t_evaluations, size_t t_len) {
     if (!a || !t_evaluations) return bad("h2_divide_by_vanishing_poly: null argument");
     return guarded([&] {
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
         if (size == 0) return (int)H2_OK;
-        if (t_len && PIPE_CHUNK % t_len == 0 && use_pipeline(size, {a})) {
-            // a[i] *= t[i % t_len]: a chunk that starts at a multiple of t_len sees the table from its first entry
-            Fr* slots = (Fr*)ctx->buf_a.get(2 * PIPE_CHUNK * sizeof(Fr));
-            Fr* d_t = (Fr*)ctx->buf_b.get(t_len * sizeof(Fr));
-            host_upload(d_t, t_evaluations, t_len * sizeof(Fr), ctx->stream);
-            H2_HIP(hipStreamSynchronize(ctx->stream));
-            int rc = H2_OK;
-            pipeline_chunks(ctx, size,
-                [&](size_t off, size_t len, int slot, hipStream_t st) {
-                    host_upload(slots + slot * PIPE_CHUNK, a + 4 * off, len * sizeof(Fr), st);
-                },
-                [&](size_t, size_t len, int slot, hipStream_t st) {
-                    int r = divide_by_vanishing_launch(slots + slot * PIPE_CHUNK, len, d_t, t_len, st);
-                    if (r != H2_OK) rc = r;
-                },
-                [&](size_t off, size_t len, int slot, hipStream_t st) {
-                    host_download(a + 4 * off, slots + slot * PIPE_CHUNK, len * sizeof(Fr), st);
-                });
-            return rc;
-        }
-        Fr* d_a = (Fr*)ctx->buf_a.get(size * sizeof(Fr));
-        Fr* d_t = (Fr*)ctx->buf_b.get(t_len * sizeof(Fr));
-        host_upload(d_a, a, size * sizeof(Fr), ctx->stream);
-        host_upload(d_t, t_evaluations, t_len * sizeof(Fr), ctx->stream);
-        int rc = divide_by_vanishing_launch(d_a, size, d_t, t_len, ctx->stream);
-        if (rc != H2_OK) return rc;
-        host_download(a, d_a, size * sizeof(Fr), ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        HostCall call;
+        HostResult res(a, size, {a});
+        // a[i] *= t[i % t_len]: a chunk that starts at a multiple of t_len sees the table from its first entry
+        const bool pipe = t_len && PIPE_CHUNK % t_len == 0 && use_pipeline(size, {a});
+        const size_t chunk = pipe ? PIPE_CHUNK : size;
+        Fr* slots = (Fr*)call.ctx->buf_a.get((pipe ? 2 * PIPE_CHUNK : size) * sizeof(Fr));
+        const Fr* d_t = (const Fr*)call.upload(call.ctx->buf_b, t_evaluations, t_len * sizeof(Fr));   // (on the stream of every `run`)
+        return call.chunked(size, pipe,
+            [&](size_t off, size_t len, int slot, hipStream_t st) { host_upload(slots + slot * chunk, a + 4 * off, len * sizeof(Fr), st); },
+            [&](size_t, size_t len, int slot, hipStream_t st) { return divide_by_vanishing_launch(slots + slot * chunk, len, d_t, t_len, st); },
+            [&](size_t off, size_t len, int slot, const ChunkSink& to) { to(res, off, len, slots + slot * chunk); });
     });
 }
 
@@ -587,8 +610,8 @@ int h2_msm(const uint64_t* scalars, const uint64_t* bases, size_t n, uint32_t ma
             msm_identity(out_xyz);
             return (int)H2_OK;
         }
-        DeviceLease lease;
-        return msm_host(lease.ctx, scalars, bases, n, max_bits, out_xyz);
+        HostCall call;
+        return msm_host(call.ctx, scalars, bases, n, max_bits, out_xyz);
     });
 }
 
@@ -639,28 +662,18 @@ int h2_msm_multi(const uint64_t* scalars, const uint64_t* bases, size_t n, uint3
 int h2_msm_intt(uint64_t* scalars, const uint64_t* bases, size_t n, uint32_t max_bits, const uint64_t omega_inv[4],
                 const uint64_t divisor[4], uint32_t log_n, uint64_t out_xyz[12]) {
     if (!out_xyz || !scalars || !bases || !omega_inv || !divisor) return bad("h2_msm_intt: null argument");
+    if (log_n > 28) return bad(BAD_LOG_N);
     if (n != ((size_t)1 << log_n)) return bad("h2_msm_intt: n != 2^log_n");
     return guarded([&] {
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        size_t sbytes = n * sizeof(Fr);
+        HostCall call;
+        HostResult res(scalars, n, {scalars});
         // one upload of the scalars feeds both the MSM and the iNTT (arithmetic.rs:402-404)
-        Fr* d_s = (Fr*)ctx->buf_a.get(sbytes);
-        Fr* d_t = (Fr*)ctx->buf_b.get(sbytes);
-        host_upload(d_s, scalars, sbytes, ctx->stream);
-        int rc = H2_OK;
+        Fr* d_s = (Fr*)call.upload(call.ctx->buf_a, scalars, n * sizeof(Fr));
         if (max_bits == 0)
             msm_identity(out_xyz);
         else
-            rc = msm_host_resident_scalars(ctx, d_s, bases, n, max_bits, out_xyz);
-        if (rc != H2_OK) return rc;
-        Fr d = fr_from_u64x4(divisor);
-        Fr post3[3] = {d, d, d};
-        rc = dev_ntt_impl(ctx, d_s, d_s, d_t, (uint32_t)n, omega_inv, log_n, nullptr, post3, ctx->stream, true);
-        if (rc != H2_OK) return rc;
-        host_download(scalars, d_s, sbytes, ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+            H2_TRY(msm_host_resident_scalars(call.ctx, d_s, bases, n, max_bits, out_xyz));
+        return host_ntt(call, res, d_s, d_s, omega_inv, divisor, log_n);
     });
 }
 
@@ -932,16 +945,11 @@ int h2_random_fr(const uint8_t key[32], size_t n, uint64_t* out) {
     if ((!out && n) || !key) return bad("h2_random_fr: null argument");
     return guarded([&] {
         if (n == 0) return (int)H2_OK;
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Prefault pf(out, n * sizeof(Fr));
-        uint64_t* d = (uint64_t*)ctx->buf_a.get(n * sizeof(Fr));
-        int rc = random_fr_launch(key, n, d, ctx->stream);
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(out, d, n * sizeof(Fr), ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        HostCall call;
+        HostResult res(out, n);
+        uint64_t* d = (uint64_t*)call.ctx->buf_a.get(n * sizeof(Fr));
+        H2_TRY(random_fr_launch(key, n, d, call.stream));
+        return res.write((const Fr*)d, call.stream);
     });
 }
 
@@ -1018,16 +1026,10 @@ int h2_dev_eval_polynomial_batch(const void* const* d_polys, size_t count, size_
 int h2_eval_polynomial(const uint64_t* poly, size_t n, const uint64_t point[4], uint64_t out[4]) {
     if (!point || !out || (n && !poly)) return bad("h2_eval_polynomial: null argument");
     return guarded([&] {
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Fr* tmp = (Fr*)ctx->buf_d.get(eval_polynomial_tmp_elems(n) * sizeof(Fr));
-        const Fr* d = n ? resident_operand(ctx, poly, n) : nullptr;
-        if (!d) {
-            Fr* up = (Fr*)ctx->buf_a.get((n ? n : 1) * sizeof(Fr));
-            if (n) host_upload(up, poly, n * sizeof(Fr), ctx->stream);
-            d = up;
-        }
-        return eval_polynomial_launch(d, n, point, tmp, out, ctx->stream);
+        HostCall call;
+        Fr* tmp = (Fr*)call.ctx->buf_d.get(eval_polynomial_tmp_elems(n) * sizeof(Fr));
+        const Fr* d = n ? call.in(call.ctx->buf_a, poly, n) : (const Fr*)call.ctx->buf_a.get(sizeof(Fr));
+        return eval_polynomial_launch(d, n, point, tmp, out, call.stream);
     });
 }
 
@@ -1045,25 +1047,10 @@ int h2_eval_polynomial_batch(const uint64_t* const* polys, size_t count, size_t 
             memset(out, 0, 32 * count);
             return (int)H2_OK;
         }
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        std::vector<const Fr*> d(count);
-        std::map<const uint64_t*, size_t> staged;        // host vector -> its slot in the upload block
-        for (size_t j = 0; j < count; j++) {
-            d[j] = resident_operand(ctx, polys[j], n);
-            if (!d[j] && !staged.count(polys[j])) {
-                const size_t slot = staged.size();
-                staged[polys[j]] = slot;
-            }
-        }
-        if (!staged.empty()) {
-            Fr* up = (Fr*)ctx->buf_a.get(staged.size() * n * sizeof(Fr));
-            for (auto& kv : staged) host_upload(up + kv.second * n, kv.first, n * sizeof(Fr), ctx->stream);
-            for (size_t j = 0; j < count; j++)
-                if (!d[j]) d[j] = up + staged[polys[j]] * n;
-        }
-        Fr* tmp = (Fr*)ctx->buf_d.get(eval_polynomial_batch_tmp_bytes(count, n));
-        return eval_polynomial_batch_launch(d.data(), count, n, points, tmp, out, ctx->stream);
+        HostCall call;
+        std::vector<const Fr*> d = call.in_packed(call.ctx->buf_a, polys, count, n);
+        Fr* tmp = (Fr*)call.ctx->buf_d.get(eval_polynomial_batch_tmp_bytes(count, n));
+        return eval_polynomial_batch_launch(d.data(), count, n, points, tmp, out, call.stream);
     });
 }
 
@@ -1079,16 +1066,12 @@ int h2_batch_invert(uint64_t* a, size_t n) {
     if (n && !a) return bad("h2_batch_invert: null argument");
     return guarded([&] {
         if (n == 0) return (int)H2_OK;
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Fr* d = (Fr*)ctx->buf_a.get(n * sizeof(Fr));
-        Fr* t = (Fr*)ctx->buf_b.get(n * sizeof(Fr));
-        host_upload(d, a, n * sizeof(Fr), ctx->stream);
-        int rc = batch_invert_launch(d, t, n, ctx->stream);
-        if (rc != H2_OK) return rc;
-        host_download(a, d, n * sizeof(Fr), ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        HostCall call;
+        HostResult res(a, n, {a});
+        Fr* d = (Fr*)call.upload(call.ctx->buf_a, a, n * sizeof(Fr));
+        Fr* t = (Fr*)call.ctx->buf_b.get(n * sizeof(Fr));
+        H2_TRY(batch_invert_launch(d, t, n, call.stream));
+        return res.write(d, call.stream);
     });
 }
 
@@ -1106,23 +1089,13 @@ int h2_kate_division(const uint64_t* a, size_t n, const uint64_t b[4], uint64_t*
     if (!b || (n >= 2 && (!a || !q))) return bad("h2_kate_division: null argument");
     return guarded([&] {
         if (n < 2) return (int)H2_OK;
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Prefault pf(q == a ? nullptr : q, (n - 1) * sizeof(Fr));
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        HostResult res(q, n - 1, {a});
         Fr* d_q = (Fr*)ctx->buf_b.get(n * sizeof(Fr));
         Fr* tmp = (Fr*)ctx->buf_d.get(scan_tmp_elems(n) * sizeof(Fr));
-        const Fr* d_a = resident_operand(ctx, a, n);
-        if (!d_a) {
-            Fr* up = (Fr*)ctx->buf_a.get(n * sizeof(Fr));
-            host_upload(up, a, n * sizeof(Fr), ctx->stream);
-            d_a = up;
-        }
-        int rc = kate_division_launch(d_a, n, b, d_q, tmp, ctx->stream);
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(q, d_q, (n - 1) * sizeof(Fr), ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        H2_TRY(kate_division_launch(call.in(ctx->buf_a, a, n), n, b, d_q, tmp, call.stream));
+        return res.write(d_q, call.stream);
     });
 }
 
@@ -1137,24 +1110,25 @@ int h2_dev_prefix_product(const void* d_f, size_t n, const uint64_t init[4], voi
     });
 }
 
-int h2_prefix_product(const uint64_t* f, size_t n, const uint64_t init[4], uint64_t* z) {
-    if (!init || (n && !z) || (n > 1 && !f)) return bad("h2_prefix_product: null argument");
+// h2_prefix_product / h2_prefix_sum: z[0] = init, z[i + 1] = z[i] (*|+) f[i] -- n - 1 elements up, one scan, n down
+typedef int (*ScanLaunch)(const Fr*, size_t, const uint64_t*, Fr*, Fr*, hipStream_t);
+static int host_prefix_scan(ScanLaunch scan, const char* null_msg, const uint64_t* f, size_t n, const uint64_t init[4], uint64_t* z) {
+    if (!init || (n && !z) || (n > 1 && !f)) return bad(null_msg);
     return guarded([&] {
         if (n == 0) return (int)H2_OK;
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Prefault pf(z, n * sizeof(Fr));
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        HostResult res(z, n, {f});
         Fr* d_f = (Fr*)ctx->buf_a.get(n * sizeof(Fr));
         Fr* d_z = (Fr*)ctx->buf_b.get(n * sizeof(Fr));
         Fr* tmp = (Fr*)ctx->buf_d.get(scan_tmp_elems(n) * sizeof(Fr));
-        if (n > 1) host_upload(d_f, f, (n - 1) * sizeof(Fr), ctx->stream);
-        int rc = prefix_product_launch(d_f, n, init, d_z, tmp, ctx->stream);
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(z, d_z, n * sizeof(Fr), ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        if (n > 1) host_upload(d_f, f, (n - 1) * sizeof(Fr), call.stream);
+        H2_TRY(scan(d_f, n, init, d_z, tmp, call.stream));
+        return res.write(d_z, call.stream);
     });
+}
+int h2_prefix_product(const uint64_t* f, size_t n, const uint64_t init[4], uint64_t* z) {
+    return host_prefix_scan(prefix_product_launch, "h2_prefix_product: null argument", f, n, init, z);
 }
 
 int h2_dev_lincomb(void* d_res, const void* const* d_polys, const uint64_t* coeffs, size_t count, size_t size,
@@ -1172,58 +1146,38 @@ int h2_lincomb(uint64_t* res, const uint64_t* const* polys, const uint64_t* coef
     for (size_t i = 0; i < count; i++)
         if (!polys[i]) return bad("h2_lincomb: null operand");
     return guarded([&] {
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        const size_t bytes = size * sizeof(Fr);
         if (count == 0 || size == 0) {
-            memset(res, 0, bytes);
+            memset(res, 0, size * sizeof(Fr));
             return (int)H2_OK;
         }
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        HostResult out(res, size, (const void* const*)polys, count);
         // operands inside a range registered with h2_poly_register are read where they lie on the device; the others cross PCIe
         std::vector<const Fr*> ptrs(count);
         std::vector<size_t> staged;                     // operands that have to be uploaded
         for (size_t i = 0; i < count; i++) {
-            ptrs[i] = resident_operand(ctx, polys[i], size);
+            ptrs[i] = call.resident(polys[i], size);
             if (!ptrs[i]) staged.push_back(i);
         }
         bool pinned_all = host_pinned(res);
         for (size_t j : staged) pinned_all = pinned_all && host_pinned(polys[j]);
-        if (pinned_all && use_pipeline(size, {})) {
-            // chunk by chunk: the operands' chunk c + 1 goes up while chunk c is combined and the result of chunk c - 1 comes down
-            Fr* sin = staged.empty() ? nullptr : (Fr*)ctx->buf_a.get(2 * staged.size() * PIPE_CHUNK * sizeof(Fr));
-            Fr* sout = (Fr*)ctx->buf_b.get(2 * PIPE_CHUNK * sizeof(Fr));
-            int rc = H2_OK;
-            pipeline_chunks(ctx, size,
-                [&](size_t off, size_t len, int slot, hipStream_t st) {
-                    for (size_t j = 0; j < staged.size(); j++)
-                        H2_HIP(hipMemcpyAsync(sin + (slot * staged.size() + j) * PIPE_CHUNK, polys[staged[j]] + 4 * off, len * sizeof(Fr),
-                                              hipMemcpyHostToDevice, st));
-                },
-                [&](size_t off, size_t len, int slot, hipStream_t st) {
-                    std::vector<const Fr*> at(count);
-                    for (size_t i = 0; i < count; i++) at[i] = ptrs[i] ? ptrs[i] + off : nullptr;
-                    for (size_t j = 0; j < staged.size(); j++) at[staged[j]] = sin + (slot * staged.size() + j) * PIPE_CHUNK;
-                    int r = lincomb_launch(sout + slot * PIPE_CHUNK, at.data(), coeffs, count, len, st);
-                    if (r != H2_OK) rc = r;
-                },
-                [&](size_t off, size_t len, int slot, hipStream_t st) {
-                    host_download(res + 4 * off, sout + slot * PIPE_CHUNK, len * sizeof(Fr), st);
-                });
-            return rc;
-        }
-        Prefault pf(count && (const void*)res == (const void*)polys[0] ? nullptr : res, bytes);
-        Fr* d_all = staged.empty() ? nullptr : (Fr*)ctx->buf_a.get(bytes * staged.size());
-        Fr* d_res = (Fr*)ctx->buf_b.get(bytes);
-        for (size_t j = 0; j < staged.size(); j++) {
-            ptrs[staged[j]] = d_all + j * size;
-            host_upload(d_all + j * size, polys[staged[j]], bytes, ctx->stream);
-        }
-        int rc = lincomb_launch(d_res, ptrs.data(), coeffs, count, size, ctx->stream);
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(res, d_res, bytes, ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        // chunk by chunk: the operands' chunk c + 1 goes up while chunk c is combined and the result of chunk c - 1 comes down
+        const bool pipe = pinned_all && use_pipeline(size, {});
+        const size_t chunk = pipe ? PIPE_CHUNK : size, slots = pipe ? 2 : 1, ns = staged.size();
+        Fr* sin = ns ? (Fr*)ctx->buf_a.get(slots * ns * chunk * sizeof(Fr)) : nullptr;
+        Fr* sout = (Fr*)ctx->buf_b.get(slots * chunk * sizeof(Fr));
+        return call.chunked(size, pipe,
+            [&](size_t off, size_t len, int slot, hipStream_t st) {
+                for (size_t j = 0; j < ns; j++) host_upload(sin + (slot * ns + j) * chunk, polys[staged[j]] + 4 * off, len * sizeof(Fr), st);
+            },
+            [&](size_t off, size_t len, int slot, hipStream_t st) {
+                std::vector<const Fr*> at(count);
+                for (size_t i = 0; i < count; i++) at[i] = ptrs[i] ? ptrs[i] + off : nullptr;
+                for (size_t j = 0; j < ns; j++) at[staged[j]] = sin + (slot * ns + j) * chunk;
+                return lincomb_launch(sout + slot * chunk, at.data(), coeffs, count, len, st);
+            },
+            [&](size_t off, size_t len, int slot, const ChunkSink& to) { to(out, off, len, sout + slot * chunk); });
     });
 }
 
@@ -1256,22 +1210,23 @@ int h2_quotient_sum(uint64_t* out, size_t n, size_t n_sets, const size_t* counts
             memset(out, 0, bytes);
             return (int)H2_OK;
         }
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Prefault pf(out, bytes);
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        hipStream_t s = call.stream;
+        HostResult res(out, n, (const void* const*)polys, total);
         size_t max_staged = 0, max_low = 0;
         {
             size_t at = 0;
-            for (size_t s = 0; s < n_sets; s++) {
+            for (size_t set = 0; set < n_sets; set++) {
                 size_t st = 0;
-                for (size_t i = 0; i < counts[s]; i++)
-                    if (!resident_operand(ctx, polys[at + i], n)) st++;
+                for (size_t i = 0; i < counts[set]; i++)
+                    if (!call.resident(polys[at + i], n)) st++;
                 max_staged = std::max(max_staged, st);
-                max_low = std::max(max_low, low_counts[s]);
-                at += counts[s];
+                max_low = std::max(max_low, low_counts[set]);
+                at += counts[set];
             }
         }
-        Fr* d_up = max_staged ? (Fr*)ctx->buf_a.get(bytes * max_staged) : nullptr;
+        if (max_staged) ctx->buf_a.get(bytes * max_staged);        // (every set's staged operands fit: no set moves the block)
         Fr* cur = (Fr*)ctx->buf_b.get(bytes);
         Fr* nxt = (Fr*)ctx->buf_c.get(bytes);
         // one block: the running sum, the synthetic divisions' scratch, a set's low coefficients
@@ -1279,54 +1234,33 @@ int h2_quotient_sum(uint64_t* out, size_t n, size_t n_sets, const size_t* counts
         Fr* acc = (Fr*)ctx->buf_d.get((n + tmp_elems + max_low) * sizeof(Fr));
         Fr* tmp = acc + n;
         Fr* d_low = tmp + tmp_elems;
-        H2_HIP(hipMemsetAsync(acc, 0, bytes, ctx->stream));
+        H2_HIP(hipMemsetAsync(acc, 0, bytes, s));
         size_t at = 0, at_low = 0, at_pt = 0;
-        for (size_t s = 0; s < n_sets; s++) {
-            const size_t count = counts[s];
-            std::vector<const Fr*> ptrs(count);
-            size_t st = 0;
-            for (size_t i = 0; i < count; i++) {
-                ptrs[i] = resident_operand(ctx, polys[at + i], n);
-                if (!ptrs[i]) {
-                    host_upload(d_up + st * n, polys[at + i], bytes, ctx->stream);
-                    ptrs[i] = d_up + st * n;
-                    st++;
-                }
+        for (size_t set = 0; set < n_sets; set++) {
+            const size_t count = counts[set];
+            if (count) {
+                std::vector<const Fr*> ptrs = call.in_packed(ctx->buf_a, polys + at, count, n);
+                H2_TRY(lincomb_launch(cur, ptrs.data(), coeffs + 4 * at, count, n, s));
+            } else {
+                H2_HIP(hipMemsetAsync(cur, 0, bytes, s));
             }
-            int rc = H2_OK;
-            if (count)
-                rc = lincomb_launch(cur, ptrs.data(), coeffs + 4 * at, count, n, ctx->stream);
-            else
-                H2_HIP(hipMemsetAsync(cur, 0, bytes, ctx->stream));
-            if (rc != H2_OK) return rc;
-            if (low_counts[s]) {
-                host_upload(d_low, low + 4 * at_low, low_counts[s] * sizeof(Fr), ctx->stream);
-                rc = eval_op_launch(H2_OP_SUB, cur, cur, d_low, 0, 0, low_counts[s], nullptr, ctx->stream);
-                if (rc != H2_OK) return rc;
+            if (low_counts[set]) {
+                host_upload(d_low, low + 4 * at_low, low_counts[set] * sizeof(Fr), s);
+                H2_TRY(eval_op_launch(H2_OP_SUB, cur, cur, d_low, 0, 0, low_counts[set], nullptr, s));
             }
-            for (size_t j = 0; j < point_counts[s]; j++) {
+            for (size_t j = 0; j < point_counts[set]; j++) {
                 const uint64_t* pt = points + 4 * (at_pt + j);
-                if (remainders) {
-                    rc = eval_polynomial_launch(cur, n, pt, tmp, remainders + 4 * (at_pt + j), ctx->stream);
-                    if (rc != H2_OK) return rc;
-                }
-                if (n >= 2) {
-                    rc = kate_division_launch(cur, n, pt, nxt, tmp, ctx->stream);      // n - 1 coefficients
-                    if (rc != H2_OK) return rc;
-                }
-                H2_HIP(hipMemsetAsync(nxt + (n - 1), 0, sizeof(Fr), ctx->stream));    // (resized as shplonk/prover.rs:118)
+                if (remainders) H2_TRY(eval_polynomial_launch(cur, n, pt, tmp, remainders + 4 * (at_pt + j), s));
+                if (n >= 2) H2_TRY(kate_division_launch(cur, n, pt, nxt, tmp, s));      // n - 1 coefficients
+                H2_HIP(hipMemsetAsync(nxt + (n - 1), 0, sizeof(Fr), s));    // (resized as shplonk/prover.rs:118)
                 std::swap(cur, nxt);
             }
-            rc = eval_op_launch(H2_OP_SUM, acc, acc, cur, 0, 0, n, nullptr, ctx->stream);
-            if (rc != H2_OK) return rc;
+            H2_TRY(eval_op_launch(H2_OP_SUM, acc, acc, cur, 0, 0, n, nullptr, s));
             at += count;
-            at_low += low_counts[s];
-            at_pt += point_counts[s];
+            at_low += low_counts[set];
+            at_pt += point_counts[set];
         }
-        pf.join();
-        host_download(out, acc, bytes, ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        return res.write(acc, s);
     });
 }
 
@@ -1348,49 +1282,38 @@ int h2_permutation_terms(uint64_t* num, uint64_t* den, const uint64_t* value, co
     if (n && (!num || !den || !value || !sigma || !beta || !gamma || !delta_pow || !omega)) return bad("h2_permutation_terms: null argument");
     return guarded([&] {
         if (n == 0) return (int)H2_OK;
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        const Fr* res_sigma = resident_operand(ctx, sigma, n);
-        const Fr* res_value = resident_operand(ctx, value, n);
-        Prefault pf_num(first ? num : nullptr, n * sizeof(Fr)), pf_den(first ? den : nullptr, n * sizeof(Fr));
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        const Fr* res_sigma = call.resident(sigma, n);
+        const Fr* res_value = call.resident(value, n);
+        // first == 0: num / den are read, multiplied into and written back -- inputs as well as results
+        HostResult r_num(num, n, {first ? nullptr : num}), r_den(den, n, {first ? nullptr : den});
         const bool pipe = use_pipeline(n, {num, den, res_value ? nullptr : (const void*)value, res_sigma ? nullptr : (const void*)sigma});
         const size_t chunk = pipe ? PIPE_CHUNK : n;
         Fr* s_num = (Fr*)ctx->buf_a.get(2 * chunk * sizeof(Fr));
         Fr* s_den = (Fr*)ctx->buf_b.get(2 * chunk * sizeof(Fr));
         Fr* s_val = res_value ? nullptr : (Fr*)ctx->buf_c.get(2 * chunk * sizeof(Fr));
         Fr* s_sig = res_sigma ? nullptr : (Fr*)ctx->buf_d.get(2 * chunk * sizeof(Fr));
-        int rc = H2_OK;
-        auto up = [&](size_t off, size_t len, int slot, hipStream_t st) {
-            if (s_val) host_upload(s_val + slot * chunk, value + 4 * off, len * sizeof(Fr), st);
-            if (s_sig) host_upload(s_sig + slot * chunk, sigma + 4 * off, len * sizeof(Fr), st);
-            if (!first) {
-                host_upload(s_num + slot * chunk, num + 4 * off, len * sizeof(Fr), st);
-                host_upload(s_den + slot * chunk, den + 4 * off, len * sizeof(Fr), st);
-            }
-        };
-        auto run = [&](size_t off, size_t len, int slot, hipStream_t st) {
-            // rows [off, off + len): the numerator's delta^c omega^i starts at delta_pow * omega^off
-            uint64_t dp[4];
-            fr_to_u64x4(fp_mul(fr_from_u64x4(delta_pow), fp_pow_u32(fr_from_u64x4(omega), (uint32_t)off)), dp);
-            int r = perm_terms_launch(s_num + slot * chunk, s_den + slot * chunk, res_value ? res_value + off : s_val + slot * chunk,
-                                      res_sigma ? res_sigma + off : s_sig + slot * chunk, len, beta, gamma, dp, omega, first, st);
-            if (r != H2_OK) rc = r;
-        };
-        auto down = [&](size_t off, size_t len, int slot, hipStream_t st) {
-            host_download(num + 4 * off, s_num + slot * chunk, len * sizeof(Fr), st);
-            host_download(den + 4 * off, s_den + slot * chunk, len * sizeof(Fr), st);
-        };
-        if (pipe) {
-            pipeline_chunks(ctx, n, up, run, down);
-        } else {
-            up(0, n, 0, ctx->stream);
-            run(0, n, 0, ctx->stream);
-            pf_num.join();
-            pf_den.join();
-            down(0, n, 0, ctx->stream);
-            H2_HIP(hipStreamSynchronize(ctx->stream));
-        }
-        return rc;
+        return call.chunked(n, pipe,
+            [&](size_t off, size_t len, int slot, hipStream_t st) {
+                if (s_val) host_upload(s_val + slot * chunk, value + 4 * off, len * sizeof(Fr), st);
+                if (s_sig) host_upload(s_sig + slot * chunk, sigma + 4 * off, len * sizeof(Fr), st);
+                if (!first) {
+                    host_upload(s_num + slot * chunk, num + 4 * off, len * sizeof(Fr), st);
+                    host_upload(s_den + slot * chunk, den + 4 * off, len * sizeof(Fr), st);
+                }
+            },
+            [&](size_t off, size_t len, int slot, hipStream_t st) {
+                // rows [off, off + len): the numerator's delta^c omega^i starts at delta_pow * omega^off
+                uint64_t dp[4];
+                fr_to_u64x4(fp_mul(fr_from_u64x4(delta_pow), fp_pow_u32(fr_from_u64x4(omega), (uint32_t)off)), dp);
+                return perm_terms_launch(s_num + slot * chunk, s_den + slot * chunk, res_value ? res_value + off : s_val + slot * chunk,
+                                         res_sigma ? res_sigma + off : s_sig + slot * chunk, len, beta, gamma, dp, omega, first, st);
+            },
+            [&](size_t off, size_t len, int slot, const ChunkSink& to) {
+                to(r_num, off, len, s_num + slot * chunk);
+                to(r_den, off, len, s_den + slot * chunk);
+            });
     });
 }
 
@@ -1410,43 +1333,32 @@ int h2_permutation_product(uint64_t* z, const uint64_t* const* values, const uin
         if (!values[j] || !sigmas[j]) return bad("h2_permutation_product: null column");
     return guarded([&] {
         if (n == 0) return (int)H2_OK;
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Prefault pf(z, n * sizeof(Fr));
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        hipStream_t s = call.stream;
+        std::vector<const void*> inputs(values, values + count);
+        inputs.insert(inputs.end(), sigmas, sigmas + count);
+        HostResult res(z, n, inputs.data(), inputs.size());
         const size_t bytes = n * sizeof(Fr);
         Fr* num = (Fr*)ctx->buf_a.get(bytes);
         Fr* den = (Fr*)ctx->buf_b.get(bytes);
-        Fr* s_val = (Fr*)ctx->buf_c.get(std::max(bytes, scan_tmp_elems(n) * sizeof(Fr)));
-        Fr* s_sig = (Fr*)ctx->buf_d.get(std::max(bytes, scan_tmp_elems(n) * sizeof(Fr)));
+        // (buf_c / buf_d: a column's staging first, then the scans' scratch)
+        Fr* tmp_c = (Fr*)ctx->buf_c.get(std::max(bytes, scan_tmp_elems(n) * sizeof(Fr)));
+        Fr* tmp_d = (Fr*)ctx->buf_d.get(std::max(bytes, scan_tmp_elems(n) * sizeof(Fr)));
         Fr dp = fr_from_u64x4(delta_pow);
         const Fr d = fr_from_u64x4(delta);
         for (size_t j = 0; j < count; j++) {
-            const Fr* value = resident_operand(ctx, values[j], n);
-            const Fr* sigma = resident_operand(ctx, sigmas[j], n);
-            if (!value) {
-                host_upload(s_val, values[j], bytes, ctx->stream);
-                value = s_val;
-            }
-            if (!sigma) {
-                host_upload(s_sig, sigmas[j], bytes, ctx->stream);
-                sigma = s_sig;
-            }
+            const Fr* value = call.in(ctx->buf_c, values[j], n);
+            const Fr* sigma = call.in(ctx->buf_d, sigmas[j], n);
             uint64_t dpj[4];
             fr_to_u64x4(dp, dpj);
-            int rc = perm_terms_launch(num, den, value, sigma, n, beta, gamma, dpj, omega, j == 0, ctx->stream);
-            if (rc != H2_OK) return rc;
+            H2_TRY(perm_terms_launch(num, den, value, sigma, n, beta, gamma, dpj, omega, j == 0, s));
             dp = fp_mul(dp, d);
         }
-        int rc = batch_invert_launch(den, s_val, n, ctx->stream);
-        if (rc != H2_OK) return rc;
-        rc = eval_op_launch(H2_OP_MUL, num, num, den, 0, 0, n, nullptr, ctx->stream);
-        if (rc != H2_OK) return rc;
-        rc = prefix_product_launch(num, n, init, den, s_sig, ctx->stream);      // z over the inverted denominators' block
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(z, den, bytes, ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        H2_TRY(batch_invert_launch(den, tmp_c, n, s));
+        H2_TRY(eval_op_launch(H2_OP_MUL, num, num, den, 0, 0, n, nullptr, s));
+        H2_TRY(prefix_product_launch(num, n, init, den, tmp_d, s));      // z over the inverted denominators' block
+        return res.write(den, s);
     });
 }
 
@@ -1487,23 +1399,7 @@ size_t h2_logup_scratch_bytes(size_t n) { return logup_scratch_bytes(n); }
 // plonk/logup/prover.rs:353-367, multiplicities :104-180, sigma columns plonk/permutation/keygen.rs:197-238,
 // distribute_powers_zeta poly/domain.rs:382-398): a host that keeps its vectors in memory needs no device pointer for any of them
 int h2_prefix_sum(const uint64_t* f, size_t n, const uint64_t init[4], uint64_t* z) {
-    if (!init || (n && !z) || (n > 1 && !f)) return bad("h2_prefix_sum: null argument");
-    return guarded([&] {
-        if (n == 0) return (int)H2_OK;
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Prefault pf((const void*)z == (const void*)f ? nullptr : z, n * sizeof(Fr));
-        Fr* d_f = (Fr*)ctx->buf_a.get(n * sizeof(Fr));
-        Fr* d_z = (Fr*)ctx->buf_b.get(n * sizeof(Fr));
-        Fr* tmp = (Fr*)ctx->buf_d.get(scan_tmp_elems(n) * sizeof(Fr));
-        if (n > 1) host_upload(d_f, f, (n - 1) * sizeof(Fr), ctx->stream);
-        int rc = prefix_sum_launch(d_f, n, init, d_z, tmp, ctx->stream);
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(z, d_z, n * sizeof(Fr), ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
-    });
+    return host_prefix_scan(prefix_sum_launch, "h2_prefix_sum: null argument", f, n, init, z);
 }
 
 // One grand-sum column of a logup lookup in ONE call (plonk/logup/prover.rs:243-347, `commit_z`, for one set of inputs):
@@ -1519,49 +1415,34 @@ int h2_logup_grand_sum(uint64_t* z, const uint64_t* const* inputs, size_t count,
         if (!inputs[j]) return bad("h2_logup_grand_sum: null input");
     return guarded([&] {
         if (n == 0) return (int)H2_OK;
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Prefault pf(z, n * sizeof(Fr));
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        hipStream_t s = call.stream;
+        std::vector<const void*> read(inputs, inputs + count);
+        read.push_back(table);
+        read.push_back(m);
+        HostResult res(z, n, read.data(), read.size());
         const size_t bytes = n * sizeof(Fr);
-        hipStream_t s = ctx->stream;
-        Fr* up = (Fr*)ctx->buf_a.get(bytes);
+        DevBuf& up = ctx->buf_a;                                   // one operand at a time is staged here
         Fr* term = (Fr*)ctx->buf_b.get(bytes);
         Fr* tmp = (Fr*)ctx->buf_c.get(bytes);
         Fr* acc = (Fr*)ctx->buf_d.get((2 * n + scan_tmp_elems(n)) * sizeof(Fr));
         Fr* d_z = acc + n;
         Fr* scan_tmp = d_z + n;
         H2_HIP(hipMemsetAsync(acc, 0, bytes, s));
-        auto operand = [&](const uint64_t* host) -> const Fr* {
-            const Fr* d = resident_operand(ctx, host, n);
-            if (d) return d;
-            host_upload(up, host, bytes, s);
-            return up;
-        };
-        int rc = H2_OK;
         for (size_t j = 0; j < count; j++) {
-            rc = eval_op_launch(H2_OP_SUM_C, term, operand(inputs[j]), nullptr, 0, 0, n, beta, s);     // beta + f_j
-            if (rc != H2_OK) return rc;
-            rc = batch_invert_launch(term, tmp, n, s);
-            if (rc != H2_OK) return rc;
-            rc = eval_op_launch(H2_OP_SUM, acc, acc, term, 0, 0, n, nullptr, s);
-            if (rc != H2_OK) return rc;
+            H2_TRY(eval_op_launch(H2_OP_SUM_C, term, call.in(up, inputs[j], n), nullptr, 0, 0, n, beta, s));     // beta + f_j
+            H2_TRY(batch_invert_launch(term, tmp, n, s));
+            H2_TRY(eval_op_launch(H2_OP_SUM, acc, acc, term, 0, 0, n, nullptr, s));
         }
         if (table) {
-            rc = eval_op_launch(H2_OP_SUM_C, term, operand(table), nullptr, 0, 0, n, beta, s);         // beta + t
-            if (rc != H2_OK) return rc;
-            rc = batch_invert_launch(term, tmp, n, s);
-            if (rc != H2_OK) return rc;
-            rc = eval_op_launch(H2_OP_MUL, term, term, operand(m), 0, 0, n, nullptr, s);               // m / (beta + t)
-            if (rc != H2_OK) return rc;
-            rc = eval_op_launch(H2_OP_SUB, acc, acc, term, 0, 0, n, nullptr, s);
-            if (rc != H2_OK) return rc;
+            H2_TRY(eval_op_launch(H2_OP_SUM_C, term, call.in(up, table, n), nullptr, 0, 0, n, beta, s));         // beta + t
+            H2_TRY(batch_invert_launch(term, tmp, n, s));
+            H2_TRY(eval_op_launch(H2_OP_MUL, term, term, call.in(up, m, n), 0, 0, n, nullptr, s));               // m / (beta + t)
+            H2_TRY(eval_op_launch(H2_OP_SUB, acc, acc, term, 0, 0, n, nullptr, s));
         }
-        rc = prefix_sum_launch(acc, n, init, d_z, scan_tmp, s);
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(z, d_z, bytes, s);
-        H2_HIP(hipStreamSynchronize(s));
-        return (int)H2_OK;
+        H2_TRY(prefix_sum_launch(acc, n, init, d_z, scan_tmp, s));
+        return res.write(d_z, s);
     });
 }
 
@@ -1569,15 +1450,11 @@ int h2_distribute_powers(uint64_t* a, size_t n, const uint64_t g[4]) {
     if ((n && !a) || !g) return bad("h2_distribute_powers: null argument");
     return guarded([&] {
         if (n == 0) return (int)H2_OK;
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Fr* d = (Fr*)ctx->buf_a.get(n * sizeof(Fr));
-        host_upload(d, a, n * sizeof(Fr), ctx->stream);
-        int rc = distribute_powers_launch(d, n, g, ctx->stream);
-        if (rc != H2_OK) return rc;
-        host_download(a, d, n * sizeof(Fr), ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        HostCall call;
+        HostResult res(a, n, {a});
+        Fr* d = (Fr*)call.upload(call.ctx->buf_a, a, n * sizeof(Fr));
+        H2_TRY(distribute_powers_launch(d, n, g, call.stream));
+        return res.write(d, call.stream);
     });
 }
 
@@ -1586,20 +1463,15 @@ int h2_permutation_sigma(uint64_t* out, const uint32_t* map_col, const uint32_t*
     if (n && (!out || !map_col || !map_row || !delta || !omega)) return bad("h2_permutation_sigma: null argument");
     return guarded([&] {
         if (n == 0) return (int)H2_OK;
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Prefault pf(out, n * sizeof(Fr));
-        Fr* d_out = (Fr*)ctx->buf_a.get(n * sizeof(Fr));
-        uint32_t* d_col = (uint32_t*)ctx->buf_b.get(2 * n * sizeof(uint32_t));
+        HostCall call;
+        HostResult res(out, n, {map_col, map_row});
+        Fr* d_out = (Fr*)call.ctx->buf_a.get(n * sizeof(Fr));
+        uint32_t* d_col = (uint32_t*)call.ctx->buf_b.get(2 * n * sizeof(uint32_t));
         uint32_t* d_row = d_col + n;
-        host_upload(d_col, map_col, n * sizeof(uint32_t), ctx->stream);
-        host_upload(d_row, map_row, n * sizeof(uint32_t), ctx->stream);
-        int rc = perm_sigma_launch(d_out, d_col, d_row, n, delta, omega, ctx->stream);
-        if (rc != H2_OK) return rc;
-        pf.join();
-        host_download(out, d_out, n * sizeof(Fr), ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        host_upload(d_col, map_col, n * sizeof(uint32_t), call.stream);
+        host_upload(d_row, map_row, n * sizeof(uint32_t), call.stream);
+        H2_TRY(perm_sigma_launch(d_out, d_col, d_row, n, delta, omega, call.stream));
+        return res.write(d_out, call.stream);
     });
 }
 
@@ -1614,44 +1486,23 @@ int h2_logup_multiplicity(const uint64_t* table, const uint64_t* const* inputs, 
     return guarded([&] {
         if (max_bits_out) *max_bits_out = 0;
         if (n == 0) return (int)H2_OK;
-        DeviceLease lease;
-        DeviceCtx* ctx = lease.ctx;
-        Prefault pf(m, n * sizeof(Fr));
-        const size_t bytes = n * sizeof(Fr), sbytes = logup_scratch_bytes(n);
-        std::vector<const Fr*> d_in(n_inputs);
-        size_t staged = 0;
-        const Fr* d_table = resident_operand(ctx, table, n);
-        for (size_t i = 0; i < n_inputs; i++) {
-            d_in[i] = resident_operand(ctx, inputs[i], n);
-            if (!d_in[i]) staged++;
-        }
-        Fr* up = (Fr*)ctx->buf_a.get((staged + (d_table ? 0 : 1)) * bytes + 256);
-        size_t at = 0;
-        if (!d_table) {
-            host_upload(up, table, bytes, ctx->stream);
-            d_table = up;
-            at = 1;
-        }
-        for (size_t i = 0; i < n_inputs; i++)
-            if (!d_in[i]) {
-                host_upload(up + at * n, inputs[i], bytes, ctx->stream);
-                d_in[i] = up + at * n;
-                at++;
-            }
-        Fr* d_m = (Fr*)ctx->buf_b.get(bytes);
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        std::vector<const uint64_t*> hosts(inputs, inputs + n_inputs);   // the inputs, then the table
+        hosts.push_back(table);
+        HostResult res(m, n, (const void* const*)hosts.data(), hosts.size());
+        const size_t sbytes = logup_scratch_bytes(n);
+        std::vector<const Fr*> d_in = call.in_packed(ctx->buf_a, hosts.data(), hosts.size(), n, 256);
+        Fr* d_m = (Fr*)ctx->buf_b.get(n * sizeof(Fr));
         void* d_scratch = ctx->buf_c.get(sbytes);
         uint32_t max_count = 0;
-        int rc = logup_multiplicity_launch(d_table, d_in.data(), n_inputs, usable_rows, n, d_m, d_scratch, sbytes, ctx->stream, &max_count);
-        if (rc != H2_OK) return rc;
+        H2_TRY(logup_multiplicity_launch(d_in[n_inputs], d_in.data(), n_inputs, usable_rows, n, d_m, d_scratch, sbytes, call.stream, &max_count));
         if (max_bits_out) {
             uint32_t bits = 0;
             while (bits < 32 && (max_count >> bits)) bits++;
             *max_bits_out = bits;
         }
-        pf.join();
-        host_download(m, d_m, bytes, ctx->stream);
-        H2_HIP(hipStreamSynchronize(ctx->stream));
-        return (int)H2_OK;
+        return res.write(d_m, call.stream);
     });
 }
 
@@ -1763,22 +1614,26 @@ int h2_evalh_stage_args(const h2_evalh_desc* desc, uint32_t stage, uint64_t* val
 uint64_t h2_evalh_generated_launches(void) { return evalh_generated_launches(); }
 
 // ------------------------------------------------------------------ evaluate_h
+// (the copy back is inside evalh_host / evalh_host_coeffs: the prefault of `values` starts once the descriptor is known to be
+// sound, runs under the wait for a slot, and is joined just before that call)
+static bool evalh_bad_sizes(const h2_evalh_desc* desc) { return desc->extended_k < desc->k || desc->extended_k > 28; }
+
 int h2_evaluate_h(const h2_evalh_desc* desc, uint64_t* values) {
     if (!desc || !values) return bad("h2_evaluate_h: null argument");
+    if (evalh_bad_sizes(desc)) return bad("h2_evaluate_h: bad k / extended_k");
     return guarded([&] {
-        Prefault pf(values, sizeof(Fr) << desc->extended_k);
-        pf.join();   // (before anything is copied back: the touch fallback must not race with the copy)
-        DeviceLease lease;
-        return evalh_host(lease.ctx, desc, values);
+        HostResult res(values, (size_t)1 << desc->extended_k);
+        HostCall call;
+        return evalh_host(call.ctx, desc, res.handed_over());
     });
 }
 
 int h2_evaluate_h_coeff(const h2_evalh_desc* desc, uint64_t* values) {
     if (!desc || !values) return bad("h2_evaluate_h_coeff: null argument");
+    if (evalh_bad_sizes(desc)) return bad("h2_evaluate_h_coeff: bad k / extended_k");
     return guarded([&] {
-        Prefault pf(values, desc->extended_k <= 28 ? sizeof(Fr) << desc->extended_k : 0);
-        pf.join();
-        return evalh_host_coeffs(desc, values);
+        HostResult res(values, (size_t)1 << desc->extended_k);
+        return evalh_host_coeffs(desc, res.handed_over());      // (leases its devices itself)
     });
 }
 
@@ -1795,36 +1650,32 @@ int h2_quotient_poly_coeff(const h2_evalh_desc* desc, const uint64_t* t_evaluati
                            const uint64_t extended_ifft_divisor[4], uint64_t* out, size_t out_len) {
     if (!desc || !t_evaluations || !t_len || !g_coset || !g_coset_inv || !extended_omega_inv || !extended_ifft_divisor || !out)
         return bad("h2_quotient_poly_coeff: null argument");
-    if (desc->extended_k < desc->k || desc->extended_k > 28) return bad("h2_quotient_poly_coeff: bad k / extended_k");
+    if (evalh_bad_sizes(desc)) return bad("h2_quotient_poly_coeff: bad k / extended_k");
     const size_t size = (size_t)1 << desc->extended_k;
     if (out_len > size) return bad("h2_quotient_poly_coeff: out_len exceeds the extended domain");
     if (size % t_len) return bad("h2_quotient_poly_coeff: t_len does not divide the extended domain");
     return guarded([&] {
-        Prefault pf(out, out_len * sizeof(Fr));
         const uint32_t ek = desc->extended_k;
-        EvalhFinish finish = [&](DeviceCtx* ctx, Fr* d_values, hipStream_t s) -> int {
-            Fr* d_t = (Fr*)ctx->buf_c.get(t_len * sizeof(Fr));
-            host_upload(d_t, t_evaluations, t_len * sizeof(Fr), s);
-            int rc = divide_by_vanishing_launch(d_values, size, d_t, t_len, s);
-            if (rc != H2_OK) return rc;
-            Fr* d_tmp = (Fr*)ctx->buf_b.get(size * sizeof(Fr));
-            rc = dev_extended_to_coeff_impl(ctx, d_values, d_tmp, ek, g_coset, g_coset_inv, extended_omega_inv, extended_ifft_divisor, s, true);
-            if (rc != H2_OK) return rc;
-            pf.join();
-            host_download(out, d_values, out_len * sizeof(Fr), s);
-            return (int)H2_OK;
-        };
         if (evalh_host_workers(desc) <= 1) {
+            // under the evaluation's own lease, on its stream
+            HostResult res(out, out_len);
+            EvalhFinish finish = [&](DeviceCtx* ctx, Fr* d_values, hipStream_t s) -> int {
+                Fr* d_t = (Fr*)ctx->buf_c.get(t_len * sizeof(Fr));
+                host_upload(d_t, t_evaluations, t_len * sizeof(Fr), s);
+                H2_TRY(divide_by_vanishing_launch(d_values, size, d_t, t_len, s));
+                Fr* d_tmp = (Fr*)ctx->buf_b.get(size * sizeof(Fr));
+                H2_TRY(dev_extended_to_coeff_impl(ctx, d_values, d_tmp, ek, g_coset, g_coset_inv, extended_omega_inv, extended_ifft_divisor, s, true));
+                return res.write(d_values, s);
+            };
             bool finished = false;
             int rc = evalh_host_coeffs(desc, nullptr, &finish, &finished);
             if (rc == H2_OK && !finished) return bad("h2_quotient_poly_coeff: the evaluation did not hand its values over");
             return rc;
         }
+        // (no result of this call's own here: h2_extended_to_coeff declares `out` as its result)
         std::vector<uint64_t> values(4 * size);
-        int rc = evalh_host_coeffs(desc, values.data());
-        if (rc != H2_OK) return rc;
-        rc = h2_divide_by_vanishing_poly(values.data(), size, t_evaluations, t_len);
-        if (rc != H2_OK) return rc;
+        H2_TRY(evalh_host_coeffs(desc, values.data()));
+        H2_TRY(h2_divide_by_vanishing_poly(values.data(), size, t_evaluations, t_len));
         return h2_extended_to_coeff(values.data(), out, out_len, ek, g_coset, g_coset_inv, extended_omega_inv, extended_ifft_divisor);
     });
 }

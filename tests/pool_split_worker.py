@@ -2,6 +2,7 @@
 entry points on ONE visible GPU -- pool entries wrap modulo the visible devices as `devices[gpu_idx % devices.len()]` does
 (arithmetic.rs:355), so four leases over two host-API slots of the one device run the real split."""
 import copy
+import ctypes
 import sys
 
 import numpy as np
@@ -37,11 +38,15 @@ assert L.h2_msm_multi(s.ctypes.data, p.ctypes.data, n, 254, out.ctypes.data) == 
 assert aff(out) == aff(oracle.best_multiexp(s, p))
 print("h2_msm_multi: 4 parts ok")
 
-# ---- h2_evaluate_h_coeff: the cosets of the extended domain dealt over the pool (evaluation.rs:1262-1275,1513-1520)
+# ---- h2_evaluate_h_coeff: the cosets of the extended domain dealt over the pool (evaluation.rs:1262-1275,1513-1520), and
+# h2_quotient_poly_coeff's branch for several devices behind it: the same cosets, then divide_by_vanishing_poly and
+# extended_to_coeff through a host vector.  The last case writes 3 * 2^16 coefficients (6 MiB): a result long enough for the
+# prefault of `out` to be live (4 MiB and more), which none of the shorter ones is.
+vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
 before = ev.generated_launches()
 for seed, j, k, kwargs in ((31, 3, 5, {}), (32, 5, 8, {}), (33, 9, 11, dict(n_calcs=60)), (34, 2, 6, {}), (36, 4, 14, dict(lookup_sets=(2,), n_shuffles=1)),
-                           (37, 17, 9, {})):
-    d, _ = oracle.domain(j, k)
+                           (37, 17, 9, {}), (38, 4, 16, {})):
+    d, t = oracle.domain(j, k)
     ek = d.extended_k
     kw = random_case(seed, k, ek, oracle, **({"n_calcs": 40} | kwargs))
     kw["zeta"], kw["extended_omega"] = d.fr("g_coset"), d.fr("extended_omega")
@@ -59,5 +64,14 @@ for seed, j, k, kwargs in ((31, 3, 5, {}), (32, 5, 8, {}), (33, 9, 11, dict(n_ca
     got = ev.evaluate_h_coeff(ev.Builder().build(**coeff))
     assert np.array_equal(got, want), ("h2_evaluate_h_coeff", seed, 1 << (ek - k))
     print("h2_evaluate_h_coeff: k=%d, %d cosets over the pool ok" % (k, 1 << (ek - k)))
+    divided = want.copy()
+    oracle.lib.oracle_divide_by_vanishing_poly(divided.ctypes.data, len(divided), t.ctypes.data, len(t), 8)
+    want_coeff = oracle.extended_to_coeff(divided, d, threads=8)
+    b = ev.Builder().build(**coeff)
+    out = np.empty((len(want_coeff), 4), dtype=np.uint64)
+    scal = [d.fr(name) for name in ("g_coset", "g_coset_inv", "extended_omega_inv", "extended_ifft_divisor")]
+    assert L.h2_quotient_poly_coeff(ctypes.byref(b.desc), vp(t), len(t), *[vp(v) for v in scal], vp(out), len(out)) == 0, L.h2_last_error()
+    assert np.array_equal(out, want_coeff), ("h2_quotient_poly_coeff", seed, 1 << (ek - k))
+    print("h2_quotient_poly_coeff: k=%d, %d result elements ok" % (k, len(out)))
 assert ev.generated_launches() > before
 print("POOL-SPLIT-OK")

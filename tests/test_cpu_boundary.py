@@ -66,6 +66,33 @@ def test_argument_validation_without_gpu():
         h2.arithmetic.best_fft(np.zeros((5, 4), np.uint64), np.zeros(4, np.uint64), 3)
 
 
+def test_evaluate_h_validates_the_descriptor_before_it_touches_memory():
+    """h2_evaluate_h / h2_evaluate_h_coeff with extended_k = 29 > 28 and with extended_k = 3 < k = 4 over a 4 KiB `values`:
+    H2_ERR_INVALID and a message, with or without a GPU -- the sizes are checked before a slot is leased or a page of `values`
+    touched (2^29 elements would be 16 GiB past the buffer).  In a child process: a library that touched them would take the
+    process down, and that is to show as this assertion failing."""
+    code = (
+        "import ctypes, sys; sys.path.insert(0, %r)\n"
+        "import numpy as np\n"
+        "import halo2_gpu_specific_amd as h2\n"
+        "from halo2_gpu_specific_amd import evaluation\n"
+        "L = h2.lib()\n"
+        "values = np.zeros(4096 // 8, dtype=np.uint64)\n"
+        "for name in ('h2_evaluate_h', 'h2_evaluate_h_coeff'):\n"
+        "    for k, ek in ((4, 29), (4, 3)):\n"
+        "        desc = evaluation.EvalHDesc()\n"
+        "        desc.k, desc.extended_k = k, ek\n"
+        "        rc = getattr(L, name)(ctypes.byref(desc), values.ctypes.data)\n"
+        "        print('CALL', name, ek, rc, bool(L.h2_last_error()), flush=True)\n"
+        "print('DONE')\n"
+    ) % ROOT
+    res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0 and "DONE" in res.stdout, res.stdout[-2000:] + res.stderr[-2000:]
+    for name in ("h2_evaluate_h", "h2_evaluate_h_coeff"):
+        for ek in (29, 3):
+            assert "CALL %s %d 1 True" % (name, ek) in res.stdout, res.stdout
+
+
 def test_missing_extension_fails_loudly(tmp_path):
     code = (
         "import sys; sys.path.insert(0, %r)\n"

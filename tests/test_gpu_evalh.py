@@ -126,11 +126,12 @@ def test_without_hiprtc_the_interpreter_kernels_run(tmp_path):
 
 @pytest.mark.parametrize("seed,j,k,kwargs", [(31, 3, 5, {}), (32, 5, 8, {}), (33, 9, 11, dict(n_calcs=60)), (34, 2, 6, {}),
                                              (35, 5, 7, dict(with_perm=False, lookup_sets=(), n_shuffles=0, n_calcs=5)),
-                                             (36, 4, 14, dict(lookup_sets=(2,), n_shuffles=1))])
+                                             (36, 4, 14, dict(lookup_sets=(2,), n_shuffles=1)), (38, 4, 16, {})])
 def test_evaluate_h_from_coefficient_forms(oracle, seed, j, k, kwargs):
     """h2_evaluate_h_coeff -- coefficient forms in, the numerator on the extended domain out, computed coset by coset
     (the cuda evaluate_h's shape, plonk/evaluation.rs:1229-1241) -- against the oracle's evaluate_h on the oracle's own
-    extended cosets (coeff_to_extended, poly/domain.rs:270-287): 2, 4, 4, 1 (extended_k = k), 4 and 4 cosets"""
+    extended cosets (coeff_to_extended, poly/domain.rs:270-287): 2, 4, 4, 1 (extended_k = k), 4, 4 and 4 cosets; the last
+    case's quotient is 3 * 2^16 coefficients (6 MiB), long enough for h2_quotient_poly_coeff's prefault of `out` to be live"""
     import copy
 
     d, _ = oracle.domain(j, k)
