@@ -499,6 +499,272 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
     }
 }
 
+// ---------------------------------------------------------------- the common pass, tile ends fused
+// The fixed geometry of k_ntt_pass<true, true, 8, ...> (8 bits, 4 columns, 256 lanes, four elements per lane, lazy domain,
+// nothing skipped; one tile per workgroup, blockIdx.y the vector) with the two ends of a tile taken out of LDS.
+// The four rows a lane loads are the inputs of ONE unit of the first stage pair, and the four rows a unit of the last stage
+// pair produces are the four a lane stores.  So the first pair runs on the loaded registers (after pre3, the coset pre-scale
+// and the inter-pass twiddle, as before) and writes its outputs to LDS, and the last pair's outputs go through the
+// post-processing to memory from registers: two LDS round trips and two of five barriers per tile less, the same operations
+// on the same operands.  Lane -> element maps (unit b of the first pair holds LDS rows 4b .. 4b + 3 = the rows
+// rho = bitrev6(b) + 64 q of the tile, x_j with bitrev2(j) = q):
+//   passes before the last: lane t takes unit b = t >> 2 of column t & 3 and loads rows bitrev6(b) + 64 q (a row is one
+//     128-byte segment whichever lane loads it; the unit's LDS writes are those of the unfused round: 2-way conflicts);
+//   last pass: a wave takes one column and lane l the rows l + 64 q of it (2 KiB contiguous per load, tw_direct in the same
+//     order), i.e. unit bitrev6(l): its LDS writes are 256 B apart (8-way conflicts per lane group, as the bit-reversed
+//     writes of the unfused load phase were).
+// The first pair needs ONE butterfly twiddle (index 1 of stage 1, entry 64 of the table) before the tile's first barrier, i.e.
+// before the LDS copy of the table is ordered against its readers: every lane reads that one from the table in memory.
+template <bool CW, bool DP>
+__global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
+    static_assert(!DP || CW, "pairs in tw_direct only next to pairs in tw_bfly");
+    constexpr uint32_t B = 8, R = 1u << B, log_c = 2, C = 1u << log_c;
+    auto tmul = [](const Fr& x, const Fr& w) -> Fr { return fp_mul_wide(x, w); };
+    uint4* t_lo = h2_smem;                  // the planes of k_ntt_pass, at the same offsets
+    uint4* t_hi = t_lo + (R << log_c);
+    uint4* w_lo = t_hi + (R << log_c);
+    uint4* w_hi = w_lo + (R >> 1) + (CW ? 0 : 1);
+    uint4* q_lo = w_hi + (R >> 1);
+    uint4* q_hi = q_lo + (R >> 1);
+    struct Tw {
+        Fr w, q;
+    };
+    auto tw_get = [&](uint32_t i) __attribute__((always_inline)) -> Tw {
+        Tw t;
+        t.w = lds_get(w_lo, w_hi, i);
+        if constexpr (CW) t.q = lds_get(q_lo, q_hi, i);
+        return t;
+    };
+    auto bmul = [](const Fr& x, const Tw& t) __attribute__((always_inline)) -> Fr {
+        if constexpr (CW) return fp_mul_const(x, t.w, t.q);
+        else return fp_mul_wide(x, t.w);
+    };
+    // stages s and s + 1 on the rows p, p + h, p + 2h, p + 3h (h = 2^s) of one column, in registers, twiddle index r = p mod h:
+    // the arithmetic of k_ntt_pass's round4, operation for operation; x0 .. x3 come back in row order
+    auto unit4 = [&](Fr& x0, Fr& x1, Fr& x2, Fr& x3, const uint32_t s, const uint32_t r, const bool unit, const Tw* w3 = nullptr) __attribute__((always_inline)) {
+        const uint32_t h = 1u << s;
+        x0 = fp_lazy_red2p(x0);
+        x2 = fp_lazy_red2p(x2);
+        if (!unit) {
+            const Tw wa = tw_get(r << (B - 1 - s));
+            x1 = bmul(x1, wa);
+            x3 = bmul(x3, wa);
+        } else {
+            x1 = fp_lazy_red2p(x1);
+            x3 = fp_lazy_red2p(x3);
+        }
+        const Fr y0 = fp_lazy_add_red(x0, x1), y1 = fp_lazy_sub_red(x0, x1);
+        Fr y2 = fp_lazy_add(x2, x3), y3 = fp_lazy_sub(x2, x3);
+        y2 = unit ? fp_lazy_red2p(y2) : bmul(y2, tw_get(r << (B - 2 - s)));
+        y3 = bmul(y3, w3 ? *w3 : tw_get((r + h) << (B - 2 - s)));   // (w3: that twiddle, already in registers)
+        x0 = fp_lazy_add(y0, y2);
+        x1 = fp_lazy_add(y1, y3);
+        x2 = fp_lazy_sub(y0, y2);
+        x3 = fp_lazy_sub(y1, y3);
+    };
+    // the unit of lane `tid` in the round of stages s, s + 1: first LDS index, twiddle index (k_ntt_pass's round4)
+    auto unit_of = [](const uint32_t tid, const uint32_t s, uint32_t& i0, uint32_t& r, bool& unit) __attribute__((always_inline)) {
+        const uint32_t h = 1u << s, log_per = (B - 2 + log_c) - s;
+        const bool by_r = s != 0 && log_per >= 6;
+        uint32_t c, p;
+        if (by_r) {
+            r = tid >> log_per;
+            const uint32_t j = tid & ((1u << log_per) - 1);
+            c = j & (C - 1);
+            p = ((j >> log_c) << (s + 2)) | r;
+        } else {
+            c = tid & (C - 1);
+            const uint32_t b = tid >> log_c;
+            r = b & (h - 1);
+            p = ((b >> s) << (s + 2)) | r;
+        }
+        i0 = (p << log_c) + c;
+        unit = s == 0 || (by_r && r == 0);
+    };
+    const uint32_t tid = threadIdx.x;
+    auto round4 = [&](const uint32_t s) __attribute__((always_inline)) {
+        uint32_t i0, r;
+        bool unit;
+        unit_of(tid, s, i0, r, unit);
+        const uint32_t step = (1u << s) << log_c;
+        Fr x0 = lds_get(t_lo, t_hi, i0), x1 = lds_get(t_lo, t_hi, i0 + step);
+        Fr x2 = lds_get(t_lo, t_hi, i0 + 2 * step), x3 = lds_get(t_lo, t_hi, i0 + 3 * step);
+        unit4(x0, x1, x2, x3, s, r, unit);
+        lds_put(t_lo, t_hi, i0, x0);
+        lds_put(t_lo, t_hi, i0 + 2 * step, x2);
+        lds_put(t_lo, t_hi, i0 + step, x1);
+        lds_put(t_lo, t_hi, i0 + 3 * step, x3);
+        __syncthreads();
+    };
+    const bool is_last = DP ? false : a.is_last != 0;   // (pairs in tw_direct: never the last pass)
+    const uint32_t n_mask = (a.log_n >= 32) ? 0xffffffffu : ((1u << a.log_n) - 1);
+
+    if (tid < (R >> 1)) {
+        if constexpr (CW) {
+            lds_put(w_lo, w_hi, tid, fp_load(a.tw_bfly + 2 * tid));
+            lds_put(q_lo, q_hi, tid, fp_load(a.tw_bfly + 2 * tid + 1));
+        } else {
+            lds_put(w_lo, w_hi, tid, fp_load(a.tw_bfly + tid));
+        }
+    }
+
+    // stage 1's twiddle of index 1 for the first stage pair, straight from the table (wave-uniform address)
+    Tw tw64;
+    if constexpr (CW) {
+        tw64.w = fp_load(a.tw_bfly + 2 * (R >> 2));
+        tw64.q = fp_load(a.tw_bfly + 2 * (R >> 2) + 1);
+    } else {
+        tw64.w = fp_load(a.tw_bfly + (R >> 2));
+    }
+
+    constexpr uint32_t NE = 4;
+    {
+        const uint32_t tile_id = blockIdx.x;
+        const Fr* const in_p = a.batch ? a.in_b[blockIdx.y] : a.in;   // (wave-uniform: scalar loads from the kernel arguments)
+        Fr* const out_p = a.batch ? a.out_b[blockIdx.y] : a.out;
+        uint32_t base = 0, K_uniform = 0;
+        if (!is_last) {
+            const uint32_t chunks_per_hi = (1u << a.s_log) >> log_c;
+            const uint32_t hi = tile_id / chunks_per_hi, lo0 = (tile_id % chunks_per_hi) << log_c;
+            base = (hi << (B + a.s_log)) + lo0;
+            K_uniform = hi_to_K(hi, a);
+        }
+
+        // ---- load (+ zero pad, coset pre-scale, inter-pass twiddle): k_ntt_pass's, with the lane -> element map above
+        {
+            uint32_t rho[NE], col[NE], idx[NE], Kk[NE];
+            Fr x[NE];
+#pragma unroll
+            for (uint32_t q = 0; q < NE; q++) {
+                if (!is_last) {
+                    col[q] = tid & (C - 1);
+                    rho[q] = bitrev(tid >> log_c, B - 2) + (q << (B - 2));
+                    idx[q] = base + (rho[q] << a.s_log) + col[q];
+                    Kk[q] = K_uniform;
+                } else {
+                    rho[q] = (tid & 63) + (q << (B - 2));
+                    col[q] = tid >> 6;
+                    Kk[q] = (tile_id << log_c) + col[q];
+                    idx[q] = (K_to_hi(Kk[q], a) << B) + rho[q];
+                }
+            }
+#pragma unroll
+            for (uint32_t q = 0; q < NE; q++) {
+                x[q] = fp_zero<FrParams>();
+                if (idx[q] < a.in_len) x[q] = fp_load(in_p + idx[q]);
+            }
+            if (a.has_pre3) {
+#pragma unroll
+                for (uint32_t q = 0; q < NE; q++) {
+                    const uint32_t m = idx[q] % 3;
+                    Fr w;
+#pragma unroll
+                    for (int l = 0; l < 8; l++) w.l[l] = m == 1 ? a.pre3[1].l[l] : a.pre3[2].l[l];
+                    if (m != 0) x[q] = tmul(x[q], w);
+                }
+            }
+            const bool pre_scale = a.scale_mode == 1u && a.nprev == 0;
+            if (a.nprev != 0 || pre_scale) {
+                if (a.tw_direct != nullptr && !pre_scale) {
+#pragma unroll
+                    for (uint32_t q0 = 0; q0 < NE; q0 += 2) {
+                        if constexpr (DP) {
+#pragma unroll
+                            for (uint32_t q = q0; q < q0 + 2; q++) {
+                                const size_t at = a.direct_kmajor ? ((Kk[q] << B) | rho[q]) : ((rho[q] << a.t_log) | Kk[q]);
+                                const Fr w = fp_load(a.tw_direct + 2 * at), wq = fp_load(a.tw_direct + 2 * at + 1);
+                                x[q] = fp_mul_const(x[q], w, wq);
+                            }
+                        } else {
+                            Fr w[2];
+#pragma unroll
+                            for (uint32_t q = 0; q < 2; q++)
+                                w[q] = fp_load(a.tw_direct + (a.direct_kmajor ? ((Kk[q0 + q] << B) | rho[q0 + q]) : ((rho[q0 + q] << a.t_log) | Kk[q0 + q])));
+#pragma unroll
+                            for (uint32_t q = 0; q < 2; q++) x[q0 + q] = tmul(x[q0 + q], w[q]);
+                        }
+                    }
+                } else if (a.log_n <= LO_BITS && !pre_scale) {
+#pragma unroll
+                    for (uint32_t q = 0; q < NE; q++) {
+                        const uint32_t ex = (uint32_t)(((uint64_t)rho[q] * Kk[q]) << a.s_log) & n_mask;
+                        x[q] = tmul(x[q], fp_load(a.tw_lo + ex));
+                    }
+                } else {
+                    const Fr* const two_lo = pre_scale ? a.sc_lo : a.tw_lo;
+                    const Fr* const two_hi = pre_scale ? a.sc_hi : a.tw_hi;
+#pragma unroll
+                    for (uint32_t q0 = 0; q0 < NE; q0 += 2) {
+                        Fr wl[2], wh[2];
+#pragma unroll
+                        for (uint32_t q = 0; q < 2; q++) {
+                            const uint32_t ex = pre_scale ? (idx[q0 + q] & n_mask)
+                                                          : ((uint32_t)(((uint64_t)rho[q0 + q] * Kk[q0 + q]) << a.s_log) & n_mask);
+                            wl[q] = fp_load(two_lo + (ex & ((1u << LO_BITS) - 1)));
+                            wh[q] = fp_load(two_hi + (ex >> LO_BITS));
+                        }
+#pragma unroll
+                        for (uint32_t q = 0; q < 2; q++) x[q0 + q] = tmul(x[q0 + q], fp_mul(wl[q], wh[q]));
+                    }
+                }
+            }
+            // x[q] is row 4b + bitrev2(q) of unit b: stages 0 and 1 (every twiddle of stage 0 and index 0 of stage 1 is 1)
+            const uint32_t b = is_last ? bitrev(tid & 63, B - 2) : (tid >> log_c);
+            const uint32_t i0 = (b << (2 + log_c)) + (is_last ? (tid >> 6) : (tid & (C - 1)));
+            unit4(x[0], x[2], x[1], x[3], 0, 0, true, &tw64);
+            lds_put(t_lo, t_hi, i0, x[0]);
+            lds_put(t_lo, t_hi, i0 + 2 * C, x[1]);
+            lds_put(t_lo, t_hi, i0 + C, x[2]);
+            lds_put(t_lo, t_hi, i0 + 3 * C, x[3]);
+        }
+        __syncthreads();
+        round4(2);
+        round4(4);
+
+        // ---- last stage pair and store (+ post-scale on the final pass): lane t holds rows (t >> 2) + 64 q of column t & 3
+        Fr y[NE];
+        {
+            uint32_t i0, r;
+            bool unit;
+            unit_of(tid, 6, i0, r, unit);
+#pragma unroll
+            for (uint32_t q = 0; q < NE; q++) y[q] = lds_get(t_lo, t_hi, i0 + q * (R << log_c) / NE);
+            unit4(y[0], y[1], y[2], y[3], 6, r, unit);
+        }
+        uint32_t idx[NE];
+#pragma unroll
+        for (uint32_t q = 0; q < NE; q++) {
+            const uint32_t c = tid & (C - 1), k = (tid >> log_c) + q * (R / NE);
+            if (!is_last)
+                idx[q] = base + (k << a.s_log) + c;
+            else
+                idx[q] = ((tile_id << log_c) + c) + (k << a.t_log);
+        }
+        if (is_last && a.scale_mode == 2u) {
+#pragma unroll
+            for (uint32_t q = 0; q < NE; q++) {
+                const uint32_t i = idx[q] & n_mask;
+                const Fr w = fp_mul(fp_load(a.sc_lo + (i & ((1u << LO_BITS) - 1))), fp_load(a.sc_hi + (i >> LO_BITS)));
+                y[q] = fp_reduce_once(fp_mul_wide(y[q], w));
+            }
+        } else if (is_last && a.has_post3 && !a.hi_scaled) {
+#pragma unroll
+            for (uint32_t q = 0; q < NE; q++) {
+                const uint32_t m = idx[q] % 3;
+                Fr w;
+#pragma unroll
+                for (int l = 0; l < 8; l++) w.l[l] = m == 0 ? a.post3[0].l[l] : (m == 1 ? a.post3[1].l[l] : a.post3[2].l[l]);
+                y[q] = fp_reduce_once(fp_mul_wide(y[q], w));
+            }
+        } else if (is_last) {
+#pragma unroll
+            for (uint32_t q = 0; q < NE; q++) y[q] = fp_lazy_canon(y[q]);
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < NE; q++) fp_store(out_p + idx[q], y[q]);
+    }
+}
+
 
 // ---------------------------------------------------------------- pass geometry (shared by the plan builder and the launcher)
 struct PassShape {
@@ -901,6 +1167,13 @@ void ntt_run_many(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr* const*
     }
 }
 
+// the common pass through k_ntt_pass8 (H2_NTT_FUSE=0: k_ntt_pass<true, true, 8, ...>, the ends of a tile through LDS).
+// Read once, like H2_NTT_FIXED.
+static bool pass8_fuse() {
+    static const bool v = !(getenv("H2_NTT_FUSE") && atoi(getenv("H2_NTT_FUSE")) == 0);
+    return v;
+}
+
 static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr* const* dsts, Fr* const* tmps, uint32_t cnt,
                           uint32_t in_len, const Fr* pre3, const Fr* post3, hipStream_t stream, const Fr* scale_tab,
                           uint32_t scale_mode) {
@@ -1092,7 +1365,13 @@ static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr
                 }
             }
             const bool dp = cw && !last;      // pairs in tw_direct: the middle passes' tables (a first pass has none)
-            if (cw && sh.fixed && a.zskip == 0 && dp)
+            if (sh.fixed && a.zskip == 0 && pass8_fuse() && cw && dp)
+                hipLaunchKernelGGL((k_ntt_pass8<true, true>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
+            else if (sh.fixed && a.zskip == 0 && pass8_fuse() && cw)
+                hipLaunchKernelGGL((k_ntt_pass8<true, false>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
+            else if (sh.fixed && a.zskip == 0 && pass8_fuse())
+                hipLaunchKernelGGL((k_ntt_pass8<false, false>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
+            else if (cw && sh.fixed && a.zskip == 0 && dp)
                 hipLaunchKernelGGL((k_ntt_pass<true, true, 8, true, true>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
             else if (cw && sh.fixed && a.zskip == 0)
                 hipLaunchKernelGGL((k_ntt_pass<true, true, 8, true, false>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
