@@ -14,6 +14,7 @@
 #include "ntt.hpp"
 #include "poly.hpp"
 #include "logup.hpp"
+#include "rangecheck.hpp"
 #include "scan.hpp"
 
 using namespace h2;
@@ -1548,6 +1549,26 @@ int h2_dev_logup_multiplicity_bits(const void* d_table, const void* const* d_inp
         while (bits < 32 && (max_count >> bits)) bits++;
         *max_bits_out = bits;
         return rc;
+    });
+}
+
+// ------------------------------------------------------------------ range-check witness completion
+size_t h2_range_check_scratch_bytes(const uint64_t* vmin, const uint64_t* vmax, size_t pairs) {
+    return range_check_scratch_bytes(vmin, vmax, pairs);
+}
+
+int h2_dev_range_check_complete(void* const* d_origins, void* const* d_companions, const uint32_t* origin_forms,
+                                const uint32_t* companion_forms, const uint64_t* vmin, const uint64_t* vmax, const uint64_t* step,
+                                const uint64_t* first_unassigned, size_t pairs, size_t usable_rows, size_t n, void* d_status,
+                                void* d_scratch, size_t scratch_bytes, void* stream) {
+    if (const char* what = range_check_validate(d_origins, d_companions, origin_forms, companion_forms, vmin, vmax, step, pairs,
+                                                usable_rows, n, d_status, d_scratch, scratch_bytes))
+        return bad((std::string("h2_dev_range_check_complete: ") + what).c_str());
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return range_check_complete_launch(d_origins, d_companions, origin_forms, companion_forms, vmin, vmax, step,
+                                           first_unassigned, pairs, usable_rows, n, (uint32_t*)d_status, d_scratch,
+                                           pick_stream(ctx, stream));
     });
 }
 

@@ -254,7 +254,7 @@ class Device:
         with self.torch.cuda.stream(self.tstream):
             return self.torch.zeros((n, 4), dtype=self.torch.int64, device=self.dev)
 
-    def upload(self, a):
+    def upload(self, a, widen=True):
         a = np.ascontiguousarray(a)
         with self.torch.cuda.stream(self.tstream):
             src = self._pinned.get(a.ctypes.data)
@@ -266,7 +266,7 @@ class Device:
                 with warnings.catch_warnings():      # read-only sources (a memory-mapped witness file) are only read
                     warnings.simplefilter("ignore", UserWarning)
                     t = self.torch.from_numpy(a.view(np.int64)).to(self.dev)
-        return self.widen(t) if a.ndim == 1 else t
+        return self.widen(t) if a.ndim == 1 and widen else t
 
     def widen(self, small, stream=None):
         """a compact column (n u64 values on the device, 8 B per cell over PCIe) -> canonical (n, 4) scalars"""
@@ -1456,10 +1456,90 @@ def complete_range_check_witness(cs, n, advice, first_unassigned=None):
     return advice
 
 
-def _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, copy_range_columns=False):
+RC_FORM_CANONICAL, RC_FORM_MONTGOMERY, RC_FORM_COMPACT = 0, 1, 2                      # H2_RANGE_CHECK_FORM_*
+RC_OK, RC_NO_FIT, RC_IN_USE, RC_OUT_OF_RANGE, RC_UNSUPPORTED = 0, 1, 2, 3, 4           # H2_RANGE_CHECK_*
+RC_STATUS_WORDS = 8
+_RC_ERRORS = {
+    RC_NO_FIT: "range check: the range does not fit the unused cells of its column",
+    RC_IN_USE: "range check: the witness already uses the cells the range is planted in",
+    RC_OUT_OF_RANGE: "range check: a value of the column lies outside its range",
+    RC_UNSUPPORTED: "range check: a range of 2^24 values or more cannot be completed on the device",
+}
+
+
+def range_check_complete_device(device, pairs, usable, n):
+    """h2_dev_range_check_complete for the column pairs of one circuit instance, in one call and one download:
+    pairs = [(origin, companion, origin form, companion form, vmin, vmax, step, first_unassigned or None)], the columns
+    device tensors in the form named (RC_FORM_*: (n, 4) canonical, (n, 4) Montgomery, 1-D compact), completed in place.
+    Returns the status records, a (len(pairs), RC_STATUS_WORDS) u32 array: [code (RC_*), first offending row, pair, ...];
+    a pair whose code is not RC_OK was left untouched."""
+    D, L = device, device.L
+    count = len(pairs)
+    if not count:
+        return np.zeros((0, RC_STATUS_WORDS), dtype=np.uint32)
+    u64s = lambda vals: (ctypes.c_uint64 * count)(*vals)                # noqa: E731
+    origins = (_vp * count)(*[p[0].data_ptr() for p in pairs])
+    companions = (_vp * count)(*[p[1].data_ptr() for p in pairs])
+    oforms = (ctypes.c_uint32 * count)(*[p[2] for p in pairs])
+    cforms = (ctypes.c_uint32 * count)(*[p[3] for p in pairs])
+    vmin, vmax, step = u64s([p[4] for p in pairs]), u64s([p[5] for p in pairs]), u64s([p[6] for p in pairs])
+    unknown = (1 << 64) - 1
+    first = u64s([unknown if p[7] is None else min(int(p[7]), unknown - 1) for p in pairs])
+    nbytes = L.h2_range_check_scratch_bytes(vmin, vmax, count)
+    with D.torch.cuda.stream(D.tstream):
+        status = D.torch.empty(count * RC_STATUS_WORDS, dtype=D.torch.int32, device=D.dev)
+    check(L.h2_dev_range_check_complete(origins, companions, oforms, cforms, vmin, vmax, step, first, count, usable, n,
+                                        status.data_ptr(), D.scratch(nbytes).data_ptr(), nbytes, D.stream),
+          "h2_dev_range_check_complete")
+    with D.torch.cuda.stream(D.tstream):
+        return status.cpu().numpy().view(np.uint32).reshape(count, RC_STATUS_WORDS)
+
+
+def complete_range_check_witness_device(device, cs, n, advice, first_unassigned=None, montgomery=False):
+    """complete_range_check_witness on the device (csrc/rangecheck.hip): the same planting, the same counting sort and the
+    same ValueErrors, for range-checked columns and companions in any form the prover takes -- canonical (n, 4) u64,
+    Montgomery residues (`montgomery`), compact 1-D u64 -- and wherever they live.
+
+    A column that is a device tensor is completed in place.  A host column is uploaded, and the completed device tensor
+    takes its place in the list `advice`: the caller's host array is NOT written (unlike complete_range_check_witness).  A
+    compact column is completed as such and then widened: its entry of `advice` becomes a canonical (n, 4) tensor.
+    Nothing of a pair is written unless all its checks pass; after a ValueError the columns of the failing pair are as
+    they were and the library stays usable.  A range of 2^24 values or more is a ValueError here (the host path sorts it)."""
+    D, torch = device, device.torch
+    usable = n - (cs.blinding_factors() + 1)
+    pairs = []
+    for origin, sort, vmin, vmax, step in cs.range_checks:
+        forms = []
+        for c in (origin, sort):
+            col = advice[c]
+            if not torch.is_tensor(col):
+                col = advice[c] = D.upload(col, widen=False)
+            if col.dim() == 1 and montgomery:
+                raise ValueError("range check: a compact column cannot hold Montgomery residues")
+            if col.shape[0] != n or not col.is_contiguous():
+                raise ValueError("range check: a column of %d contiguous rows is needed" % n)
+            forms.append(RC_FORM_COMPACT if col.dim() == 1 else RC_FORM_MONTGOMERY if montgomery else RC_FORM_CANONICAL)
+        pairs.append((advice[origin], advice[sort], forms[0], forms[1], vmin, vmax, step,
+                      None if first_unassigned is None else first_unassigned.get(origin, 0)))
+    status = range_check_complete_device(D, pairs, usable, n)
+    for rec in status:
+        if rec[0] != RC_OK:
+            raise ValueError(_RC_ERRORS[int(rec[0])])
+    for origin, sort, _, _, _ in cs.range_checks:
+        for c in (origin, sort):
+            if advice[c].dim() == 1:
+                advice[c] = D.widen(advice[c])
+    return advice
+
+
+def _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, copy_range_columns=False, device=None,
+                  range_checks_on_device=False):
     """The witness intake of create_proof_ext: (advice_sets, instance_sets), one list per circuit instance, with the
     range-checked columns completed (complete_range_check_witness, in place on the caller's columns unless
-    `copy_range_columns`, which completes copies of them instead)."""
+    `copy_range_columns`, which completes copies of them instead).  An instance whose range-checked columns or companions
+    are device tensors, or Montgomery residues, or every instance with `range_checks_on_device`, is completed on the device
+    (complete_range_check_witness_device: host columns are uploaded, not written).  An instance of host columns with a range
+    of 2^24 values or more stays on the host under `range_checks_on_device` too, completed on copies."""
     multi = len(advice) > 0 and isinstance(advice[0], (list, tuple))
     advice_sets = [list(a) for a in advice] if multi else [list(advice)]
     instance_sets = [list(i) for i in instances] if multi else [list(instances)]
@@ -1469,16 +1549,29 @@ def _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, copy_r
     if any(len(a) != nadv for a in advice_sets):
         raise ValueError("every circuit instance needs the same advice columns")
     if cs.range_checks:
-        if montgomery:
-            raise ValueError("range-check witness completion needs canonical advice columns")
         fu = first_unassigned if isinstance(first_unassigned, (list, tuple)) else [first_unassigned] * len(advice_sets)
         for a, f in zip(advice_sets, fu):                     # prover.rs:1699-1783: plant the range, sort the companion
-            if copy_range_columns:
+            resident = any(not isinstance(a[c], np.ndarray) for origin, sort, _, _, _ in cs.range_checks for c in (origin, sort))
+            on_device = device is not None and (montgomery or resident or range_checks_on_device)
+            copies = copy_range_columns
+            if on_device and not (montgomery or resident) and any(vmax - vmin >= 1 << 24 for _, _, vmin, vmax, _ in cs.range_checks):
+                # opted in, but a range is past the device's counting-sort cap: host columns keep the host path, which sorts
+                # it -- on copies, since the opt-in promises not to write the caller's arrays
+                on_device, copies = False, True
+            if montgomery and not on_device:
+                raise ValueError("range-check witness completion needs canonical advice columns")
+            if copies:
                 for origin, sort, _, _, _ in cs.range_checks:
                     for c in (origin, sort):
                         if isinstance(a[c], np.ndarray):
-                            a[c] = a[c].copy()
-            complete_range_check_witness(cs, n, a, f)
+                            if not on_device:                 # (the device path uploads host columns: a copy already)
+                                a[c] = a[c].copy()
+                        elif on_device:
+                            a[c] = device.clone(a[c])
+            if on_device:
+                complete_range_check_witness_device(device, cs, n, a, f, montgomery)
+            else:
+                complete_range_check_witness(cs, n, a, f)
     return advice_sets, instance_sets
 
 
@@ -1489,7 +1582,7 @@ def create_proof_from_witness(device, params, pk, witness, rng, use_gwc=True, ti
 
 
 def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, instances=(), montgomery=False,
-                     first_unassigned=None):
+                     first_unassigned=None, range_checks_on_device=False):
     """plonk/prover.rs:206-850.  advice: list of (n, 4) u64 columns, canonical integers (or Montgomery residues with
     montgomery=True); rows past the usable range are overwritten with blinding values; instances: one list of
     canonical integers per instance column; rng: a rng.ProverRng.  Returns the proof bytes.
@@ -1503,7 +1596,15 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
 
     `first_unassigned`: {advice column index: first row synthesis left unassigned} (one dict, or one per circuit instance) for
     the range-checked columns -- what the reference's assignment tracking records (prover.rs:1706-1731); without it the
-    cells the range is planted in must be zero."""
+    cells the range is planted in must be zero.
+
+    Range-checked columns are completed where they live: host columns of canonical integers on the host, in place
+    (complete_range_check_witness); a pair with a device tensor in it, or Montgomery residues, on the device
+    (complete_range_check_witness_device: tensors in place, host columns of the pair uploaded and left unwritten).
+    `range_checks_on_device`: host columns too go up first and are completed there by one call per circuit instance, followed
+    by one download of its status -- the caller's arrays are not written and the host does no per-row work (DESIGN.md,
+    "Completing range-check witnesses", has the measured proof times).  A circuit instance with a range of 2^24 values or
+    more, which the device refuses, is completed on the host instead, on copies of its columns."""
     import time
 
     D, L = device, device.L
@@ -1564,7 +1665,8 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
                 points_[i] = g1_add_affine(a_, b_)
         return points_
 
-    advice_sets, instance_sets = _witness_sets(cs, n, advice, instances, montgomery, first_unassigned)
+    advice_sets, instance_sets = _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, device=D,
+                                               range_checks_on_device=range_checks_on_device)
     ncirc, nadv = len(advice_sets), len(advice_sets[0])
     advice = [col for a in advice_sets for col in a]          # circuit-major: the order every phase walks them in
     # The residency of the key was decided at keygen for ONE circuit instance; advice, product and lookup polynomials scale
@@ -2378,15 +2480,16 @@ def _check_scalar(seed, what):
 
 
 def check_witness(device, pk, advice, instances=(), seed=0, max_failures=1024, montgomery=False, first_unassigned=None,
-                  timings=None):
+                  timings=None, range_checks_on_device=False):
     """Checks a witness against the circuit of `pk` on the device, as MockProver::run(..).verify() does (dev.rs:932-1340), and
     returns (failures, total): `failures` the first max_failures of them (check_failures: named tuples with MockProver's field
     names, sorted as MockProver chains its errors), `total` the exact number of failures.
 
     The witness is taken as create_proof_ext takes it -- canonical (n, 4) columns, Montgomery ones with montgomery=True,
     compact 1-D columns, device tensors, several circuit instances as a list of column lists with one instance list each --
-    and is not modified: range-checked columns are completed on copies (complete_range_check_witness; its ValueError
-    propagates) and no blinding value is written.  Under a multi-rank Device the check runs on this rank's GPU alone.
+    and is not modified: range-checked columns are completed on copies (complete_range_check_witness, or its device form
+    for resident / Montgomery columns and with `range_checks_on_device`; the ValueError propagates) and no blinding value
+    is written.  Under a multi-rank Device the check runs on this rank's GPU alone.
 
       gates     every polynomial of every gate at the usable rows: all of them Horner-folded in a random y (from `seed`) in one
                 base-domain evaluation, then the rows where that is non-zero interpreted polynomial by polynomial
@@ -2406,7 +2509,8 @@ def check_witness(device, pk, advice, instances=(), seed=0, max_failures=1024, m
     cs, dom = pk.cs, pk.domain
     n = dom.n
     usable = n - (cs.blinding_factors() + 1)
-    advice_sets, instance_sets = _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, copy_range_columns=True)
+    advice_sets, instance_sets = _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, copy_range_columns=True,
+                                               device=D, range_checks_on_device=range_checks_on_device)
     cap = max(int(max_failures), 0)
     y, theta = _check_scalar(seed, b"y"), _check_scalar(seed, b"theta")
     t_last = [time.perf_counter()]

@@ -304,6 +304,41 @@ int h2_dev_logup_counts(const void *d_table, const void *const *d_inputs, size_t
                         size_t row_begin, size_t row_end, void *d_counts, void *d_scratch, size_t scratch_bytes, void *stream);
 int h2_dev_logup_emit(const void *d_counts, size_t usable_rows, size_t n, void *d_m, void *stream);
 
+/* The witness of `advice_column_range` columns, completed after synthesis as create_proof does on the host
+ * (plonk/prover.rs:1699-1783, `sort` :164-200; range_check.rs:40-63 for the values): for each of `pairs` (origin,
+ * companion) column pairs of ONE circuit instance, every value of the range -- vmin, vmin + step, ... below vmax, then
+ * vmax -- is planted in the origin in descending row order, ending at row usable_rows - 1, and rows [0, usable_rows) of
+ * the companion become the counting sort of the origin's; rows >= usable_rows of both are left alone (blinding overwrites
+ * them).  Each column is read and written in its own form:
+ *   CANONICAL   n x 4 u64, the integer            MONTGOMERY  n x 4 u64, as h2_dev_batch_mont leaves a canonical column
+ *   COMPACT     n u64 (as h2_dev_widen_u64 takes them)
+ * d_origins, d_companions, the form codes, vmin, vmax, step and first_unassigned are HOST arrays of `pairs` entries; the
+ * columns of a call are distinct.  first_unassigned[i] = the first row of origin i that synthesis left unassigned (the
+ * reference's assignment tracking, prover.rs:1706-1731), or H2_RANGE_CHECK_UNASSIGNED_UNKNOWN; first_unassigned = NULL
+ * means unknown for every pair.
+ * Nothing of a pair is written unless all of its checks pass, and a pair that fails does not stop the others.  The outcome
+ * is d_status: H2_RANGE_CHECK_STATUS_WORDS u32 per pair = {code, first offending row or 0xffffffff, pair index, 0, and
+ * four words of working state}, final when the stream reaches the end of the call:
+ *   OK            completed
+ *   NO_FIT        the values and one spare cell below them do not fit the usable rows, or first_unassigned reaches into them
+ *   IN_USE        first_unassigned unknown, and the cells to be planted and the spare one are neither all zero nor the
+ *                 planted values already (the same columns completed again)
+ *   OUT_OF_RANGE  a usable row of the origin is outside [vmin, vmax] or has bits above the low 64
+ *   UNSUPPORTED   vmax - vmin >= 2^24, past the counting sort's cap (the caller sorts such a column some other way)
+ * d_scratch: h2_range_check_scratch_bytes(vmin, vmax, pairs) bytes, 16-byte aligned.  Asynchronous on `stream`.  Returns
+ * H2_ERR_INVALID without touching a device, h2_last_error naming the argument, for a null pointer, n not a power of two,
+ * usable_rows > n, vmin > vmax, step == 0, an unknown form code, a misaligned column or too small a scratch. */
+enum { H2_RANGE_CHECK_FORM_CANONICAL = 0, H2_RANGE_CHECK_FORM_MONTGOMERY = 1, H2_RANGE_CHECK_FORM_COMPACT = 2 };
+enum { H2_RANGE_CHECK_OK = 0, H2_RANGE_CHECK_NO_FIT = 1, H2_RANGE_CHECK_IN_USE = 2, H2_RANGE_CHECK_OUT_OF_RANGE = 3,
+       H2_RANGE_CHECK_UNSUPPORTED = 4 };
+#define H2_RANGE_CHECK_STATUS_WORDS 8
+#define H2_RANGE_CHECK_UNASSIGNED_UNKNOWN UINT64_MAX
+size_t h2_range_check_scratch_bytes(const uint64_t *vmin, const uint64_t *vmax, size_t pairs);
+int h2_dev_range_check_complete(void *const *d_origins, void *const *d_companions, const uint32_t *origin_forms,
+                                const uint32_t *companion_forms, const uint64_t *vmin, const uint64_t *vmax,
+                                const uint64_t *step, const uint64_t *first_unassigned, size_t pairs, size_t usable_rows,
+                                size_t n, void *d_status, void *d_scratch, size_t scratch_bytes, void *stream);
+
 /* Fixed-base multiplication, the work of Params::unsafe_setup (poly/commitment.rs:56-124: g[i] = [s^i] G,
  * g_lagrange[i] = [l_i(s)] G, one variable-base multiplication per point under `parallelize` there):
  * points[i] = [scalars[i]] B, with B given as d_table[j] = [2^j] B for j < 254 (affine Montgomery, 64 B each);
