@@ -841,6 +841,15 @@ int h2_msm_shape(size_t n, uint32_t max_bits, uint32_t* c, uint32_t* windows, ui
     return H2_OK;
 }
 
+int h2_ntt_shape(uint32_t log_n, uint32_t in_log, h2_ntt_pass_shape* out, size_t cap, size_t* count) {
+    static_assert(sizeof(h2_ntt_pass_shape) == 9 * sizeof(uint32_t), "h2_ntt_pass_shape is nine words");
+    if (!count || (cap && !out)) return bad("h2_ntt_shape: null argument");
+    if (log_n > 28 || in_log > log_n) return bad("h2_ntt_shape: log_n <= 28 and in_log <= log_n");
+    *count = ntt_shape_query(log_n, in_log, (uint32_t*)out, cap);
+    if (*count > cap) return bad("h2_ntt_shape: `cap` is below the number of passes (see *count)");
+    return H2_OK;
+}
+
 int h2_dev_msm(const void* d_scalars, const void* d_bases, size_t n, uint32_t max_bits, void* d_scratch,
                size_t scratch_bytes, uint64_t out_xyz[12], void* stream) {
     if (!out_xyz || (n && (!d_scalars || !d_bases))) return bad("h2_dev_msm: null argument");

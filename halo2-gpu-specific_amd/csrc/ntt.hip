@@ -801,6 +801,50 @@ static PassShape pass_shape(uint32_t L, uint32_t B, uint32_t avail) {
     return sh;
 }
 
+// the common pass through k_ntt_pass8 (H2_NTT_FUSE=0: k_ntt_pass<true, true, 8, ...>, the ends of a tile through LDS).
+// Read once, like H2_NTT_FIXED.
+static bool pass8_fuse() {
+    static const bool v = !(getenv("H2_NTT_FUSE") && atoi(getenv("H2_NTT_FUSE")) == 0);
+    return v;
+}
+
+// Rows of the first pass that zero padding leaves live: in_len = 2^(L - z) of 2^L elements prunes the first min(z, B) stages
+// of a first pass that is not also the last (H2_NTT_NO_ZSKIP: none)
+static uint32_t pass_zskip(uint32_t L, uint32_t B, size_t p, bool last, uint32_t in_len) {
+    if (p != 0 || last || !in_len || in_len >= (1u << L) || (in_len & (in_len - 1)) != 0 || getenv("H2_NTT_NO_ZSKIP") != nullptr)
+        return 0;
+    uint32_t z = 0;
+    while ((in_len << z) < (1u << L)) z++;  // padded by 2^z
+    return z < B ? z : B;                   // in_len = (R >> z) * S rows exactly when z <= B
+}
+
+// Which kernel a pass runs: one enumerator per launch of ntt_run_chunk (the values are h2_ntt_shape's kernel ids,
+// H2_NTT_KERNEL_* in halo2_hip.h).  The launcher switches on this and h2_ntt_shape reports it: the conditions live here only.
+enum NttKernel : uint32_t {
+    NK_PASS8_CW_DP = H2_NTT_KERNEL_PASS8_CW_DP,      // k_ntt_pass8<true, true>
+    NK_PASS8_CW = H2_NTT_KERNEL_PASS8_CW,            // k_ntt_pass8<true, false>
+    NK_PASS8 = H2_NTT_KERNEL_PASS8,                  // k_ntt_pass8<false, false>
+    NK_FIXED_CW_DP = H2_NTT_KERNEL_FIXED_CW_DP,      // k_ntt_pass<true, true, 8, true, true>
+    NK_FIXED_CW = H2_NTT_KERNEL_FIXED_CW,            // k_ntt_pass<true, true, 8, true, false>
+    NK_R4_LAZY_CW_DP = H2_NTT_KERNEL_R4_LAZY_CW_DP,  // k_ntt_pass<true, true, 0, true, true>
+    NK_R4_LAZY_CW = H2_NTT_KERNEL_R4_LAZY_CW,        // k_ntt_pass<true, true, 0, true, false>
+    NK_FIXED = H2_NTT_KERNEL_FIXED,                  // k_ntt_pass<true, true, 8>
+    NK_R4_LAZY = H2_NTT_KERNEL_R4_LAZY,              // k_ntt_pass<true, true>
+    NK_R4 = H2_NTT_KERNEL_R4,                        // k_ntt_pass<true, false>
+    NK_R2_LAZY = H2_NTT_KERNEL_R2_LAZY,              // k_ntt_pass<false, true>
+    NK_R2 = H2_NTT_KERNEL_R2,                        // k_ntt_pass<false, false>
+};
+static NttKernel pass_kernel(const PassShape& sh, uint32_t zskip, bool fuse, bool last) {
+    const bool dp = sh.cw && !last;  // pairs in tw_direct: the middle passes' tables (a first pass has none)
+    const bool fixed = sh.fixed && zskip == 0;
+    if (fixed && fuse) return sh.cw ? (dp ? NK_PASS8_CW_DP : NK_PASS8_CW) : NK_PASS8;
+    if (sh.cw && fixed) return dp ? NK_FIXED_CW_DP : NK_FIXED_CW;
+    if (sh.cw) return dp ? NK_R4_LAZY_CW_DP : NK_R4_LAZY_CW;
+    if (fixed) return NK_FIXED;
+    if (sh.radix4) return sh.lazy ? NK_R4_LAZY : NK_R4;
+    return sh.lazy ? NK_R2_LAZY : NK_R2;
+}
+
 // ---------------------------------------------------------------- plans
 static std::string plan_key(uint32_t log_n, const uint64_t omega[4]) {
     char buf[128];
@@ -1167,13 +1211,6 @@ void ntt_run_many(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr* const*
     }
 }
 
-// the common pass through k_ntt_pass8 (H2_NTT_FUSE=0: k_ntt_pass<true, true, 8, ...>, the ends of a tile through LDS).
-// Read once, like H2_NTT_FIXED.
-static bool pass8_fuse() {
-    static const bool v = !(getenv("H2_NTT_FUSE") && atoi(getenv("H2_NTT_FUSE")) == 0);
-    return v;
-}
-
 static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr* const* dsts, Fr* const* tmps, uint32_t cnt,
                           uint32_t in_len, const Fr* pre3, const Fr* post3, hipStream_t stream, const Fr* scale_tab,
                           uint32_t scale_mode) {
@@ -1237,11 +1274,7 @@ static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr
         a.sc_lo = scale_tab;
         a.sc_hi = scale_tab ? scale_tab + (1u << LO_BITS) : nullptr;
         a.scale_mode = (scale_tab && ((scale_mode == 1u && p == 0) || (scale_mode == 2u && last))) ? scale_mode : 0u;
-        if (p == 0 && !last && in_len && in_len < (1u << L) && (in_len & (in_len - 1)) == 0 && getenv("H2_NTT_NO_ZSKIP") == nullptr) {
-            uint32_t z = 0;
-            while ((in_len << z) < (1u << L)) z++;  // padded by 2^z
-            a.zskip = z < B ? z : B;               // in_len = (R >> z) * S rows exactly when z <= B
-        }
+        a.zskip = pass_zskip(L, B, p, last, in_len);
         if (last && p > 0 && a.post3_uniform && L > LO_BITS) {
             // iNTT: fold the divisor into the high twiddle table used by the last pass's inter-pass twiddles
             char key[80];
@@ -1364,36 +1397,46 @@ static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr
                     if (dev >= 0 && dev < 64) raised[dev] = true;
                 }
             }
-            const bool dp = cw && !last;      // pairs in tw_direct: the middle passes' tables (a first pass has none)
-            if (sh.fixed && a.zskip == 0 && pass8_fuse() && cw && dp)
-                hipLaunchKernelGGL((k_ntt_pass8<true, true>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
-            else if (sh.fixed && a.zskip == 0 && pass8_fuse() && cw)
-                hipLaunchKernelGGL((k_ntt_pass8<true, false>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
-            else if (sh.fixed && a.zskip == 0 && pass8_fuse())
-                hipLaunchKernelGGL((k_ntt_pass8<false, false>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
-            else if (cw && sh.fixed && a.zskip == 0 && dp)
-                hipLaunchKernelGGL((k_ntt_pass<true, true, 8, true, true>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
-            else if (cw && sh.fixed && a.zskip == 0)
-                hipLaunchKernelGGL((k_ntt_pass<true, true, 8, true, false>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
-            else if (cw && dp)
-                hipLaunchKernelGGL((k_ntt_pass<true, true, 0, true, true>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
-            else if (cw)
-                hipLaunchKernelGGL((k_ntt_pass<true, true, 0, true, false>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
-            else if (sh.fixed && a.zskip == 0)
-                hipLaunchKernelGGL((k_ntt_pass<true, true, 8>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
-            else if (a.radix4 && sh.lazy)
-                hipLaunchKernelGGL((k_ntt_pass<true, true>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
-            else if (a.radix4)
-                hipLaunchKernelGGL((k_ntt_pass<true, false>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
-            else if (sh.lazy)
-                hipLaunchKernelGGL((k_ntt_pass<false, true>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
-            else
-                hipLaunchKernelGGL((k_ntt_pass<false, false>), dim3(ntiles, cnt), dim3(threads), lds, stream, a);
+#define H2_NTT_LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(ntiles, cnt), dim3(threads), lds, stream, a)
+            switch (pass_kernel(sh, a.zskip, pass8_fuse(), last)) {
+                case NK_PASS8_CW_DP: H2_NTT_LAUNCH(k_ntt_pass8<true, true>); break;
+                case NK_PASS8_CW: H2_NTT_LAUNCH(k_ntt_pass8<true, false>); break;
+                case NK_PASS8: H2_NTT_LAUNCH(k_ntt_pass8<false, false>); break;
+                case NK_FIXED_CW_DP: H2_NTT_LAUNCH(k_ntt_pass<true, true, 8, true, true>); break;
+                case NK_FIXED_CW: H2_NTT_LAUNCH(k_ntt_pass<true, true, 8, true, false>); break;
+                case NK_R4_LAZY_CW_DP: H2_NTT_LAUNCH(k_ntt_pass<true, true, 0, true, true>); break;
+                case NK_R4_LAZY_CW: H2_NTT_LAUNCH(k_ntt_pass<true, true, 0, true, false>); break;
+                case NK_FIXED: H2_NTT_LAUNCH(k_ntt_pass<true, true, 8>); break;
+                case NK_R4_LAZY: H2_NTT_LAUNCH(k_ntt_pass<true, true>); break;
+                case NK_R4: H2_NTT_LAUNCH(k_ntt_pass<true, false>); break;
+                case NK_R2_LAZY: H2_NTT_LAUNCH(k_ntt_pass<false, true>); break;
+                case NK_R2: H2_NTT_LAUNCH(k_ntt_pass<false, false>); break;
+            }
+#undef H2_NTT_LAUNCH
         }
         // (`pinned` unpins here: launched -- an eviction from here on synchronises the device before it frees)
         consumed += B;
     }
     H2_HIP(hipGetLastError());
+}
+
+// The plan of a transform as the launcher will run it (h2_ntt_shape): per pass 9 words -- bits, log_c, threads, radix4, lazy,
+// fixed, cw, zskip, kernel id.  Host only: nothing is allocated or launched.
+size_t ntt_shape_query(uint32_t log_n, uint32_t in_log, uint32_t* out, size_t cap) {
+    std::vector<uint32_t> bits;
+    ntt_split(log_n, bits);
+    uint32_t consumed = 0;
+    for (size_t p = 0; p < bits.size() && p < cap; p++) {
+        const uint32_t B = bits[p];
+        const bool last = p + 1 == bits.size();
+        const PassShape sh = pass_shape(log_n, B, last ? consumed : log_n - consumed - B);
+        const uint32_t zskip = pass_zskip(log_n, B, p, last, 1u << in_log);
+        const uint32_t row[9] = {B, sh.log_c, sh.threads, sh.radix4, sh.lazy, sh.fixed, sh.cw, zskip,
+                                 (uint32_t)pass_kernel(sh, zskip, pass8_fuse(), last)};
+        for (int i = 0; i < 9; i++) out[9 * p + i] = row[i];
+        consumed += B;
+    }
+    return bits.size();
 }
 
 }  // namespace h2

@@ -584,6 +584,38 @@ int h2_dev_extended_to_coeff(void *d_a, void *d_tmp, uint32_t extended_k, const 
 size_t h2_msm_scratch_bytes(size_t n, uint32_t max_bits);
 /* the Pippenger shape the library will use: window bits c, number of windows, buckets per window */
 int h2_msm_shape(size_t n, uint32_t max_bits, uint32_t *c, uint32_t *windows, uint32_t *buckets_per_window);
+/* The passes the library will run for a transform of 2^log_n points (best_fft, arithmetic.rs:546) whose first 2^in_log
+ * inputs are live and the rest zero padding (in_log == log_n: none), for reporting and for tests: computed by the
+ * launcher's own split, geometry and kernel selector under the same once-per-process H2_NTT_* knobs.  Host only.  Writes
+ * one entry per pass to out[0 .. cap) and the number of passes to *count; log_n = 0 has none.  log_n > 28,
+ * in_log > log_n, a null pointer or cap < *count: H2_ERR_INVALID (*count is set in the last case). */
+typedef struct {
+    uint32_t bits;    /* width of the pass: 2^bits rows per tile */
+    uint32_t log_c;   /* 2^log_c columns per tile */
+    uint32_t threads; /* lanes per workgroup */
+    uint32_t radix4;  /* two stages per LDS round trip */
+    uint32_t lazy;    /* values below 4p between load and store */
+    uint32_t fixed;   /* the compiled-in geometry: 8 bits, 4 columns, 256 lanes */
+    uint32_t cw;      /* constant-operand twiddles, (value, quotient) pairs */
+    uint32_t zskip;   /* leading stages pruned by zero padding: min(log_n - in_log, bits) on the first of several passes */
+    uint32_t kernel;  /* H2_NTT_KERNEL_* */
+} h2_ntt_pass_shape;
+enum {
+    H2_NTT_KERNEL_PASS8_CW_DP = 0,   /* k_ntt_pass8<true, true> */
+    H2_NTT_KERNEL_PASS8_CW = 1,      /* k_ntt_pass8<true, false> */
+    H2_NTT_KERNEL_PASS8 = 2,         /* k_ntt_pass8<false, false> */
+    H2_NTT_KERNEL_FIXED_CW_DP = 3,   /* k_ntt_pass<true, true, 8, true, true> */
+    H2_NTT_KERNEL_FIXED_CW = 4,      /* k_ntt_pass<true, true, 8, true, false> */
+    H2_NTT_KERNEL_R4_LAZY_CW_DP = 5, /* k_ntt_pass<true, true, 0, true, true> */
+    H2_NTT_KERNEL_R4_LAZY_CW = 6,    /* k_ntt_pass<true, true, 0, true, false> */
+    H2_NTT_KERNEL_FIXED = 7,         /* k_ntt_pass<true, true, 8> */
+    H2_NTT_KERNEL_R4_LAZY = 8,       /* k_ntt_pass<true, true> */
+    H2_NTT_KERNEL_R4 = 9,            /* k_ntt_pass<true, false> */
+    H2_NTT_KERNEL_R2_LAZY = 10,      /* k_ntt_pass<false, true> */
+    H2_NTT_KERNEL_R2 = 11,           /* k_ntt_pass<false, false> */
+    H2_NTT_KERNEL_COUNT = 12
+};
+int h2_ntt_shape(uint32_t log_n, uint32_t in_log, h2_ntt_pass_shape *out, size_t cap, size_t *count);
 int h2_dev_msm(const void *d_scalars, const void *d_bases, size_t n, uint32_t max_bits, void *d_scratch,
                size_t scratch_bytes, uint64_t out_xyz[12], void *stream);
 /* `count` MSMs over the SAME bases (one per column: plonk/prover.rs:293-299 commits every advice column

@@ -151,6 +151,126 @@ def test_msm_shape_and_scratch():
         assert L.h2_msm_scratch_bytes(n, bits) > n * W.value * 8
 
 
+NTT_PASS_WIDTHS = {  # the comment in ntt_split: as many 8-bit passes as possible, the remainder first; a remainder of one
+    0: [], 1: [1], 2: [2], 3: [3], 4: [4], 5: [5], 6: [6], 7: [7], 8: [8],  # bit (and of two bits up to 2^18) as 9-bit passes at the end
+    9: [9], 10: [2, 8], 11: [3, 8], 12: [4, 8], 13: [5, 8], 14: [6, 8], 15: [7, 8], 16: [8, 8], 17: [8, 9], 18: [9, 9],
+    19: [3, 8, 8], 20: [4, 8, 8], 21: [5, 8, 8], 22: [6, 8, 8], 23: [7, 8, 8], 24: [8, 8, 8], 25: [8, 8, 9],
+    26: [2, 8, 8, 8], 27: [3, 8, 8, 8], 28: [4, 8, 8, 8],
+}
+
+
+def test_ntt_shape_reports_the_documented_plan():
+    """h2_ntt_shape, log_n 0 .. 28 and every padding: the pass widths ntt_split documents, summing to log_n; zskip = min(z, B)
+    on the first of several passes and 0 elsewhere; the fixed geometry is 8 bits, 4 columns, 256 lanes; radix-4 and the
+    constant-operand twiddles from 2^18 only; a kernel id inside the enumeration"""
+    import ntt_matrix_cases as mc
+
+    L = h2.lib()
+    assert sorted(NTT_PASS_WIDTHS) == list(range(29))
+    for log_n, widths in NTT_PASS_WIDTHS.items():
+        for in_log in range(log_n + 1):
+            z = log_n - in_log
+            passes = mc.ntt_shape(L, log_n, in_log)
+            assert [p["bits"] for p in passes] == widths, (log_n, in_log)
+            assert sum(p["bits"] for p in passes) == log_n
+            for i, p in enumerate(passes):
+                assert p["zskip"] == (min(z, p["bits"]) if i == 0 and len(passes) > 1 else 0), (log_n, in_log, i)
+                if p["fixed"]:
+                    assert (p["bits"], p["log_c"], p["threads"]) == (8, 2, 256) and p["radix4"] and p["lazy"]
+                assert p["lazy"] == 1 and p["radix4"] == p["cw"] == (1 if log_n >= 18 else 0), (log_n, p)
+                assert p["fixed"] == (1 if log_n >= 18 and p["bits"] == 8 and p["log_c"] == 2 else 0), (log_n, p)
+                assert 64 <= p["threads"] <= 512 and p["kernel"] in mc.ALL_KERNELS
+                consumed = sum(q["bits"] for q in passes[:i])
+                avail = consumed if i + 1 == len(passes) else log_n - consumed - p["bits"]
+                assert p["log_c"] <= avail
+                last = i + 1 == len(passes)
+                if log_n < 18:
+                    assert mc.KERNELS[p["kernel"]] == "k_ntt_pass<false, true>"
+                elif p["fixed"] and p["zskip"] == 0:
+                    assert mc.KERNELS[p["kernel"]] == ("k_ntt_pass8<true, false>" if last else "k_ntt_pass8<true, true>")
+                else:
+                    assert mc.KERNELS[p["kernel"]] == "k_ntt_pass<true, true, 0, true, %s>" % ("false" if last else "true")
+
+
+def test_ntt_shape_bad_arguments():
+    L = h2.lib()
+    out = np.zeros((8, 9), dtype=np.uint32)
+    count = ctypes.c_size_t(77)
+    assert L.h2_ntt_shape(29, 0, out.ctypes.data, 8, ctypes.byref(count)) == 1     # H2_ERR_INVALID: beyond the 2-adicity
+    assert L.h2_ntt_shape(20, 21, out.ctypes.data, 8, ctypes.byref(count)) == 1    # more live inputs than points
+    assert L.h2_ntt_shape(20, 18, out.ctypes.data, 8, None) == 1
+    assert L.h2_ntt_shape(20, 18, None, 8, ctypes.byref(count)) == 1
+    assert count.value == 77 and not out.any() and L.h2_last_error()
+    assert L.h2_ntt_shape(26, 26, out.ctypes.data, 3, ctypes.byref(count)) == 1    # four passes into room for three:
+    assert count.value == 4 and not out[3:].any()                                  # the count is reported, nothing past cap
+    assert L.h2_ntt_shape(26, 26, None, 0, ctypes.byref(count)) == 1 and count.value == 4
+    assert L.h2_ntt_shape(0, 0, None, 0, ctypes.byref(count)) == 0 and count.value == 0
+    assert L.h2_ntt_shape(26, 26, out.ctypes.data, 8, ctypes.byref(count)) == 0 and count.value == 4
+
+
+def test_ntt_matrix_enumerates_without_a_gpu_and_reaches_every_default_kernel():
+    """tests/ntt_matrix_cases.py, the rows of tests/test_gpu_ntt_matrix.py: enumerated here with h2_ntt_shape alone.  At least
+    one row maps to every kernel reachable with default knobs and to no other, so a change of ntt_split or pass_shape that
+    silently moves the coverage fails on any machine; the paddings sit around the first pass's width"""
+    import ntt_matrix_cases as mc
+
+    L = h2.lib()
+    reach = mc.matrix_kernel_ids(L)
+    assert set(reach) == set(mc.DEFAULT_KERNELS), {mc.KERNELS[k]: v[:3] for k, v in reach.items()}
+    assert len(mc.KERNELS) == 12 and mc.DEFAULT_KERNELS < mc.ALL_KERNELS
+    assert mc.MATRIX_SIZES == (9, 10, 16, 17) + tuple(range(18, 25))
+    for log_n in mc.MATRIX_SIZES:
+        cases = mc.matrix_cases(L, log_n)
+        assert len(cases) == len(set(cases))
+        B = mc.first_width(L, log_n)
+        assert B == NTT_PASS_WIDTHS[log_n][0]
+        zs = {c.z for c in cases if c.op == "coeff_to_extended"}
+        if log_n <= 22:
+            assert zs == {z for z in (0, 1, 2, 3, B - 1, B, B + 1, log_n - 1, log_n) if z <= log_n}
+            assert {c.op for c in cases} == set(mc.OPS)
+            assert {c.inp for c in cases} == (set(mc.INPUTS) if log_n <= 21 else {"random", "rm1", "delta_seeded"})
+            assert {c.arbitrary for c in cases if c.op == "coeff_to_extended"} == {False, True}
+        else:
+            assert zs == {1, 2, 3, B} and {c.inp for c in cases} >= {"random", "rm1"}
+        # z >= B: one live row, no stage in the first pass; an odd zskip under the radix-4 stage loop
+        assert any(mc.ntt_shape(L, log_n, log_n - z)[0]["zskip"] == B for z in zs) or len(NTT_PASS_WIDTHS[log_n]) == 1
+    for log_n in mc.CHILD_SIZES:
+        cases = mc.child_cases(L, log_n)
+        assert {c.op for c in cases} == set(mc.OPS) and {c.inp for c in cases} == {"random", "rm1"}
+        assert {c.z for c in cases} == {0, 1, mc.first_width(L, log_n)}
+    assert [s for s in mc.KNOB_SETTINGS if len(s) == 1 and "H2_NTT_FUSE" not in s] == [
+        {"H2_NTT_CONSTW": "0"}, {"H2_NTT_LAZY": "0"}, {"H2_NTT_RADIX4": "0"}, {"H2_NTT_FIXED": "0"}, {"H2_NTT_NINE": "0"},
+        {"H2_NTT_NO_ZSKIP": "1"}, {"H2_NTT_LAST_TABLE": "0"}]
+
+
+def test_ntt_shape_under_every_knob_reaches_every_kernel():
+    """the knob settings of the matrix's child processes, here with h2_ntt_shape alone (a child process each: the knobs are
+    read once): together with the default rows they reach all twelve kernels of ntt_run_chunk"""
+    import ntt_matrix_cases as mc
+
+    code = (
+        "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "import halo2_gpu_specific_amd as h2, ntt_matrix_cases as mc\n"
+        "L = h2.lib(); ids = set()\n"
+        "for log_n in mc.CHILD_SIZES:\n"
+        "    for c in mc.child_cases(L, log_n):\n"
+        "        ids |= mc.kernel_ids(L, log_n, c.z)\n"
+        "print('KERNELS', *sorted(ids))\n"
+    ) % (ROOT, os.path.join(ROOT, "tests"))
+    reached = set(mc.DEFAULT_KERNELS)
+    # what each setting's rows run: the settings that reach nothing new run the default kernels in other geometries
+    want = [{2, 8, 10}, {9, 11}, {10}, {5, 6, 10}, {0, 1, 5, 10}, {0, 1, 5, 6, 10}, {0, 1, 5, 6, 10}, {3, 4, 5, 6, 10}, {7, 8, 10}]
+    assert len(want) == len(mc.KNOB_SETTINGS)
+    for knobs, want_ids in zip(mc.KNOB_SETTINGS, want):
+        env = {k: v for k, v in os.environ.items() if k not in mc.KNOBS}
+        env.update(knobs)
+        out = subprocess.check_output([sys.executable, "-c", code], text=True, env=env, timeout=300)
+        ids = {int(v) for v in out.split()[1:]}
+        assert ids == want_ids, (knobs, sorted(ids))
+        reached |= ids
+    assert reached == set(mc.ALL_KERNELS), sorted(mc.ALL_KERNELS - reached)
+
+
 def test_sharding_plan():
     cols = [parallel.shard_columns(11, 4, r) for r in range(4)]
     assert sorted(sum(cols, [])) == list(range(11))
