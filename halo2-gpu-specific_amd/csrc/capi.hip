@@ -14,6 +14,7 @@
 #include "ntt.hpp"
 #include "poly.hpp"
 #include "logup.hpp"
+#include "permmap.hpp"
 #include "rangecheck.hpp"
 #include "scan.hpp"
 
@@ -1579,6 +1580,30 @@ int h2_dev_range_check_complete(void* const* d_origins, void* const* d_companion
                                            first_unassigned, pairs, usable_rows, n, (uint32_t*)d_status, d_scratch,
                                            pick_stream(ctx, stream));
     });
+}
+
+// ------------------------------------------------------------------ the copy constraints' cycle mapping
+size_t h2_permutation_mapping_scratch_bytes(size_t n_columns, size_t n, size_t copies) {
+    return permutation_mapping_scratch_bytes(n_columns, n, copies);
+}
+
+int h2_dev_permutation_mapping_phases(const uint32_t* d_copies, size_t copies, size_t n_columns, size_t n, uint32_t* d_map_col,
+                                      uint32_t* d_map_row, uint32_t* d_status, void* d_scratch, size_t scratch_bytes,
+                                      float* phase_ms, void* stream) {
+    if (const char* what = permutation_mapping_validate(d_copies, copies, n_columns, n, d_map_col, d_map_row, d_status, d_scratch,
+                                                        scratch_bytes))
+        return bad((std::string("h2_dev_permutation_mapping: ") + what).c_str());
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return permutation_mapping_launch(d_copies, copies, n_columns, n, d_map_col, d_map_row, d_status, d_scratch, phase_ms,
+                                          pick_stream(ctx, stream));
+    });
+}
+
+int h2_dev_permutation_mapping(const uint32_t* d_copies, size_t copies, size_t n_columns, size_t n, uint32_t* d_map_col,
+                               uint32_t* d_map_row, uint32_t* d_status, void* d_scratch, size_t scratch_bytes, void* stream) {
+    return h2_dev_permutation_mapping_phases(d_copies, copies, n_columns, n, d_map_col, d_map_row, d_status, d_scratch,
+                                             scratch_bytes, nullptr, stream);
 }
 
 // ------------------------------------------------------------------ evaluate_h: the generated form

@@ -1114,6 +1114,68 @@ def permutation_mapping(ncols, n, copies):
     return (nxt // n).astype(np.uint32).reshape(ncols, n), (nxt % n).astype(np.uint32).reshape(ncols, n)
 
 
+PM_OK, PM_OUT_OF_BOUNDS, PM_INTERNAL = 0, 1, 2                                         # H2_PERM_MAPPING_*
+PM_STATUS_WORDS = 2
+PERM_MAPPING_SORT_TILE = 4096                                                          # H2_PERM_MAPPING_SORT_TILE
+_U32_MAX = 0xFFFFFFFF
+
+
+def permutation_mapping_device(device, ncols, n, copies, phase_ms=None):
+    """permutation_mapping on the device (csrc/permmap.hip): the same (map_col, map_row), as two device tensors of
+    ncols * n u32 words (int32 storage), column-major -- entry c * n + r is where cell (c, r) maps to.  `copies` crosses
+    to the device once, as u32; a copy whose column position or row is out of bounds raises ValueError (the reference's
+    Error::BoundsFailure) naming the lowest such copy.  ncols * n must be below 2^32.  The scratch of the call is
+    released before this returns.  `phase_ms`: a list that receives [upload, components, compaction + sort, successors]
+    in milliseconds, the device's phases timed by HIP events (tools/keygen_bench.py)."""
+    D, L, torch = device, device.L, device.torch
+    copies = np.asarray(copies).reshape(-1, 4)
+    m = len(copies)
+    if copies.dtype != np.uint32:
+        # a value no u32 holds is out of bounds whatever n is: 0xffffffff keeps it so (ncols, n <= ncols * n < 2^32)
+        wide = np.asarray(copies, dtype=np.int64)
+        if m and (wide.min() < 0 or wide.max() > _U32_MAX):
+            wide = np.where((wide < 0) | (wide > _U32_MAX), _U32_MAX, wide)
+        copies = wide.astype(np.uint32)
+    copies = np.ascontiguousarray(copies)
+    cells = ncols * n
+    if cells > _U32_MAX:
+        raise ValueError("permutation mapping: %d columns of %d rows are 2^32 cells or more" % (ncols, n))
+    if cells == 0:
+        if m:
+            raise ValueError("permutation mapping: copy 0 is out of bounds (BoundsFailure)")
+        with torch.cuda.stream(D.tstream):
+            return tuple(torch.empty(0, dtype=torch.int32, device=D.dev) for _ in range(2))
+    nbytes = L.h2_permutation_mapping_scratch_bytes(ncols, n, m)
+    with torch.cuda.stream(D.tstream):
+        begin = end = None
+        if phase_ms is not None:
+            begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            begin.record(D.tstream)
+        d_copies = torch.from_numpy(copies.view(np.int32)).to(D.dev) if m else None
+        if phase_ms is not None:
+            end.record(D.tstream)
+        map_col = torch.empty(cells, dtype=torch.int32, device=D.dev)
+        map_row = torch.empty(cells, dtype=torch.int32, device=D.dev)
+        status = torch.empty(PM_STATUS_WORDS, dtype=torch.int32, device=D.dev)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=D.dev)
+    args = (d_copies.data_ptr() if m else None, m, ncols, n, map_col.data_ptr(), map_row.data_ptr(), status.data_ptr(),
+            scratch.data_ptr(), nbytes)
+    if phase_ms is None:
+        check(L.h2_dev_permutation_mapping(*args, D.stream), "h2_dev_permutation_mapping")
+    else:
+        ms = (ctypes.c_float * 3)()
+        check(L.h2_dev_permutation_mapping_phases(*args, ms, D.stream), "h2_dev_permutation_mapping")
+        phase_ms[:] = [begin.elapsed_time(end)] + list(ms)
+    with torch.cuda.stream(D.tstream):
+        code, index = status.cpu().numpy().view(np.uint32).tolist()
+    del scratch, d_copies
+    if code == PM_OUT_OF_BOUNDS:
+        raise ValueError("permutation mapping: copy %d is out of bounds (BoundsFailure)" % index)
+    if code != PM_OK:
+        raise H2Error("h2_dev_permutation_mapping: status %d (a bounded loop of the union-find ran out)" % code)
+    return map_col, map_row
+
+
 def vk_digest(cs, dom, fixed_commitments, perm_commitments):
     """VerifyingKey::hash_into (plonk.rs:91-109): Blake2b-512 ("Halo2-Verify-Key") over a u64 length and the pinned
     verifying key, reduced by from_bytes_wide.  The reference pins `format!("{:?}", vk.pinned())` -- the Debug text of
@@ -1193,19 +1255,27 @@ def keygen(device, params, cs, fixed, copies, mapping=None, fixed_montgomery=Fal
     pk.fixed_cosets = [D.coeff_to_extended(t, dom) for t in pk.fixed_polys] if plan is None else None
     # permutation: sigma columns (Lagrange), polys, cosets
     ncols = len(cs.perm_columns)
-    map_col, map_row = mapping if mapping is not None else permutation_mapping(ncols, n, copies)
-    assert len(map_col) == ncols and all(len(c) == n for c in map_col)
-    pk.mapping = (map_col, map_row)
+    if mapping is None and D.dev.type == "cuda" and ncols * n <= _U32_MAX and os.environ.get("H2_PERM_MAPPING") != "host":
+        # built on the device and downloaded once: formats.circuit_data_write and check_witness read pk.mapping
+        d_col, d_row = permutation_mapping_device(D, ncols, n, copies)
+        with D.torch.cuda.stream(D.tstream):
+            pk.mapping = tuple(t.cpu().numpy().view(np.uint32).reshape(ncols, n) for t in (d_col, d_row))
+    else:
+        # a given mapping (keygen_from_info), 2^32 cells or more, H2_PERM_MAPPING=host, or a Device whose vectors live in
+        # host memory (the host-slice data flow: the reference's cycles are host data): one block each
+        map_col, map_row = mapping if mapping is not None else permutation_mapping(ncols, n, copies)
+        assert len(map_col) == ncols and all(len(c) == n for c in map_col)
+        pk.mapping = (map_col, map_row)
+        with D.torch.cuda.stream(D.tstream):
+            d_col, d_row = (D.torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.uint32).reshape(-1)).view(np.int32))
+                            .to(D.dev) for a in (map_col, map_row))
     pk.sigma_values = []
     for i in range(ncols):
         out = D.empty(n)
-        with D.torch.cuda.stream(D.tstream):
-            mc = D.torch.from_numpy(np.ascontiguousarray(map_col[i], dtype=np.uint32).view(np.int32)).to(D.dev)
-            mr = D.torch.from_numpy(np.ascontiguousarray(map_row[i], dtype=np.uint32).view(np.int32)).to(D.dev)
-        check(L.h2_dev_permutation_sigma(out.data_ptr(), mc.data_ptr(), mr.data_ptr(), n, _fr(DELTA), _fr(dom.omega),
-                                         D.stream), "h2_dev_permutation_sigma")
-        D.sync()
+        check(L.h2_dev_permutation_sigma(out.data_ptr(), d_col[i * n:(i + 1) * n].data_ptr(), d_row[i * n:(i + 1) * n].data_ptr(),
+                                         n, _fr(DELTA), _fr(dom.omega), D.stream), "h2_dev_permutation_sigma")
         pk.sigma_values.append(out)
+    del d_col, d_row
     pk.perm_commitments = D.msm_batch(pk.sigma_values, params.g_lagrange, n, 254)
     pk.sigma_polys = [D.intt(D.clone(t), dom) for t in pk.sigma_values]
     pk.sigma_cosets = [D.coeff_to_extended(t, dom) for t in pk.sigma_polys] if plan is None else None

@@ -339,6 +339,36 @@ int h2_dev_range_check_complete(void *const *d_origins, void *const *d_companion
                                 const uint64_t *step, const uint64_t *first_unassigned, size_t pairs, size_t usable_rows,
                                 size_t n, void *d_status, void *d_scratch, size_t scratch_bytes, void *stream);
 
+/* The permutation argument's cycle mapping from the copy constraints (plonk/permutation/keygen.rs:49-145: the cycles the
+ * copies induce, every cycle sorted by (column, row), each cell mapped to its successor and the last to the first), built
+ * on the device.  d_copies: `copies` x 4 u32, row-major, each row (left column position, left row, right column position,
+ * right row) with column positions below n_columns and rows below n; null is allowed when copies == 0, which gives the
+ * identity.  d_map_col, d_map_row: n_columns x n u32 each, column-major (entry c n + r = where cell (c, r) maps to) -- what
+ * h2_dev_check_copies reads whole and h2_dev_permutation_sigma reads column by column.  n_columns * n < 2^32.
+ * The outcome is d_status, H2_PERM_MAPPING_STATUS_WORDS u32 = {code, index of the lowest offending copy or 0xffffffff},
+ * final when the stream reaches the end of the call:
+ *   OK             the mapping is complete
+ *   OUT_OF_BOUNDS  a copy names a column position >= n_columns or a row >= n; the mapping's content is unspecified
+ *   INTERNAL       a bounded loop of the union-find ran out (a defect, never an input); the content is unspecified
+ * The mapping is a function of the copies as a SET of pairs: their order, duplicates, orientation and the scheduling of the
+ * device leave every byte of it the same, call after call.
+ * d_scratch: h2_permutation_mapping_scratch_bytes(n_columns, n, copies) bytes, 16-byte aligned (as d_copies); the function
+ * returns 0 for sizes the call refuses.  Asynchronous on `stream`.  Returns H2_ERR_INVALID without touching a device,
+ * h2_last_error naming the argument, for a null output, status or scratch pointer, null d_copies with copies > 0,
+ * n_columns == 0, n == 0, n_columns * n >= 2^32, a misaligned pointer or too small a scratch.
+ * h2_dev_permutation_mapping_phases is the same call timed for tools/keygen_bench.py: phase_ms[0 .. 2] = milliseconds
+ * (HIP events) of the components, of compaction + sort and of the successors; it returns when the stream has drained.
+ * H2_PERM_MAPPING_SORT_TILE: the (label, cell) pairs a workgroup of the radix sort ranks (tests size their inputs around it). */
+enum { H2_PERM_MAPPING_OK = 0, H2_PERM_MAPPING_OUT_OF_BOUNDS = 1, H2_PERM_MAPPING_INTERNAL = 2 };
+#define H2_PERM_MAPPING_STATUS_WORDS 2
+#define H2_PERM_MAPPING_SORT_TILE 4096
+size_t h2_permutation_mapping_scratch_bytes(size_t n_columns, size_t n, size_t copies);
+int h2_dev_permutation_mapping(const uint32_t *d_copies, size_t copies, size_t n_columns, size_t n, uint32_t *d_map_col,
+                               uint32_t *d_map_row, uint32_t *d_status, void *d_scratch, size_t scratch_bytes, void *stream);
+int h2_dev_permutation_mapping_phases(const uint32_t *d_copies, size_t copies, size_t n_columns, size_t n,
+                                      uint32_t *d_map_col, uint32_t *d_map_row, uint32_t *d_status, void *d_scratch,
+                                      size_t scratch_bytes, float *phase_ms, void *stream);
+
 /* Fixed-base multiplication, the work of Params::unsafe_setup (poly/commitment.rs:56-124: g[i] = [s^i] G,
  * g_lagrange[i] = [l_i(s)] G, one variable-base multiplication per point under `parallelize` there):
  * points[i] = [scalars[i]] B, with B given as d_table[j] = [2^j] B for j < 254 (affine Montgomery, 64 B each);
