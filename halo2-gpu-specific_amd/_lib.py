@@ -133,6 +133,7 @@ SYMBOLS = {
     "h2_dev_check_lookup": (ctypes.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, _u32, _u32, _vp, _sz, _vp, _vp, _sz, _vp]),
     "h2_dev_check_shuffle": (ctypes.c_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _sz, _vp]),
     "h2_dev_check_copies": (ctypes.c_int, [_vp, _sz, _vp, _vp, _sz, _u32, _vp, _vp, _sz, _vp]),
+    "h2_dev_g1_check_points": (ctypes.c_int, [_vp, _sz, _u32, _u32, _vp, _vp, _sz, _vp]),
     "h2_dev_fixed_base_mul": (ctypes.c_int, [_vp, _vp, _sz, _vp, _vp]),
     "h2_g1_ntt_scratch_bytes": (_sz, [_u32]),
     "h2_dev_g1_ntt": (ctypes.c_int, [_vp, _vp, _u32, ctypes.c_int, _vp, _sz, _vp]),

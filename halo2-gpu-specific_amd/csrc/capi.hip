@@ -17,6 +17,7 @@
 #include "permmap.hpp"
 #include "rangecheck.hpp"
 #include "scan.hpp"
+#include "srscheck.hpp"
 
 using namespace h2;
 
@@ -1808,6 +1809,16 @@ int h2_dev_check_copies(const void* const* d_columns, size_t n_columns, const ui
         DeviceCtx* ctx = current_ctx();
         return check_copies_launch((const Fr* const*)d_columns, n_columns, d_map_col, d_map_row, n, circuit, d_count, d_records, cap,
                                    pick_stream(ctx, stream));
+    });
+}
+
+// ------------------------------------------------------------------ SRS point screening (srscheck.hip)
+int h2_dev_g1_check_points(const void* d_points, size_t n, uint32_t table, uint32_t flags, uint64_t* d_count,
+                           h2_check_record* d_records, size_t cap, void* stream) {
+    if (int rc = g1_check_points_args(d_points, n, flags, d_count, d_records, cap)) return rc;
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return g1_check_points_launch(d_points, n, table, flags, d_count, d_records, cap, pick_stream(ctx, stream));
     });
 }
 

@@ -8,9 +8,10 @@
 //   k_check_shuffle_*     counts both sides' compressed values in one hash table, then reports the input rows whose value
 //                         is counted differently (check.hpp: how this differs from the reference)
 //   k_check_copies        value(c, r) against value(mapping(c, r)) for every permutation column and row (dev.rs:1272-1310)
-// Every failure goes through check_append (check.hpp: the append scheme).
+// Every failure goes through check_append (append.hpp; check.hpp: the append scheme).
 #include <algorithm>
 
+#include "append.hpp"
 #include "check.hpp"
 #include "common.hpp"
 #include "evalh_interp.hpp"
@@ -18,26 +19,6 @@
 #include "ntt.hpp"
 
 namespace h2 {
-
-// The slot of this lane among the lanes of its wave that `take`, in a buffer whose fill count is *counter: one agent-scope
-// atomic per wave.  Called by every lane of the wave (wave-uniform control flow); the lanes that do not take get garbage.
-__device__ __forceinline__ unsigned long long wave_slot(bool take, unsigned long long* counter) {
-    const unsigned long long mask = __ballot(take);
-    if (mask == 0) return 0;
-    const uint32_t lane = threadIdx.x & 63;
-    const int leader = __ffsll(mask) - 1;
-    unsigned long long base = 0;
-    if ((int)lane == leader)
-        base = __hip_atomic_fetch_add(counter, (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    base = __shfl(base, leader, 64);
-    return base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1));
-}
-
-__device__ __forceinline__ void check_append(bool fail, uint32_t kind, uint32_t index, uint32_t sub, uint32_t row,
-                                             unsigned long long* count, h2_check_record* out, unsigned long long cap) {
-    const unsigned long long slot = wave_slot(fail, count);
-    if (fail && slot < cap) *reinterpret_cast<uint4*>(out + slot) = make_uint4(kind, index, sub, row);
-}
 
 __global__ void __launch_bounds__(256) k_check_nonzero_rows(const Fr* values, uint32_t usable, uint32_t* rows,
                                                             unsigned long long* row_count) {

@@ -60,12 +60,15 @@ def _points_read(device, f, n):
     return pts
 
 
-def params_read(device, path, k=None):
+def params_read(device, path, k=None, verify=False, seed=None):
     """Params::read -> (Params with both tables resident on the device, additional_data).
     `k` below the file's: the parameters of 2^k rows from the same setup -- only the first 2^k points of g are read and
     decompressed (the g of a smaller k is a prefix), g_lagrange is derived from them (Params.from_powers: the basis is not
     a prefix), the rest of the file is skipped; additional_data ([s]G2) does not depend on k and comes back unchanged.
-    `k` above the file's raises ValueError; None or the file's own k reads the file as it is."""
+    `k` above the file's raises ValueError; None or the file's own k reads the file as it is.
+    `verify`: the parameters go through Params.assert_valid before they are returned, with the file's additional_data as
+    [s]G2 (when it is the 64 bytes of one) and `seed` for the check's randomness: params_check.ParamsError for a file whose
+    points, powers or Lagrange basis are wrong.  Off by default -- the reference reads the points as they come."""
     with open(path, "rb") as f:
         (file_k,) = struct.unpack("<I", f.read(4))
         if k is not None and k > file_k:
@@ -74,14 +77,20 @@ def params_read(device, path, k=None):
             g = _points_read(device, f, 1 << k)
             f.seek(4 + 64 * (1 << file_k))             # past the rest of g and all of g_lagrange
             additional = _additional_read(f)
-            return Params.from_powers(device, k, g), additional
+            return _checked(device, Params.from_powers(device, k, g), additional, verify, seed), additional
         n = 1 << file_k
         tables = [_points_read(device, f, n) for _ in range(2)]
         (alen,) = struct.unpack("<I", f.read(4))
         additional = f.read(alen)
         if len(additional) != alen:
             raise IOError("truncated params file")
-    return Params(device, file_k, tables[0], tables[1]), additional
+    return _checked(device, Params(device, file_k, tables[0], tables[1]), additional, verify, seed), additional
+
+
+def _checked(device, params, additional, verify, seed):
+    if verify:
+        params.assert_valid(device, s_g2=additional if len(additional) == 64 else None, seed=seed)
+    return params
 
 
 def params_additional_data(params):

@@ -1063,6 +1063,42 @@ class Params:
             g = self.g[: 1 << k].clone()
         return Params.from_powers(device, k, g)
 
+    def verify(self, device, s_g2=None, seed=None, locate=True, max_failures=64):
+        """Checks these parameters on the device -> params_check.ParamsReport (the reference has no such step: Params::read
+        unwraps `from_bytes` per point, poly/commitment.rs:262-275, and Params::verifier trusts the rest, :297-317).
+
+          points    both tables through h2_dev_g1_check_points, the identity forbidden (s^i is never 0; an identity in
+                    g_lagrange means s^n = 1): `points` = sorted (table, index, kind) of the first max_failures, `points_total`
+                    the exact count.  Any bad point skips the structure checks (`powers` and `lagrange` None, `ok` False):
+                    a point that failed the screen never reaches an MSM.
+          powers    g[i + 1] = [s] g[i] against `s_g2` = [s]G2 -- 16 limbs, the 64 compressed bytes of an SRS file's
+                    additional_data, or self.s_g2 when None -- by one random linear combination and one pairing.  Without any
+                    [s]G2 `powers` is None: not a failure of the SRS, but `ok` is False.
+          lagrange  g_lagrange is the basis that g, as given, implies (the convention of from_powers) by one random linear
+                    combination; reported even when `powers` is False.
+        A false accept has probability 1/r per check.  With `locate`, a failed check is bisected for `first_bad_power` (the
+        lowest i with g[i + 1] != [s] g[i]) / `first_bad_lagrange` (the lowest i whose entry differs from the implied basis):
+        at most k + 1 probes of one MSM batch each.  `g0_is_generator` (g[0] == (1, 2)) is information only: a ceremony may
+        use another base point.  `timings`: milliseconds per phase.  `ok` = no bad point, `powers` True and `lagrange` True.
+
+        The random key is 32 bytes of os.urandom; `seed` gives a deterministic one (rng.py's test-only stream): the same seed
+        gives the same report.  A Device in a process group raises ValueError: one device is the scope.
+
+        The check READS THE TENSORS self.g and self.g_lagrange.  The shifted-base tables were built from them at construction:
+        a caller who writes into them afterwards has stale tables, and this check does not see that."""
+        from .params_check import verify_params
+
+        return verify_params(device, self, s_g2=s_g2, seed=seed, locate=locate, max_failures=max_failures)
+
+    def assert_valid(self, device, **kw):
+        """`verify`, raising params_check.ParamsError (a ValueError carrying `.report`) unless the report is ok"""
+        from .params_check import ParamsError
+
+        report = self.verify(device, **kw)
+        if not report.ok:
+            raise ParamsError(report)
+        return report
+
     @staticmethod
     def synthetic(device, k, seed=0x48414C4F32):
         """Timing-only parameters: two tables of valid curve points with no common trapdoor, so proofs made

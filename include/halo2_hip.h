@@ -744,6 +744,24 @@ int h2_dev_check_shuffle(const void *d_input, const void *d_shuffle, size_t usab
 int h2_dev_check_copies(const void *const *d_columns, size_t n_columns, const uint32_t *d_map_col, const uint32_t *d_map_row,
                         size_t n, uint32_t circuit, uint64_t *d_count, h2_check_record *d_records, size_t cap, void *stream);
 
+/* ---- screening the points of an SRS ------------------------------------------------------------------------------------
+ * The reference takes the points of its parameters as they come: Params::read unwraps `from_bytes` per point
+ * (poly/commitment.rs:262-275) and a table built in memory is never looked at.  h2_dev_g1_check_points tests each of the n
+ * affine Montgomery points (64 B each; any n <= 2^28) of d_points, one lane per point.  A point fails in exactly one way,
+ * tested in this order:
+ *   H2_SRS_NONCANONICAL  x or y, as stored limbs, is >= q
+ *   H2_SRS_IDENTITY      the point is (0, 0) -- only with H2_SRS_FORBID_IDENTITY in `flags`; otherwise the identity passes
+ *   H2_SRS_OFF_CURVE     y^2 != x^3 + 3 (BN254 G1 has cofactor 1: a point on the curve is in the group)
+ * and appends one record {kind, index = table, sub = 0, row = point index} by the scheme of the witness checks above: one
+ * agent-scope atomic per wave, a record stored only below `cap`, *d_count exact after the buffer fills.  The count
+ * accumulates: a call for g with table = 0 and one for g_lagrange with table = 1 share one buffer and one download.
+ * Asynchronous on `stream`.  H2_ERR_INVALID, without touching a device, for a null d_points with n > 0, a null d_count, null
+ * records with cap > 0, n > 2^28 or an unknown flag. */
+enum { H2_SRS_NONCANONICAL = 0, H2_SRS_IDENTITY = 1, H2_SRS_OFF_CURVE = 2 };
+enum { H2_SRS_FORBID_IDENTITY = 1 };
+int h2_dev_g1_check_points(const void *d_points, size_t n, uint32_t table, uint32_t flags, uint64_t *d_count,
+                           h2_check_record *d_records, size_t cap, void *stream);
+
 /* ---- the verifier's pairing and G2 (host only: no entry below touches a device) ---------------
  * What the reference takes from the pairing_bn256 crate on the verifier side.  G1: 64 B affine Montgomery, identity (0,0).
  * G2 (the twist y^2 = x^3 + 3/(9+u) over Fq2 = Fq[u]/(u^2+1)): 128 B = x.c0, x.c1, y.c0, y.c1 in Montgomery form,
