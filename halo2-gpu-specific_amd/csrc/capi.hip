@@ -10,12 +10,14 @@
 #include "common.hpp"
 #include "evalh.hpp"
 #include "g1ntt.hpp"
+#include "g1util.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
 #include "poly.hpp"
 #include "logup.hpp"
 #include "permmap.hpp"
 #include "rangecheck.hpp"
+#include "resident.hpp"
 #include "scan.hpp"
 #include "srscheck.hpp"
 

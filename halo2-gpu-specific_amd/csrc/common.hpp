@@ -62,7 +62,7 @@ void host_download(void* dst, const void* d_src, size_t bytes, hipStream_t s);
 
 struct NttPlan;  // ntt.hip
 
-// device copy of a registered host range of SRS points (msm.hip): `gen` is the registration it was uploaded for
+// device copy of a registered host range of SRS points (resident.hip): `gen` is the registration it was uploaded for
 struct ResidentCopy {
     void* ptr = nullptr;
     size_t len = 0;
@@ -73,7 +73,7 @@ struct ResidentCopy {
 // registered SRS ranges (1 GiB + a 12 GiB table at k = 24: never per slot) and their accounting.
 struct DeviceShared {
     std::mutex mu;                     // guards `resident` (a lookup may upload an SRS) and plan creation across the slots
-    std::map<const void*, ResidentCopy> resident;  // registered host base ranges -> device copies (msm.hip)
+    std::map<const void*, ResidentCopy> resident;  // registered host base ranges -> device copies (resident.hip)
     std::vector<ResidentCopy> retired;  // copies whose registration was replaced: freed by the next h2_bases_unregister, under every slot's lock
     std::map<std::string, NttPlan*> plans;
     size_t ntt_last_table_bytes = 0;   // of the optional last-pass tables (ntt.hip; guarded by ntt.hip's table mutex)

@@ -159,6 +159,29 @@ H2_DEV Jacobian xyzz_to_jacobian(const XYZZ& p) {
     return r;
 }
 
+// 1 / a = a^(q - 2)
+__device__ __forceinline__ Fq fq_inv_device(const Fq& a) {
+    // q - 2, little-endian u32 limbs
+    const uint32_t E[8] = {0xd87cfd45u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u,
+                           0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
+    Fq acc = fp_one<FqParams>();
+#pragma unroll 1
+    for (int bit = 253; bit >= 0; bit--) {
+        acc = fp_sqr(acc);
+        if ((E[bit >> 5] >> (bit & 31)) & 1) acc = fp_mul(acc, a);
+    }
+    return acc;
+}
+// Jacobian (X, Y, Z) -> XYZZ (X, Y, Z^2, Z^3)
+H2_DEV XYZZ jacobian_to_xyzz(const Jacobian& p) {
+    XYZZ q;
+    q.x = p.x;
+    q.y = p.y;
+    q.zz = fp_sqr(p.z);
+    q.zzz = fp_mul(q.zz, p.z);
+    return q;
+}
+
 H2_DEV XYZZ xyzz_load(const XYZZ* p) {
     XYZZ r;
     r.x = fp_load(&p->x);

@@ -30,7 +30,7 @@
 #include "common.hpp"
 #include "evalh.hpp"
 #include "evalh_interp.hpp"
-#include "msm.hpp"
+#include "resident.hpp"
 #include "evalh_gen.hpp"
 #include "ntt.hpp"
 #include "poly.hpp"

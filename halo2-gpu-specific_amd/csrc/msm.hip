@@ -29,12 +29,14 @@
 // lives in slot b + s: along the sorted list either b or s grows at every emission, so slots are
 // unique, a bucket's partials are contiguous, and no second prefix sum is needed.
 #include <algorithm>
-#include <array>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
-#include <thread>
+#include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "common.hpp"
 #include "ec_quad.hpp"
@@ -84,10 +86,53 @@ struct MsmShape {
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// an integer knob of the environment: `fallback` when it is unset or outside [lo, hi]
+static int env_int(const char* name, int lo, int hi, int fallback) {
+    const char* env = getenv(name);
+    const int v = env ? atoi(env) : fallback;
+    return (env && v >= lo && v <= hi) ? v : fallback;
+}
+
+static uint32_t clamp_bits(uint32_t max_bits) { return max_bits > 254 ? 254u : max_bits ? max_bits : 1u; }
+
+// slice length: aim at >= 2^18 slices (one resident round of the chip at 4 waves/SIMD), 8 <= S <= 64
+static uint32_t slice_log(size_t entries, size_t per_bucket) {
+    uint32_t log_s = 6;
+    while (log_s > 3 && (entries >> log_s) < (1u << 18)) log_s--;
+    // large MSMs: keep the partials per bucket low (k_finish folds <= FINISH_SERIAL of them per thread, more go through
+    // the heavy-bucket path) by lengthening the slices while at least 2^20 of them remain
+    while (log_s < 10 && (entries >> (log_s + 1)) >= (1u << 20) && (per_bucket >> log_s) > 2) log_s++;
+    return (uint32_t)env_int("H2_MSM_SLICE_LOG", 1, 10, (int)log_s);
+}
+
+// the scratch regions of a shape whose counts are set, each aligned to 256 bytes
+static void msm_layout(MsmShape& s) {
+    s.max_items = (s.entries >> s.log_s) + s.nbt + 2;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { return std::exchange(o, align_up(o + bytes, 256)); };
+    s.off_keys = take(s.entries * 4);
+    s.off_sorted = take(s.entries * 4);
+    s.off_tmp = take(s.entries * 8);
+    s.off_pcount = take(((size_t)s.np + 2) * 4);
+    s.off_pbase = take(((size_t)s.np + 2) * 4);
+    s.off_pcursor = take(((size_t)s.np + 2) * 4);
+    s.off_starts = take(((size_t)s.nbt + 2) * 4);
+    s.off_heavy = take(((size_t)s.nbt + 2) * 4);
+    s.off_partials = take(s.max_items * sizeof(XYZZ));
+    s.off_buckets = take((size_t)s.nbt * sizeof(XYZZ));
+    s.off_winpart = take(((size_t)s.Wt * (1 + s.RG) + s.planes) * sizeof(XYZZ));  // window sums, then the RG group partials of each
+    s.off_rcount = take((size_t)s.Wt * 4);
+    s.off_planes = s.planes ? take(((size_t)s.chunks + (size_t)s.planes * s.plane_seg) * sizeof(XYZZ) + (size_t)s.planes * 4 + 64) : 0;
+    s.off_bflags = take(s.n / 256 + 4);  // one byte per 256-row block: the block is one entry of the dominant-value bucket
+    s.off_coltab = take((size_t)(s.cols ? s.cols : 1) * 64);
+    // two-level partition: the entries pass through a second 8-byte-per-entry buffer
+    s.off_tmpa = s.two_level ? take(s.entries * 8 + (PARTA_GROUPS_MAX * 3 + 4) * 4) : 0;
+    s.total = o;
+}
+
 static MsmShape msm_shape(size_t n, uint32_t max_bits, bool hot, uint32_t cols = 0) {
     MsmShape s{};
-    if (max_bits > 254) max_bits = 254;
-    if (max_bits == 0) max_bits = 1;
+    max_bits = clamp_bits(max_bits);
     s.n = n;
     // cost model: W * (n + 3 * 2^(c-1)) group additions
     double best = 1e300;
@@ -103,11 +148,7 @@ static MsmShape msm_shape(size_t n, uint32_t max_bits, bool hot, uint32_t cols =
             best_c = c;
         }
     }
-    if (const char* env = getenv("H2_MSM_WINDOW")) {
-        int v = atoi(env);
-        if (v >= 2 && v <= 18) best_c = (uint32_t)v;  // k_reduce folds <= 128 groups per window
-    }
-    s.c = best_c;
+    s.c = (uint32_t)env_int("H2_MSM_WINDOW", 2, 18, (int)best_c);  // (<= 18: k_reduce folds <= 128 groups per window)
     s.W = (max_bits + 1 + s.c - 1) / s.c;
     // Balanced windows.  max_bits + 1 bits cut into W digits of c bits leave the top window whatever remains -- 7 bits
     // at c = 13, 2 bits at c = 12, 5 at c = 10: a window whose n digits share a handful of buckets, i.e. one sort
@@ -138,9 +179,10 @@ static MsmShape msm_shape(size_t n, uint32_t max_bits, bool hot, uint32_t cols =
         uint32_t R = 1;
         // ... until there are >= 128 partitions and a bucket holds <= 2048 entries on average (k_finish_mid's range of
         // slice partials even when half the buckets go unused, as with booleans), while the buckets stay few against
-        // the entries and a range keeps >= 2048 rows
+        // the entries and a range keeps >= 2048 rows -- and the windows, the dominant scalar's included, stay within the
+        // 16384 partitions of the sort (2^26 booleans asked for 16385: the lo_bits loop below never ended)
         while ((R * base_np < 128 || n / ((size_t)R * s.W * s.nb) > 2048) && (size_t)2 * R * s.W * s.nb * 4 <= n &&
-               (n / (2 * R)) >= 2048)
+               (n / (2 * R)) >= 2048 && (size_t)2 * R * s.W + 1 <= 16384)
             R *= 2;
         if (R > 1) {
             uint32_t shift = 11;
@@ -161,24 +203,13 @@ static MsmShape msm_shape(size_t n, uint32_t max_bits, bool hot, uint32_t cols =
             break;
         }
     }
-    if (const char* env = getenv("H2_MSM_REDUCE_QM")) {
-        int v = atoi(env);
-        if (v >= 1 && v <= 64 && (s.nb + REDUCE_T / 4 * v - 1) / (REDUCE_T / 4 * v) <= REDUCE_T / 4) s.qm = (uint32_t)v;
-    }
+    if (const uint32_t v = (uint32_t)env_int("H2_MSM_REDUCE_QM", 1, 64, 0))
+        if ((s.nb + REDUCE_T / 4 * v - 1) / (REDUCE_T / 4 * v) <= REDUCE_T / 4) s.qm = v;
     uint32_t per_group = REDUCE_T / 4 * s.qm;
     s.RG = (s.nb + per_group - 1) / per_group;
     s.G = 1;
     s.entries = n * s.Wk;
-    // slice length: aim at >= 2^18 slices (one resident round of the chip at 4 waves/SIMD), 8 <= S <= 64
-    s.log_s = 6;
-    while (s.log_s > 3 && (s.entries >> s.log_s) < (1u << 18)) s.log_s--;
-    // large MSMs: keep the partials per bucket low (k_finish folds <= FINISH_SERIAL of them per thread, more go through
-    // the heavy-bucket path) by lengthening the slices while at least 2^20 of them remain
-    while (s.log_s < 10 && (s.entries >> (s.log_s + 1)) >= (1u << 20) && ((n / s.nb) >> s.log_s) > 2) s.log_s++;
-    if (const char* env = getenv("H2_MSM_SLICE_LOG")) {
-        int v = atoi(env);
-        if (v >= 1 && v <= 10) s.log_s = (uint32_t)v;
-    }
+    s.log_s = slice_log(s.entries, n / s.nb);
     // two-level counting sort: the low bits of a bucket id are resolved inside LDS (k_bucket_sort), the
     // high bits select one of 2^hi_bits partitions per window (k_partition); W << hi_bits <= 16384 so
     // the per-workgroup partition histogram of k_digits fits in 64 KiB of LDS
@@ -186,28 +217,7 @@ static MsmShape msm_shape(size_t n, uint32_t max_bits, bool hot, uint32_t cols =
     while (((size_t)s.Wt << (s.c - 1 - s.lo_bits)) > 16384) s.lo_bits++;
     s.hi_bits = s.c - 1 - s.lo_bits;
     s.np = s.Wt << s.hi_bits;
-    s.max_items = (s.entries >> s.log_s) + s.nbt + 2;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o = align_up(o + bytes, 256);
-        return r;
-    };
-    s.off_keys = take(s.entries * 4);
-    s.off_sorted = take(s.entries * 4);
-    s.off_tmp = take(s.entries * 8);
-    s.off_pcount = take(((size_t)s.np + 2) * 4);
-    s.off_pbase = take(((size_t)s.np + 2) * 4);
-    s.off_pcursor = take(((size_t)s.np + 2) * 4);
-    s.off_starts = take(((size_t)s.nbt + 2) * 4);
-    s.off_heavy = take(((size_t)s.nbt + 2) * 4);
-    s.off_partials = take(s.max_items * sizeof(XYZZ));
-    s.off_buckets = take((size_t)s.nbt * sizeof(XYZZ));
-    s.off_winpart = take((size_t)s.Wt * (1 + s.RG) * sizeof(XYZZ));  // window sums, then the RG group partials of each
-    s.off_rcount = take((size_t)s.Wt * 4);
-    s.off_bflags = take(n / 256 + 4);  // one byte per 256-row block: the block is one entry of the dominant-value bucket
-    s.off_coltab = take((size_t)(cols ? cols : 1) * 64);
-    s.total = o;
+    msm_layout(s);
     return s;
 }
 
@@ -243,8 +253,7 @@ static uint32_t table_digits_used(const ShiftTable& t, uint32_t max_bits) {
 
 static MsmShape msm_shape_table(size_t n, uint32_t max_bits, bool hot, const ShiftTable& t) {
     MsmShape s{};
-    if (max_bits > 254) max_bits = 254;
-    if (max_bits == 0) max_bits = 1;
+    max_bits = clamp_bits(max_bits);
     s.n = n;
     s.tab = 1;
     s.tab_stride = t.n;
@@ -261,51 +270,23 @@ static MsmShape msm_shape_table(size_t n, uint32_t max_bits, bool hot, const Shi
     // as still leaves a workgroup per CU (<= 64 buckets: a chain of 128 additions)
     s.qm = 4;
     while (s.qm < 64 && (s.nb + REDUCE_T / 4 * s.qm - 1) / (REDUCE_T / 4 * s.qm) > 256) s.qm *= 2;
-    if (const char* env = getenv("H2_MSM_REDUCE_QM")) {
-        int v = atoi(env);
-        if (v >= 1 && v <= 64) s.qm = (uint32_t)v;
-    }
+    s.qm = (uint32_t)env_int("H2_MSM_REDUCE_QM", 1, 64, (int)s.qm);
     const uint32_t per_group = REDUCE_T / 4 * s.qm;
     s.RG = (s.nb + per_group - 1) / per_group;
     s.G = 1;
     s.entries = n * s.Wk;
-    s.log_s = 6;
-    while (s.log_s > 3 && (s.entries >> s.log_s) < (1u << 18)) s.log_s--;
-    while (s.log_s < 10 && (s.entries >> (s.log_s + 1)) >= (1u << 20) && ((s.entries / s.nb) >> s.log_s) > 2) s.log_s++;
-    if (const char* env = getenv("H2_MSM_SLICE_LOG")) {
-        int v = atoi(env);
-        if (v >= 1 && v <= 10) s.log_s = (uint32_t)v;
-    }
+    s.log_s = slice_log(s.entries, s.entries / s.nb);
     // sort: 2^8 bins per k_bucket_sort workgroup -- measured at 2^24 with 21-bit bucket ids: 2^8 bins 1.6 ms, 2^10 3.5 ms,
     // 2^12 5.1 ms (placing the bins in sweeps of 256 does not change that: profiles/r2_msm_experiments.txt), k_partition
     // over the remaining 2^13 / 2^11 / 2^9 partitions 3.0 / 2.5 / 2.0 ms -- so up to 2^13 partitions for k_partition
     s.lo_bits = (s.c - 1 < 8) ? (s.c - 1) : 8;
     while (s.c - 1 - s.lo_bits > 13 && s.lo_bits < 12) s.lo_bits++;
-    if (const char* env = getenv("H2_MSM_TABLE_LO")) {
-        int v = atoi(env);
-        if (v >= 4 && v <= 12 && (uint32_t)v <= s.c - 1 && s.c - 1 - (uint32_t)v <= 13) s.lo_bits = (uint32_t)v;
-    }
+    if (const uint32_t v = (uint32_t)env_int("H2_MSM_TABLE_LO", 4, 12, 0))
+        if (v <= s.c - 1 && s.c - 1 - v <= 13) s.lo_bits = v;
     s.hi_bits = s.c - 1 - s.lo_bits;
     // the dominant-scalar window only ever fills its bucket 0: it gets ONE partition (2^lo_bits buckets) behind window 0's
     s.np = (1u << s.hi_bits) + (hot ? 1u : 0u);
     s.nbt = s.nb + (hot ? (1u << s.lo_bits) : 0u);
-    s.max_items = (s.entries >> s.log_s) + s.nbt + 2;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o = align_up(o + bytes, 256);
-        return r;
-    };
-    s.off_keys = take(s.entries * 4);
-    s.off_sorted = take(s.entries * 4);
-    s.off_tmp = take(s.entries * 8);
-    s.off_pcount = take(((size_t)s.np + 2) * 4);
-    s.off_pbase = take(((size_t)s.np + 2) * 4);
-    s.off_pcursor = take(((size_t)s.np + 2) * 4);
-    s.off_starts = take(((size_t)s.nbt + 2) * 4);
-    s.off_heavy = take(((size_t)s.nbt + 2) * 4);
-    s.off_partials = take(s.max_items * sizeof(XYZZ));
-    s.off_buckets = take((size_t)s.nbt * sizeof(XYZZ));
     // Reduce by bit planes (below, k_reduce_chunks): for power-of-two chunk lengths and at least a workgroup of chunks
     static const bool planes_on = !(getenv("H2_MSM_REDUCE_PLANES") && atoi(getenv("H2_MSM_REDUCE_PLANES")) == 0);
     s.planes = 0;
@@ -324,18 +305,12 @@ static MsmShape msm_shape_table(size_t n, uint32_t max_bits, bool hot, const Shi
         while (s.plane_seg > 1 && (s.plane_seg - 1) * (REDUCE_T / 4) >= half) s.plane_seg--;   // no empty workgroups
         s.plane_l = (half + s.plane_seg * (REDUCE_T / 4) - 1) / (s.plane_seg * (REDUCE_T / 4));
     }
-    s.off_winpart = take(((size_t)s.Wt * (1 + s.RG) + s.planes) * sizeof(XYZZ));
-    s.off_rcount = take((size_t)s.Wt * 4);
-    s.off_planes = s.planes ? take(((size_t)s.chunks + (size_t)s.planes * s.plane_seg) * sizeof(XYZZ) + (size_t)s.planes * 4 + 64) : 0;
-    s.off_bflags = take(n / 256 + 4);  // one byte per 256-row block: the block is one entry of the dominant-value bucket
-    s.off_coltab = take(64);
-    // two-level partition (H2_MSM_TWO_LEVEL=0: the single pass): the entries pass through a second 8-byte-per-entry buffer
+    // two-level partition (H2_MSM_TWO_LEVEL=0: the single pass)
     static const bool two_level = !(getenv("H2_MSM_TWO_LEVEL") && atoi(getenv("H2_MSM_TWO_LEVEL")) == 0);
     static const uint32_t two_level_min_hi = getenv("H2_MSM_TWO_LEVEL_MIN_HI") ? (uint32_t)atoi(getenv("H2_MSM_TWO_LEVEL_MIN_HI")) : 8u;
     s.two_level = (two_level && s.hi_bits >= two_level_min_hi && s.hi_bits >= 2 && s.hi_bits <= 14) ? 1u : 0u;
     s.a_bits = s.hi_bits / 2;
-    s.off_tmpa = s.two_level ? take(s.entries * 8 + (PARTA_GROUPS_MAX * 3 + 4) * 4) : 0;
-    s.total = o;
+    msm_layout(s);
     return s;
 }
 
@@ -376,7 +351,6 @@ static bool table_lookup(const uint64_t* d_bases, size_t n, uint32_t max_bits, S
     return true;
 }
 
-int bases_forget(const uint64_t* d_bases);
 // drops the table whose bases contain d_bases (its bases no longer hold the points it was built from)
 static void table_drop_containing(const uint64_t* d_bases) {
     const uint64_t* key = nullptr;
@@ -400,9 +374,6 @@ size_t msm_scratch_bytes(size_t n, uint32_t max_bits) {
             need = std::max(need, std::max(msm_shape_table(n, max_bits, true, kv.second).total, msm_shape_table(n, max_bits, false, kv.second).total));
     return need;
 }
-// scratch that lets h2_dev_msm_batch(_ex) fuse `count` columns of bound `max_bits` over one base table
-size_t msm_batch_scratch_bytes(size_t n, uint32_t max_bits, size_t count);
-
 void msm_shape_query(size_t n, uint32_t max_bits, uint32_t* c, uint32_t* windows, uint32_t* buckets_per_window) {
     MsmShape s = msm_shape(n, max_bits, false);
     if (c) *c = s.c;
@@ -1307,208 +1278,6 @@ __global__ void __launch_bounds__(REDUCE_T) k_reduce_planes(const XYZZ* R, uint3
     if (qd == 0) xyzz_store_q(out + p, acc, q);
 }
 
-// ---------------------------------------------------------------- synthetic bases (bench / tests)
-// n deterministic G1 points by try-and-increment: x = mix(seed, i), y = (x^3 + 3)^((q+1)/4) when that
-// is a square root (q = 3 mod 4).  Cofactor 1: every curve point is in G1.  Not part of the prover
-// path; it exists so bench.py can build its workload without touching the CPU oracle.
-__device__ __forceinline__ uint64_t splitmix64(uint64_t& x) {
-    uint64_t z = (x += 0x9e3779b97f4a7c15ull);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-
-__global__ void __launch_bounds__(256) k_random_points(uint64_t seed, size_t n, Affine* out) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    // (q + 1) / 4, little-endian u32 limbs
-    const uint32_t E[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u,
-                           0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};
-    uint64_t st = seed ^ (0xd1342543de82ef95ull * (uint64_t)(i + 1));
-    Fq x;
-    for (int k = 0; k < 4; k++) {
-        uint64_t v = splitmix64(st);
-        x.l[2 * k] = (uint32_t)v;
-        x.l[2 * k + 1] = (uint32_t)(v >> 32);
-    }
-    x.l[7] &= 0x1fffffffu;  // < 2^253 < q: a valid Montgomery residue
-    Fq three = fp_add(fp_add(fp_one<FqParams>(), fp_one<FqParams>()), fp_one<FqParams>());
-    for (;;) {
-        Fq rhs = fp_add(fp_mul(fp_sqr(x), x), three);
-        Fq y = fp_one<FqParams>();
-        for (int bit = 253; bit >= 0; bit--) {
-            y = fp_sqr(y);
-            if ((E[bit >> 5] >> (bit & 31)) & 1) y = fp_mul(y, rhs);
-        }
-        if (fp_eq(fp_sqr(y), rhs)) {
-            if (splitmix64(st) & 1) y = fp_neg(y);
-            fp_store(&out[i].x, x);
-            fp_store(&out[i].y, y);
-            return;
-        }
-        x = fp_add(x, fp_one<FqParams>());
-    }
-}
-
-int random_points_launch(uint64_t seed, size_t n, uint64_t* d_out, hipStream_t stream) {
-    if (n == 0) return H2_OK;
-    hipLaunchKernelGGL(k_random_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, seed, n,
-                       (Affine*)d_out);
-    H2_HIP(hipGetLastError());
-    return H2_OK;
-}
-
-// ---------------------------------------------------------------- compressed points (Params::{read, write})
-// poly/commitment.rs:241-294 stores g and g_lagrange as `to_bytes()` = 32 bytes per point.  Convention (the layout of
-// pairing_bn256@30b052f cannot be checked without its sources -- "parity unpinned"): x little-endian, bit 7 of byte 31 =
-// parity of canonical y, identity = 32 zero bytes.  Decompression is one square root (y = rhs^((q+1)/4), q = 3 mod 4)
-// per point: the reference does it with a rayon `parallelize` over `from_bytes`, here it is one lane per point.
-__device__ __forceinline__ Fq fq_sqrt_candidate(const Fq& rhs) {
-    // (q + 1) / 4, little-endian u32 limbs
-    const uint32_t E[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u,
-                           0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};
-    Fq y = fp_one<FqParams>();
-    for (int bit = 253; bit >= 0; bit--) {
-        y = fp_sqr(y);
-        if ((E[bit >> 5] >> (bit & 31)) & 1) y = fp_mul(y, rhs);
-    }
-    return y;
-}
-
-__global__ void __launch_bounds__(256) k_points_decompress(const uint32_t* bytes, size_t n, Affine* out, uint32_t* bad) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fq x;
-    uint32_t any = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        x.l[k] = bytes[8 * i + k];
-        any |= x.l[k];
-    }
-    Fq zero = fp_zero<FqParams>();
-    if (any == 0) {  // identity
-        fp_store(&out[i].x, zero);
-        fp_store(&out[i].y, zero);
-        return;
-    }
-    const uint32_t sign = x.l[7] >> 31;
-    x.l[7] &= 0x7fffffffu;
-    // x must be a canonical residue (< q)
-    bool lt = false, decided = false;
-#pragma unroll
-    for (int k = 7; k >= 0; k--) {
-        if (!decided && x.l[k] != FqParams::MOD[k]) {
-            lt = x.l[k] < FqParams::MOD[k];
-            decided = true;
-        }
-    }
-    if (!lt) {
-        atomicAdd(bad, 1u);
-        fp_store(&out[i].x, zero);
-        fp_store(&out[i].y, zero);
-        return;
-    }
-    Fq xm = fp_to_mont(x);
-    Fq three = fp_add(fp_add(fp_one<FqParams>(), fp_one<FqParams>()), fp_one<FqParams>());
-    Fq rhs = fp_add(fp_mul(fp_sqr(xm), xm), three);
-    Fq y = fq_sqrt_candidate(rhs);
-    if (!fp_eq(fp_sqr(y), rhs)) {  // x is not the abscissa of a curve point
-        atomicAdd(bad, 1u);
-        fp_store(&out[i].x, zero);
-        fp_store(&out[i].y, zero);
-        return;
-    }
-    if ((fp_from_mont(y).l[0] & 1u) != sign) y = fp_neg(y);
-    fp_store(&out[i].x, xm);
-    fp_store(&out[i].y, y);
-}
-
-__global__ void __launch_bounds__(256) k_points_compress(const Affine* pts, size_t n, uint32_t* bytes) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Affine p = affine_load(pts + i);
-    Fq x = fp_from_mont(p.x), y = fp_from_mont(p.y);
-    if (fp_is_zero(x) && fp_is_zero(y)) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) bytes[8 * i + k] = 0;
-        return;
-    }
-    x.l[7] |= (y.l[0] & 1u) << 31;
-#pragma unroll
-    for (int k = 0; k < 8; k++) bytes[8 * i + k] = x.l[k];
-}
-
-int points_decompress_launch(const void* d_bytes, size_t n, uint64_t* d_out, uint32_t* d_bad, hipStream_t stream) {
-    if (n == 0) return H2_OK;
-    H2_HIP(hipMemsetAsync(d_bad, 0, 4, stream));
-    hipLaunchKernelGGL(k_points_decompress, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                       (const uint32_t*)d_bytes, n, (Affine*)d_out, d_bad);
-    H2_HIP(hipGetLastError());
-    uint32_t bad = 0;
-    H2_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, stream));
-    H2_HIP(hipStreamSynchronize(stream));
-    if (bad) {
-        set_last_error("points_decompress: " + std::to_string(bad) + " encoding(s) are not curve points");
-        return H2_ERR_INVALID;
-    }
-    return H2_OK;
-}
-
-int points_compress_launch(const uint64_t* d_points, size_t n, void* d_bytes, hipStream_t stream) {
-    if (n == 0) return H2_OK;
-    hipLaunchKernelGGL(k_points_compress, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                       (const Affine*)d_points, n, (uint32_t*)d_bytes);
-    H2_HIP(hipGetLastError());
-    return H2_OK;
-}
-
-// ---------------------------------------------------------------- fixed-base multiplication (Params::unsafe_setup)
-// out[i] = [scalars[i]] B for one base B given as the table T[j] = [2^j] B, j < 254 (affine): the setup's
-// g[i] = [s^i] G and g_lagrange[i] = [l_i(s)] G (poly/commitment.rs:67-112, a rayon `parallelize` with one variable-
-// base multiplication per point there).  One lane per point: ~127 mixed additions against the shared table (every
-// lane reads the same entry: a broadcast), then one Fq inversion (a^(q-2)) to normalise.
-__device__ __forceinline__ Fq fq_inv_device(const Fq& a) {
-    // q - 2, little-endian u32 limbs
-    const uint32_t E[8] = {0xd87cfd45u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u,
-                           0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
-    Fq acc = fp_one<FqParams>();
-#pragma unroll 1
-    for (int bit = 253; bit >= 0; bit--) {
-        acc = fp_sqr(acc);
-        if ((E[bit >> 5] >> (bit & 31)) & 1) acc = fp_mul(acc, a);
-    }
-    return acc;
-}
-
-__global__ void __launch_bounds__(256) k_fixed_base_mul(const Fr* scalars, const Affine* table, size_t n, Affine* out) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Fr s = fp_from_mont(fp_load(scalars + i));
-    XYZZ acc = xyzz_identity();
-#pragma unroll 1
-    for (int bit = 0; bit < 254; bit++)
-        if ((s.l[bit >> 5] >> (bit & 31)) & 1) acc = xyzz_madd(acc, affine_load(table + bit), false);
-    Fq zero = fp_zero<FqParams>();
-    if (fp_is_zero(acc.zz)) {  // scalar 0: the identity
-        fp_store(&out[i].x, zero);
-        fp_store(&out[i].y, zero);
-        return;
-    }
-    // x = X / ZZ, y = Y / ZZZ with one inversion: t = 1 / ZZZ, 1 / ZZ = (ZZ * t)^2  (ZZ^3 = ZZZ^2)
-    const Fq t = fq_inv_device(acc.zzz);
-    const Fq u = fp_mul(acc.zz, t);
-    fp_store(&out[i].x, fp_mul(acc.x, fp_sqr(u)));
-    fp_store(&out[i].y, fp_mul(acc.y, t));
-}
-
-int fixed_base_mul_launch(const Fr* d_scalars, const uint64_t* d_table, size_t n, uint64_t* d_out, hipStream_t stream) {
-    if (n == 0) return H2_OK;
-    hipLaunchKernelGGL(k_fixed_base_mul, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_scalars,
-                       (const Affine*)d_table, n, (Affine*)d_out);
-    H2_HIP(hipGetLastError());
-    return H2_OK;
-}
-
 // ---------------------------------------------------------------- shifted-base table build (h2_dev_bases_precompute)
 // One lane per base point: level j = [2^(width of digit j - 1)] level j - 1 by Jacobian doublings (a = 0, 2M + 5S
 // [dbl-2009-l]; BN254 G1 has prime order, so a doubling never meets the identity), X and Y parked in the table slot and
@@ -1779,6 +1548,23 @@ struct FusedCols {
     uint64_t hot_mask;
 };
 
+// raises the dynamic LDS limit of some kernels, once per device (one object per call site)
+struct LdsLimit {
+    bool raised[64] = {};
+    void raise(std::initializer_list<const void*> kernels, int bytes) {
+        int dev = 0;
+        H2_HIP(hipGetDevice(&dev));
+        if (dev >= 0 && dev < 64 && raised[dev]) return;
+        for (const void* k : kernels) H2_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        if (dev >= 0 && dev < 64) raised[dev] = true;
+    }
+};
+// name the k_partition<TILE> / k_acc_slice<WAVES> that msm_launch starts
+template <uint32_t TILE>
+using tile = std::integral_constant<uint32_t, TILE>;
+template <int WAVES>
+using waves = std::integral_constant<int, WAVES>;
+
 static void msm_launch(const MsmShape& s, const Hot& hot, const Fr* d_scalars, const Affine* d_bases, uint32_t max_bits,
                        char* scratch, hipStream_t stream, const FusedCols* fused = nullptr) {
     uint32_t* keys = (uint32_t*)(scratch + s.off_keys);
@@ -1802,51 +1588,41 @@ static void msm_launch(const MsmShape& s, const Hot& hot, const Fr* d_scalars, c
     }
     unsigned nblk = (unsigned)((s.n + 255) / 256);
     unsigned dblk = nblk < 1024 ? nblk : 1024;  // grid-stride: one LDS histogram flush per workgroup
-    if (fused) {
-        const uint32_t np_col = s.Wc << s.hi_bits;
-        hipLaunchKernelGGL(k_digits, dim3(dblk, s.cols), dim3(256), (size_t)np_col * 4, stream, (const Fr*)nullptr, s.n, s.c,
-                           s.W, s.nb, max_bits > 254 ? 254u : max_bits, s.lo_bits, s.hi_bits, np_col, keys, pcount, 0,
-                           hot.value, fused->scalars, fused->hot_values, fused->hot_mask, 31u, 1u, s.wfull, 0u, (size_t)0,
-                           (uint8_t*)nullptr);
-    } else {
-        hipLaunchKernelGGL(k_digits, dim3(dblk), dim3(256), (size_t)s.np * 4, stream, d_scalars, s.n, s.c, s.W, s.nb,
-                           max_bits > 254 ? 254u : max_bits, s.lo_bits, s.hi_bits, s.np, keys, pcount, hot.on ? 1 : 0,
-                           hot.value, (const Fr* const*)nullptr, (const Fr*)nullptr, (uint64_t)0, s.range_shift, s.R,
-                           s.wfull, s.tab, bflags ? s.n / BLOCK_ROWS * BLOCK_ROWS : (size_t)0, bflags);
-    }
+    // a fused shape (no row ranges, no table, `hot` off, d_scalars null): one grid row and one LDS histogram per column
+    const FusedCols cols = fused ? *fused : FusedCols{};
+    const uint32_t np_col = fused ? s.Wc << s.hi_bits : s.np;
+    hipLaunchKernelGGL(k_digits, dim3(dblk, fused ? s.cols : 1u), dim3(256), (size_t)np_col * 4, stream, d_scalars, s.n, s.c,
+                       s.W, s.nb, max_bits > 254 ? 254u : max_bits, s.lo_bits, s.hi_bits, np_col, keys, pcount, hot.on ? 1 : 0,
+                       hot.value, cols.scalars, cols.hot_values, cols.hot_mask, s.range_shift, s.R, s.wfull, s.tab,
+                       bflags ? s.n / BLOCK_ROWS * BLOCK_ROWS : (size_t)0, bflags);
     hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(256), 0, stream, pcount, s.np, pbase, pcursor, starts, s.nbt);
+    // k_partition<TILE> over the key arrays w_first .. w_first + arrays - 1
+    auto partition = [&](auto tile_tag, uint32_t w_first, uint32_t arrays) {
+        constexpr uint32_t TILE = decltype(tile_tag)::value;
+        hipLaunchKernelGGL(k_partition<TILE>, dim3((unsigned)((s.n + TILE - 1) / TILE), arrays), dim3(256),
+                           ((size_t)4 << s.hi_bits) + 4 * (TILE / 256), stream, keys, s.n, s.lo_bits, s.hi_bits, pcursor, tmp,
+                           s.range_shift, s.W, s.R, (uint32_t)s.tab_stride, (const uint8_t*)bflags, w_first);
+    };
     if (s.tab && s.two_level) {
         uint2* tmpa = (uint2*)(scratch + s.off_tmpa);
         uint32_t* cursor_a = (uint32_t*)(scratch + s.off_tmpa + s.entries * 8);
         uint32_t* tile_start = cursor_a + PARTA_GROUPS_MAX;
         const uint32_t a_bits = s.a_bits, b_bits = s.hi_bits - s.a_bits;
-        static bool lds_raised[64] = {};   // per device: 64 KiB of staging + the static tables exceed the default dynamic limit
-        int dev = 0;
-        H2_HIP(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 64 || !lds_raised[dev]) {
-            H2_HIP(hipFuncSetAttribute((const void*)k_part_a, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-            H2_HIP(hipFuncSetAttribute((const void*)k_part_b, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-            if (dev >= 0 && dev < 64) lds_raised[dev] = true;
-        }
+        // 64 KiB of staging + the static tables exceed the default dynamic limit
+        static LdsLimit raised;
+        raised.raise({(const void*)k_part_a, (const void*)k_part_b}, 80 * 1024);
         hipLaunchKernelGGL(k_part_init, dim3(1), dim3(PARTA_GROUPS_MAX), 0, stream, pbase, a_bits, b_bits, cursor_a, tile_start);
         hipLaunchKernelGGL(k_part_a, dim3((unsigned)((s.n + PART_AB_T - 1) / PART_AB_T), s.W), dim3(256), (size_t)PART_AB_T * 8,
                            stream, keys, s.n, s.lo_bits, b_bits, a_bits, cursor_a, tmpa, (uint32_t)s.tab_stride,
                            (const uint8_t*)bflags);
-        if (s.Wk > s.W)  // the dominant-scalar array: one partition behind the 2^hi_bits of window 0, appended as before
-            hipLaunchKernelGGL(k_partition<PART_T_TABLE>, dim3((unsigned)((s.n + PART_T_TABLE - 1) / PART_T_TABLE), s.Wk - s.W),
-                               dim3(256), ((size_t)4 << s.hi_bits) + 4 * (PART_T_TABLE / 256), stream, keys, s.n, s.lo_bits,
-                               s.hi_bits, pcursor, tmp, s.range_shift, s.W, s.R, (uint32_t)s.tab_stride, (const uint8_t*)bflags,
-                               s.W);
+        // the dominant-scalar array: one partition behind the 2^hi_bits of window 0, appended as before
+        if (s.Wk > s.W) partition(tile<PART_T_TABLE>(), s.W, s.Wk - s.W);
         hipLaunchKernelGGL(k_part_b, dim3((unsigned)(s.entries / PART_AB_T + (1u << a_bits) + 1)), dim3(256), (size_t)PART_AB_T * 8,
                            stream, (const uint2*)tmpa, pbase, s.lo_bits, b_bits, a_bits, tile_start, pcursor, tmp);
     } else if (s.tab && s.hi_bits > 10)
-        hipLaunchKernelGGL(k_partition<PART_T_TABLE>, dim3((unsigned)((s.n + PART_T_TABLE - 1) / PART_T_TABLE), s.Wk), dim3(256),
-                           ((size_t)4 << s.hi_bits) + 4 * (PART_T_TABLE / 256), stream, keys, s.n, s.lo_bits, s.hi_bits, pcursor, tmp, s.range_shift, s.W,
-                           s.R, (uint32_t)s.tab_stride, (const uint8_t*)bflags, 0u);
+        partition(tile<PART_T_TABLE>(), 0u, s.Wk);
     else
-        hipLaunchKernelGGL(k_partition<PART_T>, dim3((unsigned)((s.n + PART_T - 1) / PART_T), s.Wk), dim3(256),
-                           ((size_t)4 << s.hi_bits) + 4 * (PART_T / 256), stream, keys, s.n, s.lo_bits, s.hi_bits, pcursor, tmp, s.range_shift, s.W,
-                           s.R, (uint32_t)s.tab_stride, (const uint8_t*)bflags, 0u);
+        partition(tile<PART_T>(), 0u, s.Wk);
     // a partition holding more than 4x its fair share (and at least a few thousand entries) takes the skew path
     uint32_t skew_threshold = (uint32_t)std::max<size_t>(4 * (s.entries / s.np), 4096);
     const uint32_t hot_partition = (!fused && hot.on) ? ((s.tab ? 1u : s.R * s.W) << s.hi_bits) : 0xffffffffu;
@@ -1856,13 +1632,8 @@ static void msm_launch(const MsmShape& s, const Hot& hot, const Fr* d_scalars, c
     const size_t avg_part = s.entries / s.np;
     const uint32_t stage_cap = (sort_stage && s.tab && avg_part >= 8192 && avg_part + avg_part / 10 <= 32768) ? 32768u : 0u;
     if (stage_cap) {
-        static bool raised[64] = {};
-        int dev = 0;
-        H2_HIP(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 64 || !raised[dev]) {
-            H2_HIP(hipFuncSetAttribute((const void*)k_bucket_sort, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-            if (dev >= 0 && dev < 64) raised[dev] = true;
-        }
+        static LdsLimit raised;
+        raised.raise({(const void*)k_bucket_sort}, 160 * 1024 - 256);
     }
     hipLaunchKernelGGL(k_bucket_sort, dim3(s.np), dim3(SORT_T), ((size_t)4 << s.lo_bits) + (size_t)stage_cap * 4, stream, tmp, pbase,
                        s.lo_bits, s.hi_bits, s.nb, skew_threshold, hot_partition, fused ? s.Wc : 0u,
@@ -1876,12 +1647,14 @@ static void msm_launch(const MsmShape& s, const Hot& hot, const Fr* d_scalars, c
     unsigned nslices = (unsigned)(((s.entries + (1u << s.log_s) - 1) >> s.log_s));
     // waves per SIMD the accumulation is compiled for: 4 (110 VGPRs, no spills) or 5 (96 VGPRs, 14 spilled): H2_MSM_ACC_WAVES
     static const int acc_waves = getenv("H2_MSM_ACC_WAVES") ? atoi(getenv("H2_MSM_ACC_WAVES")) : 4;
+    auto accumulate = [&](auto waves_tag) {
+        hipLaunchKernelGGL(k_acc_slice<decltype(waves_tag)::value>, dim3((nslices + 255) / 256), dim3(256), 0, stream, d_bases,
+                           (!fused && hot.on) ? hot.block_sums : (const Affine*)nullptr, sorted, starts, s.nbt, s.log_s, partials);
+    };
     if (acc_waves == 5)
-        hipLaunchKernelGGL(k_acc_slice<5>, dim3((nslices + 255) / 256), dim3(256), 0, stream, d_bases,
-                           (!fused && hot.on) ? hot.block_sums : (const Affine*)nullptr, sorted, starts, s.nbt, s.log_s, partials);
+        accumulate(waves<5>());
     else
-        hipLaunchKernelGGL(k_acc_slice<4>, dim3((nslices + 255) / 256), dim3(256), 0, stream, d_bases,
-                           (!fused && hot.on) ? hot.block_sums : (const Affine*)nullptr, sorted, starts, s.nbt, s.log_s, partials);
+        accumulate(waves<4>());
     // one lane per bucket from 2^19 buckets on (round 3, same box: 2^22 windowed 6.75 -> 6.61 ms, over a table 5.91 -> 5.76-5.90,
     // 2^24 windowed 23.9 -> 23.7; at 2^17 the forms tie, at 2^16 buckets the quads win by 4-7 %)
     static const uint32_t lane_from = getenv("H2_MSM_FINISH_LANE_LOG") ? 1u << atoi(getenv("H2_MSM_FINISH_LANE_LOG")) : 1u << 19;
@@ -1907,20 +1680,13 @@ static void msm_launch(const MsmShape& s, const Hot& hot, const Fr* d_scalars, c
         hipLaunchKernelGGL(k_reduce_chunks, dim3(groups), dim3(REDUCE_T), 0, stream, buckets, s.nb, s.qm, s.chunks, R, group_acc);
         hipLaunchKernelGGL(k_reduce_planes, dim3(s.plane_seg, s.planes), dim3(REDUCE_T), 0, stream, (const XYZZ*)R, s.chunks,
                            s.planes - 1, (const XYZZ*)group_acc, groups, s.plane_l, part, counters, winpart + s.Wt);
-        if (s.Wt > 1)
-            hipLaunchKernelGGL(k_reduce, dim3(1, 1), dim3(REDUCE_T), 0, stream, buckets + s.nb, 1u, 1u, s.qm,
-                               winpart + s.Wt, winpart + 1, (uint32_t*)(scratch + s.off_rcount));
-    } else if (s.tab) {
-        // one window of nb buckets; the dominant-scalar window only ever fills its bucket 0
-        hipLaunchKernelGGL(k_reduce, dim3(s.RG, 1), dim3(REDUCE_T), 0, stream, buckets, s.nb, s.RG, s.qm, winpart + s.Wt,
-                           winpart, (uint32_t*)(scratch + s.off_rcount));
-        if (s.Wt > 1)
-            hipLaunchKernelGGL(k_reduce, dim3(1, 1), dim3(REDUCE_T), 0, stream, buckets + s.nb, 1u, 1u, s.qm,
-                               winpart + s.Wt, winpart + 1, (uint32_t*)(scratch + s.off_rcount));
-    } else {
-        hipLaunchKernelGGL(k_reduce, dim3(s.RG, s.Wt), dim3(REDUCE_T), 0, stream, buckets, s.nb, s.RG, s.qm, winpart + s.Wt,
-                           winpart, (uint32_t*)(scratch + s.off_rcount));
+    } else {  // (over a table: one window of nb buckets)
+        hipLaunchKernelGGL(k_reduce, dim3(s.RG, s.tab ? 1u : s.Wt), dim3(REDUCE_T), 0, stream, buckets, s.nb, s.RG, s.qm,
+                           winpart + s.Wt, winpart, (uint32_t*)(scratch + s.off_rcount));
     }
+    if (s.tab && s.Wt > 1)  // the dominant-scalar window only ever fills its bucket 0
+        hipLaunchKernelGGL(k_reduce, dim3(1, 1), dim3(REDUCE_T), 0, stream, buckets + s.nb, 1u, 1u, s.qm, winpart + s.Wt,
+                           winpart + 1, (uint32_t*)(scratch + s.off_rcount));
     H2_HIP(hipGetLastError());
 }
 
@@ -1948,8 +1714,7 @@ static void msm_host_tail(const MsmShape& s, const Hot& hot, const std::vector<X
         acc = xyzz_add(acc, ws);
     }
     if (hot.on) {  // + v * E, E = the extra window's sum (bucket 0 carries weight 1)
-        XYZZ e = xyzz_identity();
-        e = winpart[w0 + (s.tab ? 1u : (size_t)s.R * s.W)];
+        const XYZZ e = winpart[w0 + (s.tab ? 1u : (size_t)s.R * s.W)];
         const Fr v = fp_from_mont(hot.value);
         XYZZ r = xyzz_identity();
         for (int bit = 253; bit >= 0; bit--) {
@@ -1962,6 +1727,69 @@ static void msm_host_tail(const MsmShape& s, const Hot& hot, const std::vector<X
     memcpy(out_xyz, &j, 96);
 }
 
+// points that leave the device per MSM
+static size_t exported_points(const MsmShape& s) { return (size_t)s.Wt * s.G + s.planes; }
+
+// ---------------------------------------------------------------- the plan of one column
+// What is decided for ONE MSM of n rows -- msm_device's only column, each column of msm_device_batch_ex -- in three steps
+// around the stream synchronisation both drivers have anyway: plan_find_table (host only), plan_probe (enqueues the
+// sampling), [synchronise], plan_decide (host only; leaves `hot`, `use_tab` and `shape` ready for msm_launch).
+struct ColumnPlan {
+    const Fr* scalars = nullptr;
+    const uint64_t* bases = nullptr;
+    uint32_t bits = 0;             // the column's scalar bound
+    bool fused = false;            // batch: already committed in a fused group
+    ShiftTable tab{}, found{};     // the table worth using for this bound; the table that contains the bases at all
+    bool use_tab = false;          // commit in table form
+    bool have_tab = false;         // a table of these bases exists (its block sums serve the windowed form too)
+    Hot hot;
+    MsmShape shape{};
+
+    bool active() const { return bits != 0 && !fused; }   // bound 0: the identity (arithmetic.rs:346)
+    const Affine* points() const { return use_tab ? tab.table : (const Affine*)bases; }
+};
+
+// the batch's "column i is on the host" event: one still alive when the driver leaves (an H2_HIP that threw) goes with it
+struct EventDestroy {
+    void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+};
+using ColumnEvent = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
+
+static void plan_find_table(ColumnPlan& p, size_t n) {
+    if (!p.bits || !p.bases) return;
+    p.use_tab = table_lookup(p.bases, n, p.bits, &p.tab);
+    p.have_tab = p.use_tab;
+    if (p.use_tab)
+        p.found = p.tab;
+    else
+        p.have_tab = table_find(p.bases, n, &p.found);
+}
+
+// 64 sampled scalars decide whether a dominant value gets its own window; next to them the table's copy of the bases is
+// compared with the bases (k_table_check).  h_samples (HOT_SAMPLES values) and h_stale: mapped pinned memory of the caller
+static void plan_probe(const ColumnPlan& p, size_t n, Fr* h_samples, uint32_t* h_stale, hipStream_t stream) {
+    *h_stale = 0;
+    hipLaunchKernelGGL(k_sample, dim3(1), dim3(HOT_SAMPLES), 0, stream, p.scalars, n, h_samples);
+    if (p.have_tab && !p.fused)
+        hipLaunchKernelGGL(k_table_check, dim3(1), dim3(HOT_SAMPLES), 0, stream, (const Affine*)p.bases, p.found.table, n, h_stale);
+}
+
+// after the synchronisation that brought the samples and the flag in
+static void plan_decide(ColumnPlan& p, size_t n, const Fr* h_samples, const uint32_t* h_stale) {
+    if (p.have_tab && *h_stale) {  // the bases changed under their table (see k_table_check): windowed form, table dropped
+        table_drop_containing(p.bases);
+        p.use_tab = p.have_tab = false;
+    }
+    p.hot = detect_hot(h_samples);
+    // the extra window trades W additions per dominant row for one: with one or two windows there is nothing to gain,
+    // only a giant bucket to fold and a 254-bit multiplication on the host
+    if (p.hot.on && msm_shape(n, p.bits, false).W <= 2) p.hot.on = false;
+    p.use_tab = p.use_tab && table_pays(p.tab, n, p.bits, p.hot);
+    if (p.hot.on && p.have_tab && p.found.blocks && (p.use_tab ? (size_t)p.tab.D * p.tab.n : n) < BLOCK_INDEX0)
+        p.hot.block_sums = p.found.blocks;
+    p.shape = p.use_tab ? msm_shape_table(n, p.bits, p.hot.on, p.tab) : msm_shape(n, p.bits, p.hot.on);
+}
+
 int msm_device(DeviceCtx* ctx, const Fr* d_scalars, const uint64_t* d_bases, size_t n, uint32_t max_bits,
                void* d_scratch, size_t scratch_bytes, uint64_t* out_xyz, hipStream_t stream) {
     if (n == 0 || max_bits == 0) {
@@ -1972,48 +1800,30 @@ int msm_device(DeviceCtx* ctx, const Fr* d_scalars, const uint64_t* d_bases, siz
         set_last_error("h2 msm: n * windows must be < 2^32 (sorted entries are indexed with 32 bits): split the MSM");
         return H2_ERR_INVALID;
     }
-    ShiftTable tab{}, found{};
-    bool use_tab = table_lookup(d_bases, n, max_bits, &tab);
-    bool have_tab = use_tab;  // a table of these bases exists (its block sums serve the windowed form too)
-    if (use_tab)
-        found = tab;
-    else
-        have_tab = table_find(d_bases, n, &found);
+    ColumnPlan p{d_scalars, d_bases, max_bits};
+    plan_find_table(p, n);
     if (!d_scratch || scratch_bytes < msm_scratch_bytes(n, max_bits)) {
         set_last_error("h2 msm: scratch too small (see h2_msm_scratch_bytes)");
         return H2_ERR_INVALID;
     }
     static thread_local PinnedBuf staging;  // per calling thread: this entry point takes no context lock
-    // 64 sampled scalars decide whether a dominant value gets its own window
     Fr* h_samples = (Fr*)staging.get((HOT_SAMPLES + 1) * sizeof(Fr));
     uint32_t* h_stale = (uint32_t*)(h_samples + HOT_SAMPLES);
-    *h_stale = 0;
-    hipLaunchKernelGGL(k_sample, dim3(1), dim3(HOT_SAMPLES), 0, stream, d_scalars, n, (Fr*)h_samples);
-    if (have_tab)
-        hipLaunchKernelGGL(k_table_check, dim3(1), dim3(HOT_SAMPLES), 0, stream, (const Affine*)d_bases, found.table, n, h_stale);
+    plan_probe(p, n, h_samples, h_stale, stream);
     H2_HIP(hipStreamSynchronize(stream));
-    if (have_tab && *h_stale) {
-        table_drop_containing(d_bases);
-        use_tab = have_tab = false;
-    }
-    Hot hot = detect_hot(h_samples);
-    // the extra window trades W additions per dominant row for one: with one or two windows there is nothing to gain,
-    // only a giant bucket to fold and a 254-bit multiplication on the host
-    if (hot.on && msm_shape(n, max_bits, false).W <= 2) hot.on = false;
-    use_tab = use_tab && table_pays(tab, n, max_bits, hot);
-    if (hot.on && have_tab && found.blocks && (use_tab ? (size_t)tab.D * tab.n : n) < BLOCK_INDEX0) hot.block_sums = found.blocks;
-    MsmShape s = use_tab ? msm_shape_table(n, max_bits, hot.on, tab) : msm_shape(n, max_bits, hot.on);
+    plan_decide(p, n, h_samples, h_stale);
+    const MsmShape& s = p.shape;
     if (s.total > scratch_bytes) {   // (cannot happen while h2_msm_scratch_bytes covers every shape; never run past the buffer)
         set_last_error("h2 msm: internal: the chosen shape needs more scratch than h2_msm_scratch_bytes reported");
         return H2_ERR_INVALID;
     }
-    msm_launch(s, hot, d_scalars, use_tab ? tab.table : (const Affine*)d_bases, max_bits, (char*)d_scratch, stream);
-    const size_t wp = (size_t)s.Wt * s.G + s.planes;
+    msm_launch(s, p.hot, d_scalars, p.points(), max_bits, (char*)d_scratch, stream);
+    const size_t wp = exported_points(p.shape);
     XYZZ* h_win = (XYZZ*)staging.get(wp * sizeof(XYZZ));
     export_to_host((const XYZZ*)((char*)d_scratch + s.off_winpart), h_win, wp, stream);
     H2_HIP(hipStreamSynchronize(stream));
     std::vector<XYZZ> winpart(h_win, h_win + wp);
-    msm_host_tail(s, hot, winpart, out_xyz);
+    msm_host_tail(s, p.hot, winpart, out_xyz);
     return H2_OK;
 }
 
@@ -2025,7 +1835,7 @@ int msm_device(DeviceCtx* ctx, const Fr* d_scalars, const uint64_t* d_bases, siz
 static int msm_device_fused(DeviceCtx* ctx, const Fr* const* d_scalars, uint32_t cols, const uint64_t* d_bases, size_t n,
                             uint32_t bits, char* scratch, uint64_t* const* outs, hipStream_t stream) {
     const MsmShape s = msm_shape(n, bits, false, cols);
-    const size_t wp = (size_t)s.Wt * s.G + s.planes;
+    const size_t wp = exported_points(s);
     // the column table (cols pointers, padded to 16 bytes, then cols dominant values) is staged in pinned memory too
     const size_t tab_ptr_bytes = ((size_t)cols * 8 + 15) & ~(size_t)15, tab_bytes = tab_ptr_bytes + (size_t)cols * sizeof(Fr);
     char* pinned = (char*)ctx->pinned.get((size_t)cols * HOT_SAMPLES * sizeof(Fr) + wp * sizeof(XYZZ) + tab_bytes);
@@ -2069,11 +1879,7 @@ static uint32_t fused_group_limit(size_t n, uint32_t bits) {
     // two-stream pipeline, which hides every column's host tail under the next column's kernels, is the better shape.
     // Columns with a short scalar bound have one or two windows: the slot every fused column keeps for its
     // dominant-scalar window would double their finish / reduce work -- they stay in the pipeline too.
-    uint32_t fuse_log = 22;
-    if (const char* env = getenv("H2_MSM_FUSE_LOG")) {
-        int v = atoi(env);
-        if (v >= 10 && v <= 28) fuse_log = (uint32_t)v;
-    }
+    const uint32_t fuse_log = (uint32_t)env_int("H2_MSM_FUSE_LOG", 10, 28, 22);
     // Short bounds (a few windows): fused only when a column still spreads over >= 16 sort partitions; a column of a few
     // hundred buckets is one partition and nothing but heavy buckets -- the row ranges of the single-column shape are
     // what it needs
@@ -2111,8 +1917,13 @@ int msm_device_batch_ex(DeviceCtx* ctx, const Fr* const* d_scalars, const uint64
                         const uint32_t* bits_each, size_t count, const uint64_t* d_bases, size_t n, uint32_t max_bits,
                         void* d_scratch, size_t scratch_bytes, uint64_t* out_xyz, hipStream_t stream) {
     if (count == 0) return H2_OK;
+    std::vector<ColumnPlan> plans(count);
     uint32_t top_bits = 0;
-    for (size_t i = 0; i < count; i++) top_bits = std::max(top_bits, bits_each ? bits_each[i] : max_bits);
+    for (size_t i = 0; i < count; i++) {
+        const uint64_t* bases = bases_each && bases_each[i] ? bases_each[i] : d_bases;
+        plans[i] = ColumnPlan{d_scalars[i], bases, bits_each ? bits_each[i] : max_bits};
+        top_bits = std::max(top_bits, plans[i].bits);
+    }
     if (n > 0x7fffffffu || (top_bits && msm_shape(n, top_bits, true).entries >= ((size_t)1 << 32))) {
         set_last_error("h2 msm: n * windows must be < 2^32 (sorted entries are indexed with 32 bits): split the MSM");
         return H2_ERR_INVALID;
@@ -2123,67 +1934,48 @@ int msm_device_batch_ex(DeviceCtx* ctx, const Fr* const* d_scalars, const uint64
     }
     // columns that share their base table and their bound are committed as fused groups when the caller's scratch
     // allows it (h2_msm_batch_scratch_bytes); the rest goes through the two-stream pipeline below
-    std::vector<char> done_fused(count, 0);
     // columns whose bases have a shifted-base table go through the pipeline in table form
-    std::vector<ShiftTable> tabs(count), founds(count);
-    std::vector<char> use_tab(count, 0), have_tab(count, 0);
-    for (size_t i = 0; i < count; i++) {
-        const uint32_t bits = bits_each ? bits_each[i] : max_bits;
-        const uint64_t* bases = bases_each && bases_each[i] ? bases_each[i] : d_bases;
-        if (!bits || !bases) continue;
-        use_tab[i] = table_lookup(bases, n, bits, &tabs[i]) ? 1 : 0;
-        if (use_tab[i]) {
-            founds[i] = tabs[i];
-            have_tab[i] = 1;
-        } else {
-            have_tab[i] = table_find(bases, n, &founds[i]) ? 1 : 0;  // its block sums serve the windowed form too
-        }
-    }
+    for (ColumnPlan& p : plans) plan_find_table(p, n);
     if (getenv("H2_MSM_NO_FUSE") == nullptr) {
         H2_HIP(hipStreamSynchronize(stream));
         for (size_t i = 0; i < count; i++) {
-            if (done_fused[i] || use_tab[i]) continue;
-            const uint32_t bits = bits_each ? bits_each[i] : max_bits;
-            if (bits == 0) continue;
-            const uint64_t* bases = bases_each && bases_each[i] ? bases_each[i] : d_bases;
+            const ColumnPlan& first = plans[i];
+            if (first.fused || first.use_tab || first.bits == 0) continue;
             std::vector<size_t> members{i};
-            for (size_t j = i + 1; j < count; j++) {
-                const uint32_t bj = bits_each ? bits_each[j] : max_bits;
-                const uint64_t* basej = bases_each && bases_each[j] ? bases_each[j] : d_bases;
-                if (!done_fused[j] && !use_tab[j] && bj == bits && basej == bases) members.push_back(j);
-            }
-            const uint32_t limit = fused_group_limit(n, bits);
+            for (size_t j = i + 1; j < count; j++)
+                if (!plans[j].fused && !plans[j].use_tab && plans[j].bits == first.bits && plans[j].bases == first.bases)
+                    members.push_back(j);
+            const uint32_t limit = fused_group_limit(n, first.bits);
             for (size_t m0 = 0; m0 < members.size(); m0 += limit) {
                 const uint32_t g = (uint32_t)std::min<size_t>(limit, members.size() - m0);
                 if (g < 2) break;
-                if (msm_shape(n, bits, false, g).total > scratch_bytes) break;  // caller sized the scratch for the pipeline only
+                if (msm_shape(n, first.bits, false, g).total > scratch_bytes) break;  // caller sized the scratch for the pipeline only
                 std::vector<const Fr*> sc(g);
                 std::vector<uint64_t*> outs(g);
                 for (uint32_t t = 0; t < g; t++) {
                     sc[t] = d_scalars[members[m0 + t]];
                     outs[t] = out_xyz + 12 * members[m0 + t];
-                    done_fused[members[m0 + t]] = 1;
+                    plans[members[m0 + t]].fused = true;
                 }
-                int rc = msm_device_fused(ctx, sc.data(), g, bases, n, bits, (char*)d_scratch, outs.data(), stream);
+                int rc = msm_device_fused(ctx, sc.data(), g, first.bases, n, first.bits, (char*)d_scratch, outs.data(), stream);
                 if (rc != H2_OK) return rc;
             }
         }
     }
+    // a lane's scratch and a column's read-back are sized before the samples are in: for the windowed and (where a table
+    // may be used) the table form, without and with a dominant scalar
+    // (plan_decide computes the one shape it chooses again: which one that is depends on the samples)
     size_t per = 0, wp_max = 0;
-    std::vector<MsmShape> shapes(2 * count), tshapes(2 * count);  // windowed / table form, without / with a dominant scalar
-    for (size_t i = 0; i < count; i++) {
-        const uint32_t bits = bits_each ? bits_each[i] : max_bits;
-        if (done_fused[i]) continue;
-        shapes[2 * i] = msm_shape(n, bits ? bits : 1, false);
-        shapes[2 * i + 1] = msm_shape(n, bits ? bits : 1, true);
-        per = std::max(per, align_up(std::max(shapes[2 * i].total, shapes[2 * i + 1].total), 256));
-        wp_max = std::max(wp_max, (size_t)shapes[2 * i + 1].Wt * shapes[2 * i + 1].G + shapes[2 * i + 1].planes);
-        if (use_tab[i]) {
-            tshapes[2 * i] = msm_shape_table(n, bits, false, tabs[i]);
-            tshapes[2 * i + 1] = msm_shape_table(n, bits, true, tabs[i]);
-            per = std::max(per, align_up(std::max(tshapes[2 * i].total, tshapes[2 * i + 1].total), 256));
-            // (the table form exports its window sum as bit planes: up to 24 points where the windowed form has its W + 1)
-            wp_max = std::max(wp_max, (size_t)tshapes[2 * i + 1].Wt * tshapes[2 * i + 1].G + tshapes[2 * i + 1].planes);
+    auto cover = [&](const MsmShape& s, bool hot) {
+        per = std::max(per, align_up(s.total, 256));
+        // (the table form exports its window sum as bit planes: up to 24 points where the windowed form has its W + 1)
+        if (hot) wp_max = std::max(wp_max, exported_points(s));
+    };
+    for (const ColumnPlan& p : plans) {
+        if (p.fused) continue;
+        for (bool hot : {false, true}) {
+            cover(msm_shape(n, p.bits ? p.bits : 1, hot), hot);
+            if (p.use_tab) cover(msm_shape_table(n, p.bits, hot, p.tab), hot);
         }
     }
     if (!d_scratch || scratch_bytes < 2 * per) {
@@ -2195,315 +1987,52 @@ int msm_device_batch_ex(DeviceCtx* ctx, const Fr* const* d_scalars, const uint64
     Fr* h_samples = (Fr*)pinned;
     XYZZ* h_win = (XYZZ*)(pinned + count * HOT_SAMPLES * sizeof(Fr));
     uint32_t* h_stale = (uint32_t*)(pinned + count * (HOT_SAMPLES * sizeof(Fr) + wp_max * sizeof(XYZZ)));  // per column
-    for (size_t i = 0; i < count; i++) h_stale[i] = 0;
     // pipeline lanes: one stream + one scratch slice each.  Two: a third and fourth lane (H2_MSM_LANES, when the scratch
     // holds them) were measured and do not pay -- 2^18: 0.78 (2) / 0.76 (3) / 0.84 (4) ms per MSM, 2^20: 2.06 / 2.08 / 2.17
     hipStream_t st[4] = {ctx->stream, ctx->copy_stream, ctx->aux_stream[0], ctx->aux_stream[1]};
-    size_t lanes = 2;
-    if (const char* env = getenv("H2_MSM_LANES")) {
-        int v = atoi(env);
-        if (v >= 2 && v <= 4 && per && (size_t)v * per <= scratch_bytes) lanes = (size_t)v;
-    }
-    for (size_t i = 0; i < count; i++) {
-        hipLaunchKernelGGL(k_sample, dim3(1), dim3(HOT_SAMPLES), 0, stream, d_scalars[i], n, h_samples + i * HOT_SAMPLES);
-        if (have_tab[i] && !done_fused[i])
-            hipLaunchKernelGGL(k_table_check, dim3(1), dim3(HOT_SAMPLES), 0, stream,
-                               (const Affine*)(bases_each && bases_each[i] ? bases_each[i] : d_bases), founds[i].table, n, h_stale + i);
-    }
+    size_t lanes = (size_t)env_int("H2_MSM_LANES", 2, 4, 2);
+    if (!per || lanes * per > scratch_bytes) lanes = 2;
+    // (every column is sampled, the fused and the empty ones too; only the pipeline's columns are decided and launched)
+    for (size_t i = 0; i < count; i++) plan_probe(plans[i], n, h_samples + i * HOT_SAMPLES, h_stale + i, stream);
     H2_HIP(hipStreamSynchronize(stream));  // inputs produced on the caller's stream are complete; samples are in
     for (size_t i = 0; i < count; i++)
-        if (have_tab[i] && h_stale[i]) {  // the bases changed under their table (see k_table_check): windowed form, table dropped
-            table_drop_containing(bases_each && bases_each[i] ? bases_each[i] : d_bases);
-            use_tab[i] = have_tab[i] = 0;
-        }
-    std::vector<Hot> hots(count);
-    for (size_t i = 0; i < count; i++) {
-        hots[i] = detect_hot(h_samples + i * HOT_SAMPLES);
-        if (hots[i].on && !done_fused[i] && shapes[2 * i].W <= 2) hots[i].on = false;  // nothing to gain (see msm_device)
-        if (use_tab[i] && !done_fused[i]) {
-            const uint32_t bits = bits_each ? bits_each[i] : max_bits;
-            if (table_pays(tabs[i], n, bits, hots[i])) {
-                shapes[2 * i] = tshapes[2 * i];
-                shapes[2 * i + 1] = tshapes[2 * i + 1];
-            } else {
-                use_tab[i] = 0;
-            }
-        }
-        if (hots[i].on && have_tab[i] && !done_fused[i] && founds[i].blocks &&
-            (use_tab[i] ? (size_t)tabs[i].D * tabs[i].n : n) < BLOCK_INDEX0)
-            hots[i].block_sums = founds[i].blocks;
-    }
-    std::vector<hipEvent_t> done(count, nullptr);
+        if (plans[i].active()) plan_decide(plans[i], n, h_samples + i * HOT_SAMPLES, h_stale + i);
+    std::vector<ColumnEvent> done(count);
     size_t lane_of = 0;
     for (size_t i = 0; i < count; i++) {
-        const uint32_t bits = bits_each ? bits_each[i] : max_bits;
-        if (bits == 0 || done_fused[i]) continue;  // identity (arithmetic.rs:346) / already committed in a fused group
-        const MsmShape& s = shapes[2 * i + (hots[i].on ? 1 : 0)];
-        const uint64_t* bases = bases_each && bases_each[i] ? bases_each[i] : d_bases;
+        const ColumnPlan& p = plans[i];
+        if (!p.active()) continue;
         char* scratch = (char*)d_scratch + (lane_of % lanes) * per;
         hipStream_t q = st[lane_of % lanes];
         lane_of++;
-        msm_launch(s, hots[i], d_scalars[i], use_tab[i] ? tabs[i].table : (const Affine*)bases, bits, scratch, q);
-        export_to_host((const XYZZ*)(scratch + s.off_winpart), h_win + i * wp_max, (size_t)s.Wt * s.G + s.planes, q);
-        H2_HIP(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
-        H2_HIP(hipEventRecord(done[i], q));
+        msm_launch(p.shape, p.hot, p.scalars, p.points(), p.bits, scratch, q);
+        export_to_host((const XYZZ*)(scratch + p.shape.off_winpart), h_win + i * wp_max, exported_points(p.shape), q);
+        hipEvent_t e = nullptr;
+        H2_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        done[i].reset(e);
+        H2_HIP(hipEventRecord(e, q));
     }
     for (size_t i = 0; i < count; i++) {
-        if (done_fused[i]) continue;
+        const ColumnPlan& p = plans[i];
+        if (p.fused) continue;
         if (!done[i]) {
             msm_identity(out_xyz + 12 * i);
             continue;
         }
-        const MsmShape& s = shapes[2 * i + (hots[i].on ? 1 : 0)];
-        H2_HIP(hipEventSynchronize(done[i]));
-        H2_HIP(hipEventDestroy(done[i]));
-        std::vector<XYZZ> winpart(h_win + i * wp_max, h_win + i * wp_max + (size_t)s.Wt * s.G + s.planes);
-        msm_host_tail(s, hots[i], winpart, out_xyz + 12 * i);
+        H2_HIP(hipEventSynchronize(done[i].get()));
+        H2_HIP(hipEventDestroy(done[i].release()));
+        std::vector<XYZZ> winpart(h_win + i * wp_max, h_win + i * wp_max + exported_points(p.shape));
+        msm_host_tail(p.shape, p.hot, winpart, out_xyz + 12 * i);
     }
     return H2_OK;
 }
 
+// scratch that lets h2_dev_msm_batch(_ex) fuse `count` columns of bound `max_bits` over one base table
 size_t msm_batch_scratch_bytes(size_t n, uint32_t max_bits, size_t count) {
     const size_t pipeline = 2 * align_up(msm_scratch_bytes(n, max_bits), 256);
     if (count < 2 || n == 0 || max_bits == 0) return pipeline;
     const uint32_t g = (uint32_t)std::min<size_t>(count, fused_group_limit(n, max_bits));
     return g >= 2 ? std::max(pipeline, msm_shape(n, max_bits, false, g).total) : pipeline;
-}
-
-// ---- resident SRS: host ranges the caller promised not to modify (h2_bases_register).  The reference
-// re-uploads the bases on every MSM (arithmetic.rs:354-360); at 2^20 that is 64 MiB of PCIe per call,
-// about as long as the MSM itself.
-namespace {
-struct Registration {
-    size_t len;    // in units of `unit` bytes: points (64) for an SRS range, field elements (32) for a polynomial
-    uint64_t gen;  // bumped by every register / unregister: a device copy made for another generation is stale
-    uint32_t unit; // 64: G1Affine points (h2_bases_register); 32: Fr coefficients / values (h2_poly_register: no table)
-};
-std::mutex g_reg_mu;
-std::map<const uint64_t*, Registration> g_registered;  // host pointer -> length, generation, element size
-uint64_t g_reg_gen = 0;
-}  // namespace
-
-int bases_register(const uint64_t* bases, size_t n) {
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    g_registered[bases] = Registration{n, ++g_reg_gen, 64u};
-    return H2_OK;
-}
-
-// h2_poly_register: a host vector of n field elements the caller promises not to modify -- the proving key's fixed / sigma / l_0 /
-// l_last coefficient forms (plonk.rs:226-240), read by every proof (plonk/evaluation.rs:1229-1241, prover.rs:731-737) -- so that
-// the host-slice entry points that READ vectors find a device copy uploaded once per device instead of crossing PCIe per call.
-// Same registry, generations and unregister path as the SRS ranges; no shifted-base table, of course.
-int poly_register(const uint64_t* values, size_t n) {
-    std::lock_guard<std::mutex> g(g_reg_mu);
-    g_registered[values] = Registration{n, ++g_reg_gen, 32u};
-    return H2_OK;
-}
-
-int bases_unregister(const uint64_t* bases) {
-    {
-        std::lock_guard<std::mutex> g(g_reg_mu);
-        g_registered.erase(bases);
-        ++g_reg_gen;
-    }
-    // free the device copies now, on every device (under the locks of ALL its host-API slots: a host-buffer MSM holds its
-    // slot's lock until its result is back, so nothing in flight reads the copy; then the shared map's own lock); a device
-    // that never runs another MSM would keep them otherwise
-    std::map<DeviceShared*, std::vector<DeviceCtx*>> by_device;
-    for (DeviceCtx* ctx : existing_contexts()) by_device[ctx->shared].push_back(ctx);
-    for (auto& dv : by_device) {
-        std::sort(dv.second.begin(), dv.second.end(), [](DeviceCtx* a, DeviceCtx* b) { return a->slot < b->slot; });
-        for (DeviceCtx* ctx : dv.second) ctx->mu.lock();
-        {
-            std::lock_guard<std::mutex> g(dv.first->mu);
-            auto it = dv.first->resident.find((const void*)bases);
-            if (it != dv.first->resident.end()) {
-                bases_forget((const uint64_t*)it->second.ptr);
-                (void)hipFree(it->second.ptr);
-                dv.first->resident.erase(it);
-            }
-            for (ResidentCopy& c : dv.first->retired) {
-                bases_forget((const uint64_t*)c.ptr);
-                (void)hipFree(c.ptr);
-            }
-            dv.first->retired.clear();
-        }
-        for (DeviceCtx* ctx : dv.second) ctx->mu.unlock();
-    }
-    return H2_OK;
-}
-
-// device copy of a registered range that contains [bases, bases + n) -- or nullptr.  A copy is reused only for the
-// registration (generation, length) it was uploaded for: unregister + refill + register of the same address uploads
-// the new points.
-static const void* resident_lookup_unit(DeviceCtx* ctx, const uint64_t* bases, size_t n, uint32_t unit);
-static const Affine* resident_lookup(DeviceCtx* ctx, const uint64_t* bases, size_t n) {
-    return (const Affine*)resident_lookup_unit(ctx, bases, n, 64u);
-}
-// the device copy of host Fr values [values, values + n) when they lie inside a range registered with h2_poly_register (uploaded
-// on this device's first use, complete when this returns) -- or nullptr: the caller uploads as before.  Call with the slot's lock.
-const Fr* poly_resident(DeviceCtx* ctx, const uint64_t* values, size_t n) {
-    {
-        std::lock_guard<std::mutex> g(g_reg_mu);
-        if (g_registered.empty()) return nullptr;     // (the common case of a caller that registers nothing: no device lock taken)
-    }
-    return (const Fr*)resident_lookup_unit(ctx, values, n, 32u);
-}
-static const void* resident_lookup_unit(DeviceCtx* ctx, const uint64_t* bases, size_t n, uint32_t unit) {
-    const uint64_t* key = nullptr;
-    Registration reg{0, 0, 0};
-    const size_t words = unit / 8;
-    // the device copies are shared by the host-API slots of the device: one slot uploads (and tabulates) an SRS, the other
-    // waits here and finds it complete
-    std::lock_guard<std::mutex> shared_lock(ctx->shared->mu);
-    {
-        std::lock_guard<std::mutex> g(g_reg_mu);
-        // Device copies whose registration is gone or was replaced are never FREED here: this caller holds its own slot's
-        // lock only, and the other host-API slot of the device may be in the middle of an MSM over such a copy.
-        // A copy whose registration is gone is about to be freed by the h2_bases_unregister that removed it (under every
-        // slot's lock); one whose registration was REPLACED (register again without unregister) steps aside into `retired`,
-        // which the next unregister empties the same way.
-        for (auto it = ctx->resident.begin(); it != ctx->resident.end();) {
-            auto r = g_registered.find((const uint64_t*)it->first);
-            if (r != g_registered.end() && (r->second.gen != it->second.gen || r->second.len != it->second.len)) {
-                ctx->shared->retired.push_back(it->second);
-                it = ctx->resident.erase(it);
-            } else {
-                ++it;
-            }
-        }
-        auto it = g_registered.upper_bound(bases);
-        if (it == g_registered.begin()) return nullptr;
-        --it;
-        if (it->second.unit != unit) return nullptr;      // points asked of a polynomial's range or the reverse
-        if (bases + words * n > it->first + words * it->second.len) return nullptr;
-        if ((size_t)(bases - it->first) % words) return nullptr;   // (not on an element boundary of the registered range)
-        key = it->first;
-        reg = it->second;
-    }
-    auto rit = ctx->resident.find((const void*)key);
-    if (rit != ctx->resident.end() && (rit->second.gen != reg.gen || rit->second.len != reg.len)) return nullptr;  // (cannot happen: swept above)
-    if (rit == ctx->resident.end()) {
-        ResidentCopy c;
-        c.len = reg.len;
-        c.gen = reg.gen;
-        H2_HIP(hipMalloc(&c.ptr, reg.len * (size_t)unit));
-        host_upload(c.ptr, key, reg.len * (size_t)unit, ctx->stream);
-        rit = ctx->resident.emplace((const void*)key, c).first;
-        // a registered SRS is committed against for the life of the process: give its device copy a shifted-base table
-        // when that takes less than half of the free memory (H2_MSM_TABLES=0: never)
-        // -- an OPTIONAL optimisation: a failed build (allocation, launch) must not fail the MSM that triggered it; the
-        // windowed pipeline answers with the same point
-        const char* env = getenv("H2_MSM_TABLES");
-        size_t free_b = 0, total_b = 0;
-        if (unit == 64u && !(env && env[0] == '0') && reg.len >= ((size_t)1 << 15) && hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
-            bases_precompute_bytes(reg.len, 0) < free_b / 2) {
-            try {
-                if (bases_precompute((const uint64_t*)c.ptr, reg.len, 0, ctx->stream) != H2_OK) (void)hipGetLastError();
-            } catch (const HipError&) {
-                (void)hipGetLastError();  // clear the sticky error; no table for this copy
-            }
-        }
-        H2_HIP(hipStreamSynchronize(ctx->stream));  // complete before another slot (another stream) can find it
-    }
-    return (const char*)rit->second.ptr + (size_t)(bases - key) * 8;
-}
-
-int msm_host_resident_scalars(DeviceCtx* ctx, const Fr* d_scalars, const uint64_t* bases, size_t n, uint32_t max_bits,
-                              uint64_t out_xyz[12]) {
-    const Affine* d_bases = resident_lookup(ctx, bases, n);
-    if (!d_bases) {
-        Affine* up = (Affine*)ctx->buf_c.get(n * sizeof(Affine));
-        host_upload(up, bases, n * sizeof(Affine), ctx->stream);
-        d_bases = up;
-    }
-    size_t sb = msm_scratch_bytes(n, max_bits);
-    void* scratch = ctx->msm_scratch.get(sb);
-    return msm_device(ctx, d_scalars, (const uint64_t*)d_bases, n, max_bits, scratch, sb, out_xyz, ctx->stream);
-}
-
-int msm_host(DeviceCtx* ctx, const uint64_t* scalars, const uint64_t* bases, size_t n, uint32_t max_bits,
-             uint64_t out_xyz[12]) {
-    Fr* d_s = (Fr*)ctx->buf_d.get(n * sizeof(Fr));
-    host_upload(d_s, scalars, n * sizeof(Fr), ctx->stream);
-    return msm_host_resident_scalars(ctx, d_s, bases, n, max_bits, out_xyz);
-}
-
-// gpu_multiexp_bound (arithmetic.rs:413-440): ceil(n / N_GPU) contiguous chunks, one leased
-// device each (par_chunks), partial points folded on the host (`reduce(|acc, x| acc + x)`).
-int msm_host_multi(const uint64_t* scalars, const uint64_t* bases, size_t n, uint32_t max_bits, uint64_t out_xyz[12]) {
-    int n_gpu = device_count();
-    if (n_gpu <= 0) throw HipError{hipErrorNoDevice, "no HIP device visible", __FILE__, __LINE__};
-    size_t part_len = (n + n_gpu - 1) / n_gpu;
-    size_t nparts = (n + part_len - 1) / part_len;
-    std::vector<std::array<uint64_t, 12>> parts(nparts);
-    std::vector<int> rcs(nparts, H2_OK);
-    std::vector<std::string> errs(nparts);
-    std::vector<std::thread> th;
-    for (size_t p = 0; p < nparts; p++) {
-        th.emplace_back([&, p] {
-            size_t lo = p * part_len, len = std::min(part_len, n - lo);
-            rcs[p] = guarded([&] {
-                DeviceLease lease;
-                return msm_host(lease.ctx, scalars + 4 * lo, bases + 8 * lo, len, max_bits, parts[p].data());
-            });
-            if (rcs[p] != H2_OK) errs[p] = get_last_error();
-        });
-    }
-    for (auto& t : th) t.join();
-    for (size_t p = 0; p < nparts; p++)
-        if (rcs[p] != H2_OK) {
-            set_last_error(errs[p]);
-            return rcs[p];
-        }
-    g1_sum_host(parts[0].data(), nparts, out_xyz);
-    return H2_OK;
-}
-
-// host fold of `count` Jacobian points (12 x u64 each) -- the `reduce(|acc, x| acc + x)` of
-// arithmetic.rs:434 and the local add after an all-gather of per-rank partial points.
-// Jacobian (X, Y, Z) -> XYZZ (X, Y, Z^2, Z^3).
-// Device-side fold of gathered partial points (one proof over several ranks): points[r * count + j] = rank r's partial of
-// MSM j (Jacobian, 96 B), out[j] = sum over r in rank order -- the `.reduce(|acc, x| acc + x)` of arithmetic.rs:433-435
-// after an all-gather, without bringing world x count points back to the host.  One lane per MSM (count is ~10).
-__global__ void __launch_bounds__(64) k_g1_fold(const Jacobian* points, uint32_t world, uint32_t count, Jacobian* out) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= count) return;
-    XYZZ acc = xyzz_identity();
-    for (uint32_t r = 0; r < world; r++) {
-        const Jacobian p = points[(size_t)r * count + j];
-        XYZZ q;
-        q.x = p.x;
-        q.y = p.y;
-        q.zz = fp_sqr(p.z);
-        q.zzz = fp_mul(q.zz, p.z);
-        acc = xyzz_add(acc, q);
-    }
-    out[j] = xyzz_to_jacobian(acc);
-}
-
-int g1_fold_launch(const uint64_t* d_points, uint32_t world, uint32_t count, uint64_t* d_out, hipStream_t stream) {
-    if (count == 0) return H2_OK;
-    hipLaunchKernelGGL(k_g1_fold, dim3((count + 63) / 64), dim3(64), 0, stream, (const Jacobian*)d_points, world, count,
-                       (Jacobian*)d_out);
-    H2_HIP(hipGetLastError());
-    return H2_OK;
-}
-
-void g1_sum_host(const uint64_t* points, size_t count, uint64_t out_xyz[12]) {
-    XYZZ acc = xyzz_identity();
-    for (size_t p = 0; p < count; p++) {
-        Jacobian j;
-        memcpy(&j, points + 12 * p, 96);
-        XYZZ q;
-        q.x = j.x;
-        q.y = j.y;
-        q.zz = fp_sqr(j.z);
-        q.zzz = fp_mul(q.zz, j.z);
-        acc = xyzz_add(acc, q);
-    }
-    Jacobian j = xyzz_to_jacobian(acc);
-    memcpy(out_xyz, &j, 96);
 }
 
 }  // namespace h2

@@ -199,3 +199,47 @@ def test_table_is_dropped_when_the_bases_change(oracle, small_tables):
     dev.precompute()                                                           # a fresh table serves the new points
     assert _affine(oracle, dev.msm(scalars)) == _affine(oracle, oracle.best_multiexp(scalars, new))
     dev.forget()
+
+
+def test_table_is_dropped_when_the_bases_change_under_a_batch(oracle, small_tables):
+    """the same rule through h2_dev_msm_batch_ex, the only MSM entry point the prover uses: a uniform column (table form),
+    a mostly-constant one, a 16-bit column (windowed form: the table saves nothing there) and a column of bound 0 (the
+    identity) are committed over a table, the bases are overwritten in place, and the same call must answer for the
+    points now in memory -- as must h2_dev_msm afterwards"""
+    import torch
+
+    L = h2.lib()
+    n = 1 << 13
+    old, new = oracle.random_g1(1101, n), oracle.random_g1(1102, n)
+    dom = oracle.random_fr(1104, n)
+    dom[n // 8:] = dom[5]
+    cols = [oracle.random_fr(1103, n), dom, to_mont([(i * 2654435761) % 65536 for i in range(n)]), oracle.random_fr(1105, n)]
+    bits = [254, 254, 16, 0]
+    count = len(cols)
+    dev = DevMsm(old)
+    dev.precompute()
+    try:
+        d_cols = [torch.from_numpy(np.ascontiguousarray(c).view(np.int64)).cuda() for c in cols]
+        per = max((L.h2_msm_scratch_bytes(n, b) + 255) // 256 * 256 for b in bits)
+        scratch = torch.empty(2 * per, dtype=torch.uint8, device="cuda")
+        sp = (ctypes.c_void_p * count)(*[t.data_ptr() for t in d_cols])
+        bp = (ctypes.c_void_p * count)(*[dev.d_pts.data_ptr()] * count)
+        bb = (ctypes.c_uint32 * count)(*bits)
+
+        def batch(pts):
+            out = np.zeros((count, 12), dtype=np.uint64)
+            rc = L.h2_dev_msm_batch_ex(sp, bp, bb, count, n, scratch.data_ptr(), 2 * per, out.ctypes.data, None)
+            assert rc == 0, L.h2_last_error()
+            got = [_affine(oracle, out[j]) for j in range(count)]
+            for j in range(count):
+                want = (0, 0) if bits[j] == 0 else _affine(oracle, oracle.best_multiexp(cols[j], pts))
+                assert got[j] == want, j
+            return got
+
+        batch(old)
+        dev.d_pts.copy_(torch.from_numpy(new.view(np.int64)).cuda())          # same address, other points
+        torch.cuda.synchronize()
+        got = batch(new)
+        assert _affine(oracle, dev.msm(cols[0])) == got[0]
+    finally:
+        dev.forget()
