@@ -124,6 +124,8 @@ SYMBOLS = {
     "h2_dev_logup_emit": (ctypes.c_int, [_vp, _sz, _sz, _vp, _vp]),
     "h2_range_check_scratch_bytes": (_sz, [_vp, _vp, _sz]),
     "h2_dev_range_check_complete": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp]),
+    "h2_dev_assigned_resolve": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _u32, _vp, _vp]),
+    "h2_assigned_resolve": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _u32, _vp]),
     "h2_permutation_mapping_scratch_bytes": (_sz, [_sz, _sz, _sz]),
     "h2_dev_permutation_mapping": (ctypes.c_int, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
     "h2_dev_permutation_mapping_phases": (ctypes.c_int, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _fp, _vp]),

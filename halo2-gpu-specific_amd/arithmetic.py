@@ -157,6 +157,36 @@ def batch_invert(a):
     return a
 
 
+def batch_invert_assigned(numerators, denominators):
+    """poly.rs:148-173: columns of `Assigned` cells -> columns of field elements, numerator * denominator^-1 with 0 for a
+    zero denominator; one h2_assigned_resolve call for all of them.  numerators[i], denominators[i]: (n, 4) columns;
+    denominators[i] = None is a column of trivial cells (the reference's denominator() == None for every cell)."""
+    nums = [_fr(a).reshape(-1, 4) for a in numerators]
+    assert len(nums) == len(denominators)
+    if not nums:
+        return []
+    n = len(nums[0])
+    one = None
+    dens = []
+    for a, d in zip(nums, denominators):
+        assert len(a) == n
+        if d is None:
+            if one is None:
+                one = gpu_mont(np.tile(np.array([1, 0, 0, 0], dtype=np.uint64), (n, 1)))
+            d = one
+        d = _fr(d).reshape(-1, 4)
+        assert len(d) == n
+        dens.append(d)
+    outs = [np.zeros((n, 4), dtype=np.uint64) for _ in nums]
+    count = len(nums)
+    ptrs = lambda cols: (ctypes.c_void_p * count)(*[c.ctypes.data for c in cols])    # noqa: E731
+    forms = (ctypes.c_uint32 * count)(*([1] * count))                                # H2_ASSIGNED_FORM_MONTGOMERY
+    status = np.zeros(4 * count, dtype=np.uint32)
+    check(lib().h2_assigned_resolve(ptrs(nums), forms, ptrs(dens), forms, None, None, ptrs(outs), count, n, 1, _p(status)),
+          "h2_assigned_resolve")
+    return outs
+
+
 def kate_division(a, b):
     """arithmetic.rs:754-773: a(X) / (X - b), no remainder"""
     a = _fr(a).reshape(-1, 4)

@@ -6,6 +6,7 @@
 #include <sys/mman.h>
 #include <thread>
 
+#include "assigned.hpp"
 #include "check.hpp"
 #include "common.hpp"
 #include "evalh.hpp"
@@ -1582,6 +1583,78 @@ int h2_dev_range_check_complete(void* const* d_origins, void* const* d_companion
         return range_check_complete_launch(d_origins, d_companions, origin_forms, companion_forms, vmin, vmax, step,
                                            first_unassigned, pairs, usable_rows, n, (uint32_t*)d_status, d_scratch,
                                            pick_stream(ctx, stream));
+    });
+}
+
+// ------------------------------------------------------------------ rational (Assigned) cells
+int h2_dev_assigned_resolve(const void* const* d_num, const uint32_t* num_forms, const void* const* d_den,
+                            const uint32_t* den_forms, const uint32_t* const* d_rows, const uint64_t* counts,
+                            void* const* d_out, size_t cols, size_t n, uint32_t out_form, void* d_status, void* stream) {
+    if (const char* what = assigned_validate(d_num, num_forms, d_den, den_forms, d_rows, counts, d_out, cols, n, out_form,
+                                             d_status, true))
+        return bad((std::string("h2_dev_assigned_resolve: ") + what).c_str());
+    return guarded([&] {
+        if (cols == 0) return (int)H2_OK;
+        hipStream_t s = pick_stream(current_ctx(), stream);
+        std::vector<AssignedColumn> c(cols);
+        for (size_t i = 0; i < cols; i++) {
+            const uint32_t* rows = d_rows ? d_rows[i] : nullptr;
+            c[i] = AssignedColumn{d_num[i], d_den[i], rows, d_out[i], (uint32_t*)d_status + i * H2_ASSIGNED_STATUS_WORDS,
+                                  rows ? counts[i] : (uint64_t)n, num_forms[i], den_forms[i], 0};
+        }
+        H2_TRY(assigned_status_init((uint32_t*)d_status, cols, s));
+        return assigned_resolve_launch(c.data(), cols, n, out_form, s);
+    });
+}
+
+// What keygen.rs:276 (`batch_invert_assigned` of the fixed columns) and assign_advice would call: the columns go through the
+// staging buffers one after the other, a dense one of page-locked memory chunk by chunk (a chunk of rows is a batch
+// inversion of its own); a sparse one in one piece (its rows index the whole column).
+int h2_assigned_resolve(const void* const* num, const uint32_t* num_forms, const void* const* den, const uint32_t* den_forms,
+                        const uint32_t* const* rows, const uint64_t* counts, void* const* out, size_t cols, size_t n,
+                        uint32_t out_form, uint32_t* status) {
+    if (const char* what = assigned_validate(num, num_forms, den, den_forms, rows, counts, out, cols, n, out_form, status, false))
+        return bad((std::string("h2_assigned_resolve: ") + what).c_str());
+    return guarded([&] {
+        if (cols == 0) return (int)H2_OK;
+        HostCall call;
+        DeviceCtx* ctx = call.ctx;
+        const size_t status_bytes = cols * H2_ASSIGNED_STATUS_WORDS * sizeof(uint32_t);
+        uint32_t* d_status = (uint32_t*)ctx->buf_d.get(status_bytes);
+        H2_TRY(assigned_status_init(d_status, cols, call.stream));
+        for (size_t i = 0; i < cols; i++) {
+            const uint32_t* r = rows ? rows[i] : nullptr;
+            const size_t m = r ? (size_t)counts[i] : n;
+            const size_t ncell = num_forms[i] == H2_ASSIGNED_FORM_COMPACT ? 8 : 32, dcell = den_forms[i] == H2_ASSIGNED_FORM_COMPACT ? 8 : 32;
+            HostResult res((uint64_t*)out[i], n, {num[i], den[i]});
+            const bool pipe = !r && use_pipeline(n, {num[i], den[i], out[i]});
+            const size_t chunk = pipe ? PIPE_CHUNK : n, slots = pipe ? 2 : 1;
+            const size_t den_bytes = (std::min(chunk, m) * dcell + 15) & ~(size_t)15;        // (the rows follow the denominators)
+            char* d_num = (char*)ctx->buf_a.get(slots * chunk * ncell);
+            char* d_den = (char*)ctx->buf_b.get(slots * den_bytes + (r ? m * sizeof(uint32_t) : 0) + 16);
+            Fr* d_out = (Fr*)ctx->buf_c.get(slots * chunk * sizeof(Fr));
+            uint32_t* d_rows = r ? (uint32_t*)(d_den + den_bytes) : nullptr;
+            H2_TRY(call.chunked(n, pipe,
+                [&](size_t off, size_t len, int slot, hipStream_t st) {
+                    host_upload(d_num + slot * chunk * ncell, (const char*)num[i] + off * ncell, len * ncell, st);
+                    if (r) {
+                        if (m) host_upload(d_den, den[i], m * dcell, st);
+                        if (m) host_upload(d_rows, r, m * sizeof(uint32_t), st);
+                    } else {
+                        host_upload(d_den + slot * den_bytes, (const char*)den[i] + off * dcell, len * dcell, st);
+                    }
+                },
+                [&](size_t off, size_t len, int slot, hipStream_t st) {
+                    const AssignedColumn c{d_num + slot * chunk * ncell, d_den + slot * den_bytes, d_rows, d_out + slot * chunk,
+                                           d_status + i * H2_ASSIGNED_STATUS_WORDS, (uint64_t)(r ? m : len), num_forms[i], den_forms[i],
+                                           (uint32_t)off};
+                    return assigned_resolve_launch(&c, 1, len, out_form, st);
+                },
+                [&](size_t off, size_t len, int slot, const ChunkSink& to) { to(res, off, len, d_out + slot * chunk); }));
+        }
+        host_download(status, d_status, status_bytes, call.stream);
+        H2_HIP(hipStreamSynchronize(call.stream));
+        return (int)H2_OK;
     });
 }
 

@@ -349,6 +349,20 @@ class HostApiDevice(P.Device):
     def upload_async(self, a):
         return (self.clone(a) if self.torch.is_tensor(a) else self.upload(a)), None
 
+    def _assigned_operand(self, a):
+        """an operand of resolve_rational where the caller has it: pageable host memory, read by the call itself"""
+        if self.torch.is_tensor(a):
+            return a
+        a = np.ascontiguousarray(a)
+        return self.torch.from_numpy(a.view(np.int32 if a.dtype == np.uint32 else np.int64))
+
+    def _assigned_call(self, num, nforms, den, dforms, rows, counts, outs, count, n, out_form):
+        status = np.zeros(count * P.ASSIGNED_STATUS_WORDS, dtype=np.uint32)
+        self.L._count("h2_assigned_resolve")
+        check(self.L.R.h2_assigned_resolve(num, nforms, den, dforms, rows, counts, outs, count, n, out_form, status.ctypes.data),
+              "h2_assigned_resolve")
+        return status
+
     def widen(self, small, stream=None):
         out = self.zeros(small.shape[0])
         out[:, 0] = small

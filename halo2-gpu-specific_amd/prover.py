@@ -277,6 +277,27 @@ class Device:
         small.record_stream(self.tstream)
         return out
 
+    def resolve_rational(self, columns, n, montgomery, strict=False, input_montgomery=None, names=None):
+        """Rational columns -> device vectors (see prover.resolve_rational)"""
+        return resolve_rational(self, columns, n, montgomery, strict, input_montgomery, names)
+
+    def _assigned_operand(self, a):
+        """an operand of resolve_rational as it crosses PCIe: compact cells stay 8 bytes, row indices 4"""
+        if self.torch.is_tensor(a):
+            return a
+        if a.dtype == np.uint32:
+            with self.torch.cuda.stream(self.tstream):
+                return self.torch.from_numpy(a.view(np.int32)).to(self.dev)
+        return self.upload(a, widen=False)
+
+    def _assigned_call(self, num, nforms, den, dforms, rows, counts, outs, count, n, out_form):
+        with self.torch.cuda.stream(self.tstream):
+            status = self.torch.empty(count * ASSIGNED_STATUS_WORDS, dtype=self.torch.int32, device=self.dev)
+        check(self.L.h2_dev_assigned_resolve(num, nforms, den, dforms, rows, counts, outs, count, n, out_form,
+                                             status.data_ptr(), self.stream), "h2_dev_assigned_resolve")
+        with self.torch.cuda.stream(self.tstream):
+            return status.cpu().numpy().view(np.uint32)
+
     def upload_async(self, a):
         """-> (device tensor, event or None): a pinned source is copied by DMA on the copy stream and the event marks
         its arrival; anything else goes through the synchronous path.  `a`: a canonical (n, 4) u64 column, a COMPACT column
@@ -1262,10 +1283,12 @@ def program_descriptor(cs, k, extended_k, graph=None, value_parts=None, lookup_c
         y=zero, beta=zero, gamma=zero, theta=zero, delta=zero, zeta=zero, extended_omega=zero)
 
 
-def keygen(device, params, cs, fixed, copies, mapping=None, fixed_montgomery=False, transcript_repr=None):
+def keygen(device, params, cs, fixed, copies, mapping=None, fixed_montgomery=False, transcript_repr=None, strict_rationals=False):
     """keygen_vk + keygen_pk.  fixed: list of canonical (n, 4) u64 columns; copies: see permutation_mapping.
     `mapping` = (map_col, map_row) replaces `copies` and `fixed_montgomery` marks columns already in the in-memory
-    representation: the two things a CircuitData file holds (keygen_pk_from_info, plonk/keygen.rs:458-553)."""
+    representation: the two things a CircuitData file holds (keygen_pk_from_info, plonk/keygen.rs:458-553).
+    A fixed column may be a `Rational` (batch_invert_assigned, keygen.rs:276): resolved on the device straight to the
+    in-memory representation, all of them by one call; `strict_rationals` makes a zero denominator a ValueError."""
     D, L = device, device.L
     dom = Domain(params.k, cs.degree())
     n, bf = dom.n, cs.blinding_factors()
@@ -1281,7 +1304,13 @@ def keygen(device, params, cs, fixed, copies, mapping=None, fixed_montgomery=Fal
         plan = (dom.quotient_poly_degree, 1, list(range(dom.quotient_poly_degree)))
     # fixed columns: values, coefficient form, extended cosets
     pk.fixed_values = []
-    for col in fixed:
+    rational = [isinstance(col, Rational) for col in fixed]
+    if any(rational):
+        fixed = _resolve_rational_columns(D, list(fixed), n, True, strict_rationals, "fixed", input_montgomery=fixed_montgomery)
+    for col, resolved in zip(fixed, rational):
+        if resolved:                                                 # Montgomery already
+            pk.fixed_values.append(col)
+            continue
         t = D.upload(col)
         if not fixed_montgomery:
             check(L.h2_dev_batch_mont(t.data_ptr(), n, D.stream), "h2_dev_batch_mont")
@@ -1449,14 +1478,14 @@ def _vanishing(roots, z):
     return acc
 
 
-def create_proof(device, params, pk, advice, rng, timings=None, instances=()):
+def create_proof(device, params, pk, advice, rng, timings=None, instances=(), strict_rationals=False):
     """plonk/prover.rs:877-893: the GWC multiopen, as the reference's `create_proof`"""
-    return create_proof_ext(device, params, pk, advice, rng, True, timings, instances)
+    return create_proof_ext(device, params, pk, advice, rng, True, timings, instances, strict_rationals=strict_rationals)
 
 
-def create_proof_with_shplonk(device, params, pk, advice, rng, timings=None, instances=()):
+def create_proof_with_shplonk(device, params, pk, advice, rng, timings=None, instances=(), strict_rationals=False):
     """plonk/prover.rs:856-871"""
-    return create_proof_ext(device, params, pk, advice, rng, False, timings, instances)
+    return create_proof_ext(device, params, pk, advice, rng, False, timings, instances, strict_rationals=strict_rationals)
 
 
 _ANY = {"advice": ev.ANY_ADVICE, "fixed": ev.ANY_FIXED, "instance": ev.ANY_INSTANCE}
@@ -1638,14 +1667,127 @@ def complete_range_check_witness_device(device, cs, n, advice, first_unassigned=
     return advice
 
 
+ASSIGNED_FORM_CANONICAL, ASSIGNED_FORM_MONTGOMERY, ASSIGNED_FORM_COMPACT = 0, 1, 2       # H2_ASSIGNED_FORM_*
+ASSIGNED_OK, ASSIGNED_BAD_ROWS = 0, 1                                                    # H2_ASSIGNED_*
+ASSIGNED_STATUS_WORDS = 4
+
+
+class Rational:
+    """A column of rational cells num / den (the reference's `Assigned<F>`, plonk/assigned.rs) that may stand wherever a
+    column may: in `advice` of create_proof* and check_witness, in `fixed` of keygen.  It is resolved on the device
+    (Device.resolve_rational: one batch inversion for all rational columns of a circuit instance); a zero denominator
+    gives 0, as `Assigned::evaluate` does.
+
+    num: the n numerators -- an (n, 4) u64 column, a compact 1-D u64 column, or a device tensor of either shape.
+    den: the denominators, likewise: n of them, or len(rows) with `rows`, the strictly increasing indices of the rows that
+    HAVE a denominator (the reference's `Option<F>`: only they cross PCIe); every other row is num.
+    32-byte cells are in the form of the call they are handed to (canonical integers, or Montgomery residues under
+    `montgomery` / `fixed_montgomery`).  Host arrays are checked here, without a device."""
+
+    def __init__(self, num, den, rows=None):
+        self.num, self.den = self._column(num, "num"), self._column(den, "den")
+        self.n = int(self.num.shape[0])
+        if self.n == 0:
+            raise ValueError("Rational: a column has at least one row")
+        self.rows = None
+        if rows is not None:
+            if hasattr(rows, "data_ptr"):
+                raise ValueError("Rational: rows is a host array of row indices")
+            r = np.asarray(rows)
+            if r.ndim != 1 or (r.size and r.dtype.kind not in "ui"):
+                raise ValueError("Rational: rows is a 1-D array of row indices")
+            r = r.astype(np.int64)
+            if r.size and (r[0] < 0 or r[-1] >= self.n or np.any(r[1:] <= r[:-1]) or np.any(r >= self.n)):
+                raise ValueError("Rational: rows must be strictly increasing and below n = %d" % self.n)
+            self.rows = np.ascontiguousarray(r.astype(np.uint32))
+        want = self.n if self.rows is None else len(self.rows)
+        if int(self.den.shape[0]) != want:
+            raise ValueError("Rational: den has %d entries for %d %s" % (int(self.den.shape[0]), want,
+                                                                         "rows" if self.rows is None else "listed rows"))
+
+    @staticmethod
+    def _column(a, what):
+        if hasattr(a, "data_ptr"):                                   # a device (or host) tensor of i64 words
+            if a.dim() not in (1, 2) or (a.dim() == 2 and a.shape[1] != 4) or a.element_size() != 8 or not a.is_contiguous():
+                raise ValueError("Rational: %s is an (n, 4) or 1-D tensor of contiguous 64-bit words" % what)
+            return a
+        a = np.asarray(a)
+        if a.dtype != np.uint64 or a.ndim not in (1, 2) or (a.ndim == 2 and a.shape[1] != 4):
+            raise ValueError("Rational: %s is an (n, 4) u64 column or a compact 1-D u64 column" % what)
+        return np.ascontiguousarray(a)
+
+
+def resolve_rational(device, columns, n, montgomery, strict=False, input_montgomery=None, names=None):
+    """Device.resolve_rational: the Rational `columns` of n rows -> one (n, 4) vector each, Montgomery residues under
+    `montgomery`, else canonical integers.  ONE h2_dev_assigned_resolve (h2_assigned_resolve on the host-slice device) and
+    one download of its status.  `input_montgomery`: the form of the 32-byte input cells (default: as `montgomery`).
+    ValueError for a bad `rows` (device tensors are first checked there) and, with `strict`, for a zero denominator -- the
+    reference's `unwrap` at prover.rs:1609 -- naming the column (`names`) and its first such row; without, the cell is 0."""
+    D = device
+    count = len(columns)
+    if not count:
+        return []
+    wide = ASSIGNED_FORM_MONTGOMERY if (montgomery if input_montgomery is None else input_montgomery) else ASSIGNED_FORM_CANONICAL
+    names = list(names) if names is not None else ["rational column %d" % i for i in range(count)]
+    keep, ptrs = [], {"num": [], "den": [], "rows": [], "out": []}
+    forms = {"num": [], "den": []}
+    counts = []
+    for c in columns:
+        if not isinstance(c, Rational) or c.n != n:
+            raise ValueError("resolve_rational: every column is a Rational of %d rows" % n)
+        for what in ("num", "den"):
+            t = D._assigned_operand(getattr(c, what))
+            keep.append(t)
+            ptrs[what].append(t.data_ptr() if t.shape[0] else None)
+            forms[what].append(ASSIGNED_FORM_COMPACT if t.dim() == 1 else wide)
+        if c.rows is None:
+            ptrs["rows"].append(None)
+            counts.append(n)
+        else:
+            # (an empty list still says "sparse": one index that is never read keeps the pointer non-null)
+            t = D._assigned_operand(c.rows if len(c.rows) else np.zeros(1, dtype=np.uint32))
+            keep.append(t)
+            ptrs["rows"].append(t.data_ptr())
+            counts.append(len(c.rows))
+    outs = [D.empty(n) for _ in columns]
+    arr = lambda key: (_vp * count)(*ptrs[key])                         # noqa: E731
+    u32s = lambda vals: (ctypes.c_uint32 * count)(*vals)                # noqa: E731
+    out_form = ASSIGNED_FORM_MONTGOMERY if montgomery else ASSIGNED_FORM_CANONICAL
+    status = D._assigned_call(arr("num"), u32s(forms["num"]), arr("den"), u32s(forms["den"]), arr("rows"),
+                              (ctypes.c_uint64 * count)(*counts), (_vp * count)(*[t.data_ptr() for t in outs]), count, n, out_form)
+    del keep
+    for name, rec in zip(names, status.reshape(count, ASSIGNED_STATUS_WORDS)):
+        if rec[0] != ASSIGNED_OK:
+            raise ValueError("%s: rows[%d] is not a row below n above its predecessor" % (name, int(rec[3])))
+        if strict and rec[1]:
+            raise ValueError("%s: zero denominator at row %d (%d in all)" % (name, int(rec[2]), int(rec[1])))
+    return outs
+
+
+def _resolve_rational_columns(device, cols, n, montgomery, strict, what, input_montgomery=None):
+    """the Rational entries of the column list `cols` replaced by their resolved vectors (in the list; one call)"""
+    at = [i for i, c in enumerate(cols) if isinstance(c, Rational)]
+    if at:
+        if device is None:
+            raise ValueError("Rational columns are resolved on a device: none was given")
+        done = device.resolve_rational([cols[i] for i in at], n, montgomery, strict=strict, input_montgomery=input_montgomery,
+                                       names=["%s column %d" % (what, i) for i in at])
+        for i, t in zip(at, done):
+            cols[i] = t
+    return cols
+
+
 def _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, copy_range_columns=False, device=None,
-                  range_checks_on_device=False):
+                  range_checks_on_device=False, strict_rationals=False):
     """The witness intake of create_proof_ext: (advice_sets, instance_sets), one list per circuit instance, with the
     range-checked columns completed (complete_range_check_witness, in place on the caller's columns unless
     `copy_range_columns`, which completes copies of them instead).  An instance whose range-checked columns or companions
     are device tensors, or Montgomery residues, or every instance with `range_checks_on_device`, is completed on the device
     (complete_range_check_witness_device: host columns are uploaded, not written).  An instance of host columns with a range
-    of 2^24 values or more stays on the host under `range_checks_on_device` too, completed on copies."""
+    of 2^24 values or more stays on the host under `range_checks_on_device` too, completed on copies.
+    A `Rational` column is resolved first (Device.resolve_rational, one call per circuit instance that has any; a zero
+    denominator is a ValueError under `strict_rationals`) and is a device vector from there on; without one the caller's
+    columns go through as they are."""
     multi = len(advice) > 0 and isinstance(advice[0], (list, tuple))
     advice_sets = [list(a) for a in advice] if multi else [list(advice)]
     instance_sets = [list(i) for i in instances] if multi else [list(instances)]
@@ -1654,6 +1796,9 @@ def _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, copy_r
     nadv = len(advice_sets[0])
     if any(len(a) != nadv for a in advice_sets):
         raise ValueError("every circuit instance needs the same advice columns")
+    for ci, a in enumerate(advice_sets):                      # rational cells first: a resolved column is a resident one
+        _resolve_rational_columns(device, a, n, montgomery, strict_rationals,
+                                  "advice" if len(advice_sets) == 1 else "circuit instance %d: advice" % ci)
     if cs.range_checks:
         fu = first_unassigned if isinstance(first_unassigned, (list, tuple)) else [first_unassigned] * len(advice_sets)
         for a, f in zip(advice_sets, fu):                     # prover.rs:1699-1783: plant the range, sort the companion
@@ -1681,19 +1826,23 @@ def _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, copy_r
     return advice_sets, instance_sets
 
 
-def create_proof_from_witness(device, params, pk, witness, rng, use_gwc=True, timings=None, instances=()):
+def create_proof_from_witness(device, params, pk, witness, rng, use_gwc=True, timings=None, instances=(), strict_rationals=False):
     """plonk/prover.rs:916-1500: the advice columns come from a witness file (formats.witness_fetch), i.e. in the
     in-memory Montgomery representation"""
-    return create_proof_ext(device, params, pk, witness, rng, use_gwc, timings, instances, montgomery=True)
+    return create_proof_ext(device, params, pk, witness, rng, use_gwc, timings, instances, montgomery=True,
+                            strict_rationals=strict_rationals)
 
 
 def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, instances=(), montgomery=False,
-                     first_unassigned=None, range_checks_on_device=False):
+                     first_unassigned=None, range_checks_on_device=False, strict_rationals=False):
     """plonk/prover.rs:206-850.  advice: list of (n, 4) u64 columns, canonical integers (or Montgomery residues with
     montgomery=True); rows past the usable range are overwritten with blinding values; instances: one list of
     canonical integers per instance column; rng: a rng.ProverRng.  Returns the proof bytes.
     A column may also be COMPACT -- a 1-D u64 array of n values below 2^64 (booleans, bytes, limbs: 8 bytes per cell over
-    PCIe instead of 32, widened on the device) -- or a device tensor of canonical scalars (a witness already resident).
+    PCIe instead of 32, widened on the device) -- or a device tensor of canonical scalars (a witness already resident) --
+    or a `Rational`, a column of fractions (an inverse column, a division, a slope) that is resolved on the device before
+    anything else, in the form `montgomery` names; `strict_rationals`: a zero denominator is a ValueError, not the cell 0
+    (in ANY row, the unused and the blinding rows included: give those the denominator 1, or list the assigned rows, `rows`).
 
     Several circuit instances in one proof (`circuits: &[ConcreteCircuit]`, prover.rs:206-232): pass `advice` as a list
     of such column lists and `instances` as the matching list of instance-column lists.  Every phase then runs circuit
@@ -1772,7 +1921,7 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
         return points_
 
     advice_sets, instance_sets = _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, device=D,
-                                               range_checks_on_device=range_checks_on_device)
+                                               range_checks_on_device=range_checks_on_device, strict_rationals=strict_rationals)
     ncirc, nadv = len(advice_sets), len(advice_sets[0])
     advice = [col for a in advice_sets for col in a]          # circuit-major: the order every phase walks them in
     # The residency of the key was decided at keygen for ONE circuit instance; advice, product and lookup polynomials scale
@@ -2586,13 +2735,14 @@ def _check_scalar(seed, what):
 
 
 def check_witness(device, pk, advice, instances=(), seed=0, max_failures=1024, montgomery=False, first_unassigned=None,
-                  timings=None, range_checks_on_device=False):
+                  timings=None, range_checks_on_device=False, strict_rationals=False):
     """Checks a witness against the circuit of `pk` on the device, as MockProver::run(..).verify() does (dev.rs:932-1340), and
     returns (failures, total): `failures` the first max_failures of them (check_failures: named tuples with MockProver's field
     names, sorted as MockProver chains its errors), `total` the exact number of failures.
 
     The witness is taken as create_proof_ext takes it -- canonical (n, 4) columns, Montgomery ones with montgomery=True,
-    compact 1-D columns, device tensors, several circuit instances as a list of column lists with one instance list each --
+    compact 1-D columns, device tensors, `Rational` columns (resolved first; `strict_rationals` as there), several circuit
+    instances as a list of column lists with one instance list each --
     and is not modified: range-checked columns are completed on copies (complete_range_check_witness, or its device form
     for resident / Montgomery columns and with `range_checks_on_device`; the ValueError propagates) and no blinding value
     is written.  Under a multi-rank Device the check runs on this rank's GPU alone.
@@ -2616,7 +2766,8 @@ def check_witness(device, pk, advice, instances=(), seed=0, max_failures=1024, m
     n = dom.n
     usable = n - (cs.blinding_factors() + 1)
     advice_sets, instance_sets = _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, copy_range_columns=True,
-                                               device=D, range_checks_on_device=range_checks_on_device)
+                                               device=D, range_checks_on_device=range_checks_on_device,
+                                               strict_rationals=strict_rationals)
     cap = max(int(max_failures), 0)
     y, theta = _check_scalar(seed, b"y"), _check_scalar(seed, b"theta")
     t_last = [time.perf_counter()]

@@ -339,6 +339,39 @@ int h2_dev_range_check_complete(void *const *d_origins, void *const *d_companion
                                 const uint64_t *step, const uint64_t *first_unassigned, size_t pairs, size_t usable_rows,
                                 size_t n, void *d_status, void *d_scratch, size_t scratch_bytes, void *stream);
 
+/* Rational cells (`Assigned<F>`, plonk/assigned.rs) resolved to field elements, as poly::batch_invert_assigned
+ * (poly.rs:148-173) does for keygen's fixed columns and the fork's assign_advice cell by cell (plonk/prover.rs:1607-1612):
+ * for each of `cols` columns of n rows, out[r] = num[r] / den[r], and 0 where den[r] = 0 (`Assigned::evaluate`).  All
+ * columns of a call are resolved by one launch (more than fit its arguments: in slices), with one field inversion per
+ * workgroup and no scratch: `out` holds the working state, so no out column may overlap a num or den column of the call.
+ * d_num, d_den, d_rows, d_out, the form codes and counts are HOST arrays of `cols` entries.  Each column is read in its own
+ * form (CANONICAL / MONTGOMERY: 4 u64 per cell, reduced; COMPACT: one u64 per cell, as h2_dev_widen_u64 takes them --
+ * the H2_RANGE_CHECK_FORM_* numbers) and every out column is written in out_form, CANONICAL or MONTGOMERY.
+ *   dense   d_rows == NULL or d_rows[i] == NULL: d_den[i] has n cells (counts[i] is not read)
+ *   sparse  d_rows[i] = counts[i] <= n strictly increasing u32 row indices and d_den[i] has counts[i] cells, the
+ *           denominators of those rows (the reference's `Option<F>`); every other row is num[r] in out_form
+ * The outcome is d_status, H2_ASSIGNED_STATUS_WORDS u32 per column = {code, number of zero denominators, first row with a
+ * zero denominator or 0xffffffff, first bad index into rows or 0xffffffff}, final when the stream reaches the end of the
+ * call:
+ *   OK        resolved
+ *   BAD_ROWS  an entry of rows is not below n or not above its predecessor; nothing was written through it and the
+ *             content of the column is unspecified
+ * Asynchronous on `stream`.  Returns H2_ERR_INVALID without touching a device, h2_last_error naming the argument, for a
+ * null array or element (d_rows[i] may be null; d_den[i] when counts[i] == 0), an unknown form code, n == 0 or n >= 2^32,
+ * counts[i] > n, a misaligned column (16 bytes for 4-u64 cells, 8 for compact ones, 4 for rows) or an out column that
+ * overlaps a num, den, rows or other out column.  cols == 0 does nothing.
+ * h2_assigned_resolve: the same on HOST arrays (8-byte alignment does), status included, through the host-slice call
+ * scope; a dense column of page-locked memory is resolved chunk by chunk under its own transfers. */
+enum { H2_ASSIGNED_FORM_CANONICAL = 0, H2_ASSIGNED_FORM_MONTGOMERY = 1, H2_ASSIGNED_FORM_COMPACT = 2 };
+enum { H2_ASSIGNED_OK = 0, H2_ASSIGNED_BAD_ROWS = 1 };
+#define H2_ASSIGNED_STATUS_WORDS 4
+int h2_dev_assigned_resolve(const void *const *d_num, const uint32_t *num_forms, const void *const *d_den,
+                            const uint32_t *den_forms, const uint32_t *const *d_rows, const uint64_t *counts,
+                            void *const *d_out, size_t cols, size_t n, uint32_t out_form, void *d_status, void *stream);
+int h2_assigned_resolve(const void *const *num, const uint32_t *num_forms, const void *const *den,
+                        const uint32_t *den_forms, const uint32_t *const *rows, const uint64_t *counts, void *const *out,
+                        size_t cols, size_t n, uint32_t out_form, uint32_t *status);
+
 /* The permutation argument's cycle mapping from the copy constraints (plonk/permutation/keygen.rs:49-145: the cycles the
  * copies induce, every cycle sorted by (column, row), each cell mapped to its successor and the last to the first), built
  * on the device.  d_copies: `copies` x 4 u32, row-major, each row (left column position, left row, right column position,
