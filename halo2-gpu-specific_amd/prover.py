@@ -17,12 +17,15 @@ stream.  There is no CPU path in this file: without the library or a GPU it rais
 import ctypes
 import hashlib
 import os
+import time
 from collections import namedtuple
 
 import numpy as np
 
 from . import evaluation as ev
 from ._lib import H2Error, check, lib
+from .arithmetic import (OP_ADDGAMMA, OP_CONSTANT, OP_LCBETA, OP_LCTHETA, OP_MUL, OP_MUL_C, OP_SUB, OP_SUM,  # noqa: F401
+                         OP_SUM_C)                          # Device.eval_op's operations: H2_OP_* of include/halo2_hip.h
 from .circuit import compile_compress, compile_evaluator
 from .transcript import (Blake2bWrite, R_MOD, fr_from_mont_limbs, fr_to_mont_limbs, g1_add_affine, jacobian_to_affine, jacobians_to_affine,
                          point_to_bytes)
@@ -166,7 +169,19 @@ _DEVICE_STREAMS = {}        # (GPU index, stream priorities) -> {"compute", "cop
 
 
 class Device:
-    """Buffers (torch) + stream + thin typed wrappers over the h2_dev_* entry points."""
+    """Buffers (torch) + stream + thin typed wrappers over the h2_dev_* entry points.
+
+    Optional fused steps: a device whose vectors live on the host (host_api.HostApiDevice) does in ONE call what the proof
+    flow otherwise does step by step; None = step by step.
+      permutation_product       one permutation grand product: terms, batch inversion, product and scan
+      logup_grand_sum           one lookup grand sum: beta + f, the inversions, the table's term and the scan
+      commit_lagrange_and_ifft  the product columns' commitments and their inverse transforms
+      quotient_poly_coeff       evaluate_h, the division by the vanishing polynomial and the way back to coefficients
+                                (with `quotient_from_coeffs`: the evaluator is handed COEFFICIENT forms)
+      quotient_sum              a multiopen quotient: the fold, the subtraction of the low terms and the division"""
+    permutation_product = logup_grand_sum = commit_lagrange_and_ifft = quotient_poly_coeff = quotient_sum = None
+    quotient_from_coeffs = False
+    _side = _side_scratch = None            # (side stream, its helper thread) and the side MSM's scratch: made on first use
 
     def __init__(self, device=0, group=None, force_collective=False, force_cosets=False, mem_budget=None, eval_cache=None):
         """`mem_budget` (bytes; default H2_DEVICE_MEM_BUDGET, K / M / G suffixes; None = the device's memory): what the
@@ -187,9 +202,7 @@ class Device:
         torch.cuda.set_device(self.dev)
         self.L = lib()
         # H2_STREAM_PRIORITY = "<compute>,<side>" (torch / HIP stream priorities: lower = more urgent): experiment knob
-        import os as _os
-
-        pr = _os.environ.get("H2_STREAM_PRIORITY", "")
+        pr = os.environ.get("H2_STREAM_PRIORITY", "")
         self._prio = tuple(int(x) for x in pr.split(",")) if pr else (0, 0)
         # The streams belong to the PROCESS, not to the Device object: HIP multiplexes streams onto a few hardware queues
         # (GPU_MAX_HW_QUEUES) in creation order, and streams that share a queue serialise.  A process that made a Device per
@@ -206,8 +219,6 @@ class Device:
         self._scratch = None
         self._pinned = {}
         self.group, self.group_size, self.group_rank, self.force_collective = group, 1, 0, force_collective
-        import os
-
         self.force_cosets = force_cosets or os.environ.get("H2_FORCE_COSETS") == "1"   # experiment knob
         self.mem_budget = mem_budget if mem_budget is not None else parse_bytes(os.environ.get("H2_DEVICE_MEM_BUDGET"))
         if mem_budget is None and self.mem_budget is not None and not os.environ.get("H2_NTT_TABLE_BUDGET"):
@@ -351,26 +362,6 @@ class Device:
                 t[start:start + len(vals)] = blob[at:at + len(vals)]
                 at += len(vals)
 
-    def set_rows_raw(self, t, start, small):
-        """t[start : start + len(small)] <- small non-negative integers < 2^63, limb 0 only (no Montgomery form)"""
-        a = np.zeros((len(small), 4), dtype=np.int64)
-        a[:, 0] = small
-        with self.torch.cuda.stream(self.tstream):
-            t[start:start + len(small)] = self.torch.from_numpy(a).to(self.dev)
-
-    def max_scalar_bits(self, t):
-        """find_max_scalar_bits (plonk/prover.rs:237-254) of a canonical column resident on the device"""
-        torch = self.torch
-        sign = -(1 << 63)
-        with torch.cuda.stream(self.tstream):
-            # unsigned maxima of the four limbs: flip the sign bit so that the signed max orders them as unsigned
-            m = ((t ^ sign).amax(dim=0) ^ sign).cpu().tolist()
-        for limb in (3, 2, 1, 0):
-            v = m[limb] & ((1 << 64) - 1)
-            if v:
-                return 64 * limb + v.bit_length()
-        return 0
-
     def max_scalar_bits_many(self, cols, n):
         """find_max_scalar_bits of several canonical columns resident on the device: one launch, one synchronisation"""
         count = len(cols)
@@ -511,7 +502,7 @@ class Device:
         count = len(ts)
         if count == 0:
             return ts
-        if count == 1 or not hasattr(self.L, "h2_dev_intt_batch"):
+        if count == 1:
             return [self.intt(t, dom) for t in ts]
         width = self._batch_width(dom.n)
         tmp = self.empty(min(count, width) * dom.n)
@@ -614,7 +605,7 @@ class Device:
         computed on the side stream, behind what is queued on the compute stream now; returns (copies, extended or None,
         event): the compute stream must wait for the event before it reads them.  The transforms then fill the issue
         slots that the latency-bound tails of the commitments in between leave."""
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             import concurrent.futures
 
             self._side = (self._side_stream(), concurrent.futures.ThreadPoolExecutor(max_workers=1))
@@ -626,7 +617,7 @@ class Device:
         with self.torch.cuda.stream(side):
             sptr = _vp(side.cuda_stream)
             out = [t.clone() for t in cols]
-            if len(out) >= 2 and hasattr(self.L, "h2_dev_intt_batch"):
+            if len(out) >= 2:
                 width = self._batch_width(dom.n)
                 tmp = self.torch.empty((min(len(out), width) * dom.n, 4), dtype=self.torch.int64, device=self.dev)
                 for at in range(0, len(out), width):
@@ -670,7 +661,7 @@ class Device:
         for that to matter (<= 2^23 points: a pass over one vector does not keep the chip busy; the scratch is 16 extended
         vectors), one by one above"""
         count = len(ts)
-        if count < 2 or dom.extended_k > 23 or not hasattr(self.L, "h2_dev_coeff_to_extended_batch"):
+        if count < 2 or dom.extended_k > 23:
             return [self.coeff_to_extended(t, dom, stream=stream) for t in ts]
         import contextlib
 
@@ -712,14 +703,14 @@ class Device:
             fut = concurrent.futures.Future()
             fut.set_result(point)
             return fut
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = (self._side_stream(), concurrent.futures.ThreadPoolExecutor(max_workers=1))
         side, pool = self._side
         ready = self.torch.cuda.Event()
         ready.record(self.tstream)
         side.wait_event(ready)
         nbytes = self.L.h2_msm_scratch_bytes(n, max_bits)
-        if getattr(self, "_side_scratch", None) is None or self._side_scratch.numel() < nbytes:
+        if self._side_scratch is None or self._side_scratch.numel() < nbytes:
             self._side_scratch = self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.dev)
         scratch = self._side_scratch
 
@@ -860,7 +851,7 @@ class Device:
         at = self.get_rows(tmp, probe - lo, 1)[0] if lo <= probe < hi else 0
         gathered = self._exchange([total, at])
         carries = scan_carries([g[0] for g in gathered], init, product)
-        self.eval_op(0 if product else 1, z[lo:hi], tmp[:m], c=carries[self.group_rank], size=m)   # H2_OP_MUL_C / SUM_C
+        self.eval_op(OP_MUL_C if product else OP_SUM_C, z[lo:hi], tmp[:m], c=carries[self.group_rank], size=m)
         owner = probe // m
         value = carries[owner] * gathered[owner][1] % R_MOD if product else (carries[owner] + gathered[owner][1]) % R_MOD
         return z, value
@@ -920,9 +911,9 @@ class Device:
             if b == 0:                                                # only out[hi - 1] = C
                 self.set_rows(out, hi - 1, [carry])
             else:
-                corr = self.eval_op(8, self.empty(m), c=carry * pow(b, m - 1, R_MOD) % R_MOD)      # H2_OP_CONSTANT
+                corr = self.eval_op(OP_CONSTANT, self.empty(m), c=carry * pow(b, m - 1, R_MOD) % R_MOD)
                 check(self.L.h2_dev_distribute_powers(corr.data_ptr(), m, _fr(_inv(b)), self.stream), "h2_dev_distribute_powers")
-                self.eval_op(2, out[lo:hi], out[lo:hi], corr, size=m)                              # H2_OP_SUM
+                self.eval_op(OP_SUM, out[lo:hi], out[lo:hi], corr, size=m)
         return out
 
 
@@ -1031,7 +1022,7 @@ class Params:
         table = D.upload(np.array([mq(x) + mq(y) for x, y in pts], dtype=np.uint64))
 
         def powers(base):                       # [base^i]: the running product of a constant column
-            f = D.eval_op(8, D.empty(n), c=base)                                # H2_OP_CONSTANT
+            f = D.eval_op(OP_CONSTANT, D.empty(n), c=base)
             out = D.empty(n)
             check(L.h2_dev_prefix_product(f.data_ptr(), n, _fr(1), out.data_ptr(), D.stream), "h2_dev_prefix_product")
             return out
@@ -1045,11 +1036,11 @@ class Params:
 
         g = fixed_base(powers(s))
         w = powers(omega)
-        t = D.eval_op(1, D.empty(n), w, c=-s)                                   # w^i - s
+        t = D.eval_op(OP_SUM_C, D.empty(n), w, c=-s)                            # w^i - s
         check(L.h2_dev_batch_invert(t.data_ptr(), D.empty(n).data_ptr(), n, D.stream), "h2_dev_batch_invert")
-        D.eval_op(3, t, t, w)                                                   # w^i / (w^i - s)
+        D.eval_op(OP_MUL, t, t, w)                                            # w^i / (w^i - s)
         multiplier = (pow(s, n, R_MOD) - 1) * pow(n, -1, R_MOD) % R_MOD
-        D.eval_op(0, t, t, c=-multiplier)                                       # multiplier * w^i / (s - w^i)
+        D.eval_op(OP_MUL_C, t, t, c=-multiplier)                                # multiplier * w^i / (s - w^i)
         g_lagrange = fixed_base(t)
         D.sync()
         params = Params(D, k, g, g_lagrange)
@@ -1354,9 +1345,9 @@ def keygen(device, params, cs, fixed, copies, mapping=None, fixed_montgomery=Fal
     l_blind_poly = lagrange_poly(list(range(n - bf, n)))
 
     def active_row(l_last, l_blind, size):
-        tmp = D.eval_op(2, D.empty(size), l_last, l_blind)                     # H2_OP_SUM
-        one = D.eval_op(8, D.empty(size), c=1)                                 # H2_OP_CONSTANT
-        return D.eval_op(4, one, one, tmp)                                     # H2_OP_SUB
+        tmp = D.eval_op(OP_SUM, D.empty(size), l_last, l_blind)
+        one = D.eval_op(OP_CONSTANT, D.empty(size), c=1)
+        return D.eval_op(OP_SUB, one, one, tmp)
 
     def coset_tables(j):
         nf, ns = len(pk.fixed_polys), len(pk.sigma_polys)
@@ -1833,6 +1824,88 @@ def create_proof_from_witness(device, params, pk, witness, rng, use_gwc=True, ti
                             strict_rationals=strict_rationals)
 
 
+class _Lookup:
+    """one lookup of one circuit instance (logup/prover.rs): what its phases hand on"""
+
+    def __init__(self, table, inputs):
+        self.table = table                  # theta-compressed table column; None once the grand sums are committed
+        self.inputs = inputs                # per input set: its theta-compressed columns; None once the grand sums are committed
+        self.m = None                       # the multiplicities: Lagrange values, coefficients from the end of the grand-sum phase
+        self.m_bits = None                  # what log2(rows x inputs) allows m
+        self.m_usable_bits = None           # the measured width of the largest count (None: not measured)
+        self.inv_inputs = None              # per input set [1 / (beta + f_i)]: only between the batch inversion and the grand sums
+        self.inv_table = None               # 1 / (beta + t): only between the batch inversion and the grand sums
+        self.z = []                         # grand-sum columns: Lagrange values, coefficients from the end of the grand-sum phase
+
+
+class _Circuit:
+    """one circuit instance of a proof: its columns as the phases leave them"""
+
+    def __init__(self, instance, instance_polys):
+        self.instance, self.instance_polys = instance, instance_polys
+        self.advice = None                  # blinded Lagrange columns: from the advice phase; None once the quotient has the coefficients
+        self.advice_polys = None            # from the quotient phase on
+        self.advice_extended = None         # extended-domain values made on the side stream (small proofs), else None
+        self.lookups = []                   # [_Lookup]
+        self.shuffles = []                  # per group [(compressed input, compressed shuffle)]; None once the products are committed
+        self.nums = self.inv = None         # numerators / the batch-inverted buffer: only inside the grand-product phase
+        self.shuffle_inv = None             # per shuffle group its slot of `inv`: only inside the grand-product phase
+        self.z = []                         # permutation products: Lagrange values, coefficients from the end of that phase
+        self.shuffle_z = []                 # shuffle products: likewise
+
+
+class _Proof:
+    """what the phases of create_proof_ext share"""
+
+    def __init__(self, device, params, pk, rng, timings):
+        D = device
+        self.D, self.L, self.params, self.pk, self.cs, self.dom = D, D.L, params, pk, pk.cs, pk.domain
+        self.n, self.bf = self.dom.n, self.cs.blinding_factors()
+        self.last_rot, self.usable = -(self.bf + 1), self.n - (self.bf + 1)
+        self.chunk = self.cs.degree() - 2                       # permutation columns per product
+        self.nsets = (len(self.cs.perm_columns) + self.chunk - 1) // self.chunk
+        self.lo, self.hi = D.row_range(self.n)                  # the rows this rank computes in the phases dealt by rows
+        # The blinding rows are 16-bit values whatever the column holds (prover.rs:281-289), so the bound the reference
+        # computes over the whole column is never below 16 bits -- a column of booleans or of a few tiny values then runs
+        # as ONE window of 2^16 buckets with everything in its first partition.  A commitment is a sum: the usable rows
+        # are committed under THEIR bound (the narrow-column shapes of the MSM) and the bf + 1 blinding rows as one more
+        # (fused, few-point) MSM per group; the two points are added (_commit_lagrange_with_tail).
+        self.split_tail = not (D.group_size > 1 or D.force_collective) and self.usable >= (1 << 12)
+        self.transcript, self.rng = Blake2bWrite(), rng
+        self.theta = self.beta = self.gamma = self.y = self.x = None   # challenges, as they are squeezed
+        self.coset_tabs = pk.coset                              # the key's coset tables, or those built for a multi-instance proof
+        self.circuits = []                                      # [_Circuit], from the instance phase on
+        self.random_poly = self.random_commitment = None        # from the advice phase on
+        self.whole_advice_rows = None       # several ranks: every rank holds every row of the advice columns (advice phase on)
+        self.side_parts = []                # advice groups transformed on the side stream: advice phase -> _begin_advice_transforms
+        self.side_intt = None               # (coefficients, extended or None, event): _begin_advice_transforms -> quotient
+        self.advice_coeffs = self.advice_arrival = None         # several ranks: _begin_advice_transforms -> quotient
+        self.z_arrival = self.m_arrival = None                  # several ranks: grand products -> quotient
+        self.y_step = None                                      # y^(terms per circuit): inside the quotient phase
+        self.timings, self.marks = timings, [("start", time.perf_counter())]
+        self.host_trace = [] if os.environ.get("H2_PROVER_HOST_TRACE") else None
+
+    def htrace(self, name):                   # host-side timestamps without any synchronisation (H2_PROVER_HOST_TRACE=1)
+        if self.host_trace is not None:
+            self.host_trace.append((name, time.perf_counter()))
+
+    def mark(self, name):
+        D = self.D
+        self.htrace("mark " + name)
+        if self.timings is not None:
+            D.sync()
+            self.marks.append((name, time.perf_counter()))
+            if D.group_size > 1:
+                from . import parallel as _par
+
+                _par.comm_trace_phase(name)
+        if TRACE_TRANSCRIPT:                 # where two runs (or two ranks) of one proof part ways: the transcript after a phase
+            import sys
+
+            sys.stderr.write("h2 trace: rank %d after %s: %s (%d bytes)\n" % (
+                D.group_rank, name, hashlib.sha256(bytes(self.transcript.writer)).hexdigest()[:12], len(self.transcript.writer)))
+
+
 def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, instances=(), montgomery=False,
                      first_unassigned=None, range_checks_on_device=False, strict_rationals=False):
     """plonk/prover.rs:206-850.  advice: list of (n, 4) u64 columns, canonical integers (or Montgomery residues with
@@ -1859,101 +1932,126 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
     `range_checks_on_device`: host columns too go up first and are completed there by one call per circuit instance, followed
     by one download of its status -- the caller's arrays are not written and the host does no per-row work (DESIGN.md,
     "Completing range-check witnesses", has the measured proof times).  A circuit instance with a range of 2^24 values or
-    more, which the device refuses, is completed on the host instead, on copies of its columns."""
-    import time
+    more, which the device refuses, is completed on the host instead, on copies of its columns.
 
-    D, L = device, device.L
-    cs, dom = pk.cs, pk.domain
-    n, bf, ek = dom.n, cs.blinding_factors(), dom.extended_k
-    en = dom.extended_n
-    last_rot = -(bf + 1)
-    usable = n - (bf + 1)
-    marks = [("start", time.perf_counter())]
-
+    A proof that raises (a witness that does not satisfy a lookup, say) releases what it retained on the device."""
+    D = device
+    ps = _Proof(D, params, pk, rng, timings)
+    transcript = ps.transcript
     if timings is not None and D.group_size > 1:
         from . import parallel as _par
 
         _par.comm_trace_begin()              # this (untimed) proof records what its collectives cost, phase by phase
-
-    _host_trace = [] if os.environ.get("H2_PROVER_HOST_TRACE") else None
-
-    def htrace(name):                         # host-side timestamps without any synchronisation (H2_PROVER_HOST_TRACE=1)
-        if _host_trace is not None:
-            _host_trace.append((name, time.perf_counter()))
-
-    def mark(name):
-        htrace("mark " + name)
-        if timings is not None:
-            D.sync()
-            marks.append((name, time.perf_counter()))
-            if D.group_size > 1:
-                _par.comm_trace_phase(name)
-        if TRACE_TRANSCRIPT:                 # where two runs (or two ranks) of one proof part ways: the transcript after a phase
-            import sys
-
-            sys.stderr.write("h2 trace: rank %d after %s: %s (%d bytes)\n" % (
-                D.group_rank, name, hashlib.sha256(bytes(transcript.writer)).hexdigest()[:12], len(transcript.writer)))
-
-    transcript = Blake2bWrite()
     transcript.common_scalar(pk.transcript_repr)
-    D.release_retained()                     # (a proof that raised half way left its registrations behind)
-    if D.group_size > 1:
-        rng = rng.shared(D.group)            # every rank of one proof draws the same blinding values
+    D.release_retained()                     # (a caller may have retained by hand)
+    try:
+        if D.group_size > 1:
+            ps.rng = rng.shared(D.group)      # every rank of one proof draws the same blinding values
+        advice_sets, instance_sets = _witness_sets(ps.cs, ps.n, advice, instances, montgomery, first_unassigned, device=D,
+                                                   range_checks_on_device=range_checks_on_device,
+                                                   strict_rationals=strict_rationals)
+        # The residency of the key was decided at keygen for ONE circuit instance; advice, product and lookup polynomials scale
+        # with the number of instances.  A key judged 'extended' whose multi-instance proof does not fit runs this proof by the
+        # coset route, from tables built on demand out of the key's coefficient forms (same bytes).
+        if len(advice_sets) > 1 and pk.coset is None and D.group_size <= 1 and getattr(pk, "coset_builder", None) is not None:
+            mode, keep_ = D.residency(ps.cs, ps.dom, len(advice_sets))
+            if mode == "cosets":
+                hit = pk.__dict__.get("_multi_coset")
+                if hit is None or hit.keep != keep_:
+                    hit = pk._multi_coset = CosetTables(pk.coset_builder, range(ps.dom.quotient_poly_degree), keep_)
+                ps.coset_tabs = hit
+        _commit_instances(ps, instance_sets)
+        _commit_advice(ps, advice_sets, montgomery)
+        ps.mark("advice commit")
+        ps.theta = transcript.squeeze_challenge_scalar()
+        _begin_advice_transforms(ps)
+        _lookup_multiplicities(ps)
+        ps.mark("lookups compress")
+        ps.beta = transcript.squeeze_challenge_scalar()
+        ps.gamma = transcript.squeeze_challenge_scalar()
+        _grand_products(ps)
+        ps.mark("permutation")
+        ps.htrace("before random_commitment.result")
+        transcript.write_point(ps.random_commitment.result())
+        ps.y = transcript.squeeze_challenge_scalar()
+        ps.htrace("y squeezed")
+        pieces = _quotient(ps)
+        ps.mark("vanishing transforms")
+        for P in D.msm_batch(pieces, params.g, ps.n, 254):
+            transcript.write_point(P)
+        ps.x = transcript.squeeze_challenge_scalar()
+        ps.mark("vanishing construct")
+        h_poly, evals = _evaluations(ps, pieces)
+        ps.mark("evaluations")
+        queries, polys = _multiopen_queries(ps, h_poly, evals)
+        (_gwc if use_gwc else _shplonk)(D, params, transcript, queries, polys, ps.n)
+    finally:
+        D.release_retained()                 # also of a proof that raised half way: its vectors are about to be freed
+    ps.mark("multiopen")
+    if ps.host_trace:
+        import sys
 
-    def commit_lagrange_with_tail(cols_, bits_, split_tail):
-        """commit_lagrange of columns whose USABLE rows are bounded by bits_[i] and whose bf + 1 blinding rows are 16-bit
-        values (advice columns, the lookups' multiplicities).  `split_tail`: a column whose usable rows are narrower than the
-        blinding rows (and large enough for the narrow shapes of the MSM to matter) is committed as two sums -- the usable
-        rows under THEIR bound, the blinding rows as one more (fused, few-point) MSM -- and the two points are added; the
-        others are committed whole, under the bound of the whole column."""
-        narrow_ = [i for i, b in enumerate(bits_) if split_tail and b <= 12 and n >= (1 << 20)]
-        whole_ = [i for i in range(len(cols_)) if i not in narrow_]
-        points_ = [None] * len(cols_)
-        if whole_:
-            wb = [max(bits_[i], 16) if split_tail else bits_[i] for i in whole_]
-            for i, P in zip(whole_, D.msm_batch([cols_[i] for i in whole_], params.g_lagrange, n, wb)):
-                points_[i] = P
-        if narrow_:
-            main_ = D.msm_batch([cols_[i] for i in narrow_], params.g_lagrange, usable, [bits_[i] for i in narrow_])
-            tail_ = D.msm_batch([cols_[i][usable:] for i in narrow_], params.g_lagrange[usable:], n - usable, 16)
-            for i, a_, b_ in zip(narrow_, main_, tail_):
-                points_[i] = g1_add_affine(a_, b_)
-        return points_
+        base = ps.host_trace[0][1]
+        sys.stderr.write("host trace (ms): " + ", ".join("%s %.2f" % (nm, (t - base) * 1e3) for nm, t in ps.host_trace) + "\n")
+    if timings is not None:
+        for (_, t0), (name, t1) in zip(ps.marks, ps.marks[1:]):
+            timings[name] = timings.get(name, 0.0) + (t1 - t0)
+        if D.group_size > 1:
+            # per phase: seconds / bytes / calls of this rank's collectives (parallel.COMM_TRACE), next to `timings`
+            D.last_comm = _par.comm_trace_end()
+    return transcript.finalize()
 
-    advice_sets, instance_sets = _witness_sets(cs, n, advice, instances, montgomery, first_unassigned, device=D,
-                                               range_checks_on_device=range_checks_on_device, strict_rationals=strict_rationals)
-    ncirc, nadv = len(advice_sets), len(advice_sets[0])
+
+def _instance_columns(D, cs, n, usable, inst):
+    """the instance columns of one circuit instance on the device, zero-padded (prover.rs:85-162)"""
+    if len(inst) != cs.num_instance:
+        raise ValueError("InvalidInstances")
+    cols = []
+    for vals in inst:
+        if len(vals) > usable:
+            raise ValueError("InstanceTooLarge")
+        t = D.zeros(n)
+        D.set_rows(t, 0, list(vals))
+        cols.append(t)
+    return cols
+
+
+def _commit_instances(ps, instance_sets):
+    """instance columns (prover.rs:85-162): zero-padded, committed, hashed but not written"""
+    D = ps.D
+    dev_sets = [_instance_columns(D, ps.cs, ps.n, ps.usable, inst) for inst in instance_sets]
+    for P in D.msm_batch([t for cols in dev_sets for t in cols], ps.params.g_lagrange, ps.n, 254):
+        ps.transcript.common_point(P)
+    ps.circuits = [_Circuit(cols, [D.intt(D.clone(t), ps.dom) for t in cols]) for cols in dev_sets]
+
+
+def _commit_lagrange_with_tail(ps, cols_, bits_):
+    """commit_lagrange of columns whose USABLE rows are bounded by bits_[i] and whose bf + 1 blinding rows are 16-bit
+    values (advice columns, the lookups' multiplicities).  Under `ps.split_tail` a column whose usable rows are narrower than the
+    blinding rows (and large enough for the narrow shapes of the MSM to matter) is committed as two sums -- the usable
+    rows under THEIR bound, the blinding rows as one more (fused, few-point) MSM -- and the two points are added; the
+    others are committed whole, under the bound of the whole column."""
+    D, n, usable, bases, split_tail = ps.D, ps.n, ps.usable, ps.params.g_lagrange, ps.split_tail
+    narrow_ = [i for i, b in enumerate(bits_) if split_tail and b <= 12 and n >= (1 << 20)]
+    whole_ = [i for i in range(len(cols_)) if i not in narrow_]
+    points_ = [None] * len(cols_)
+    if whole_:
+        wb = [max(bits_[i], 16) if split_tail else bits_[i] for i in whole_]
+        for i, P in zip(whole_, D.msm_batch([cols_[i] for i in whole_], bases, n, wb)):
+            points_[i] = P
+    if narrow_:
+        main_ = D.msm_batch([cols_[i] for i in narrow_], bases, usable, [bits_[i] for i in narrow_])
+        tail_ = D.msm_batch([cols_[i][usable:] for i in narrow_], bases[usable:], n - usable, 16)
+        for i, a_, b_ in zip(narrow_, main_, tail_):
+            points_[i] = g1_add_affine(a_, b_)
+    return points_
+
+
+def _commit_advice(ps, advice_sets, montgomery):
+    """advice columns: blinding rows, bounded commitments (prover.rs:255-312); the random polynomial next to them"""
+    D, L, cs, dom, n, bf, usable, rng, transcript = ps.D, ps.L, ps.cs, ps.dom, ps.n, ps.bf, ps.usable, ps.rng, ps.transcript
+    nadv = len(advice_sets[0])
     advice = [col for a in advice_sets for col in a]          # circuit-major: the order every phase walks them in
-    # The residency of the key was decided at keygen for ONE circuit instance; advice, product and lookup polynomials scale
-    # with the number of instances.  A key judged 'extended' whose multi-instance proof does not fit runs this proof by the
-    # coset route, from tables built on demand out of the key's coefficient forms (same bytes).
-    coset_tabs = pk.coset
-    if ncirc > 1 and coset_tabs is None and D.group_size <= 1 and getattr(pk, "coset_builder", None) is not None:
-        mode, keep_ = D.residency(cs, dom, ncirc)
-        if mode == "cosets":
-            hit = pk.__dict__.get("_multi_coset")
-            if hit is None or hit.keep != keep_:
-                hit = pk._multi_coset = CosetTables(pk.coset_builder, range(dom.quotient_poly_degree), keep_)
-            coset_tabs = hit
-
-    # ---- instance columns (prover.rs:85-162): zero-padded, committed, hashed but not written -------------------
-    instance_dev_sets = []
-    for inst in instance_sets:
-        if len(inst) != cs.num_instance:
-            raise ValueError("InvalidInstances")
-        cols_i = []
-        for vals in inst:
-            if len(vals) > usable:
-                raise ValueError("InstanceTooLarge")
-            t = D.zeros(n)
-            D.set_rows(t, 0, list(vals))
-            cols_i.append(t)
-        instance_dev_sets.append(cols_i)
-    for P in D.msm_batch([t for cols_i in instance_dev_sets for t in cols_i], params.g_lagrange, n, 254):
-        transcript.common_point(P)
-    instance_polys_sets = [[D.intt(D.clone(t), dom) for t in cols_i] for cols_i in instance_dev_sets]
-
-    # ---- advice columns: blinding rows, bounded commitments (prover.rs:255-312) ----------------------------
     # Every column is queued for upload on the copy stream first (DMA when it lives in pinned memory); the columns are
     # then blinded, measured (per-column max_bits, as the reference) and committed in small groups -- one pipelined
     # batch per group -- while the later groups are still in flight.
@@ -1965,7 +2063,7 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
     # theta-compressions of lookups and shuffles (replicated).  Without them (mini-PLONK) a rank keeps its own rows -- all the
     # permutation terms of its range read -- and a column's rows follow their OWNER for the inverse transform
     # (Device.intt_columns_begin with complete = False): 1 / P of the all-gather's traffic.
-    whole_advice_rows = bool(cs.lookups or cs.shuffles) or not sharded_upload
+    whole_advice_rows = ps.whole_advice_rows = bool(cs.lookups or cs.shuffles) or not sharded_upload
     lo_r, hi_r = 0, n
     if sharded_upload:
         from .parallel import allgather_rows, allreduce_max, msm_split_range
@@ -1982,12 +2080,12 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
         # every column of a wide witness in the copy queue the FIRST group's commitment returned only when the LAST column
         # had crossed PCIe (k = 22, 64 compact columns: the GPU idle for 34 of the phase's 125 ms; tools/experiments/busy.sh)
         uploads = [None] * len(advice)
-    uploads_queued = [len(uploads) if sharded_upload else 0]
+    queued = len(uploads) if sharded_upload else 0
 
-    def queue_uploads(upto):
-        while uploads_queued[0] < min(upto, len(uploads)):
-            uploads[uploads_queued[0]] = D.upload_async(advice[uploads_queued[0]])
-            uploads_queued[0] += 1
+    def queue_uploads(queued, upto):
+        for i in range(queued, min(upto, len(uploads))):
+            uploads[i] = D.upload_async(advice[i])
+        return max(queued, min(upto, len(uploads)))
 
     # columns are blinded, measured and committed in groups while later uploads are still in flight; small witnesses
     # (<= 256 MiB: already on the device by the time the random polynomial is committed) go as one group -- one
@@ -2004,7 +2102,7 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
         group = int(os.environ["H2_ADVICE_GROUP"])
     group = max(group, 1)
     ahead = max(1, int(os.environ.get("H2_ADVICE_AHEAD", "2"))) * group
-    queue_uploads(len(uploads) if len(uploads) <= group else group + ahead)
+    queued = queue_uploads(queued, len(uploads) if len(uploads) <= group else group + ahead)
     # The vanishing argument's random polynomial (vanishing/prover.rs:40-67) and its commitment depend on nothing the
     # transcript has hashed: generated and committed NOW, while the witness columns cross PCIe on the copy stream (k = 24:
     # a 22 ms MSM under a 29 ms transfer) -- on a side stream, so that the columns that have already arrived are
@@ -2012,11 +2110,11 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
     # written where the protocol puts it, after the z's.
     # (Small witnesses too: folding it into the advice columns' batch instead was measured slower, k = 18 lookup circuit
     # 28.6 -> 30.2 ms -- the early MSM runs under the host's preparation of the blinding rows.)
-    htrace("uploads queued")
-    random_poly = D.empty(n)
-    check(L.h2_dev_random_fr(rng.random_poly_key(), n, random_poly.data_ptr(), D.stream), "h2_dev_random_fr")
-    random_commitment = D.msm_async(random_poly, params.g, n)   # collected where the transcript needs it
-    D.retain([random_poly])
+    ps.htrace("uploads queued")
+    ps.random_poly = D.empty(n)
+    check(L.h2_dev_random_fr(rng.random_poly_key(), n, ps.random_poly.data_ptr(), D.stream), "h2_dev_random_fr")
+    ps.random_commitment = D.msm_async(ps.random_poly, ps.params.g, n)   # collected where the transcript needs it
+    D.retain([ps.random_poly])
     # the blinding rows of every column (drawn column by column, as the reference does) go up in one copy
     blind = np.zeros((max(len(uploads), 1), n - usable, 4), dtype=np.int64)
     for ci in range(len(uploads)):
@@ -2031,11 +2129,9 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
     # (profiles/r6_side_groups_ab.txt): wide k = 22 447 -> 352 ms (344 from a compact witness, was 369), wide k = 20 122 -> 113,
     # mini-PLONK k = 24 185 -> 177, k = 22 51.5 -> 50.6.  A witness that fits ONE group keeps the whole-phase form further down.
     side_groups = (os.environ.get("H2_SIDE_GROUPS", "1") != "0" and os.environ.get("H2_SIDE_INTT", "1") != "0" and
-                   not sharded_upload and D.group_size <= 1 and not D.force_collective and len(uploads) > group and
-                   hasattr(D, "intt_on_side_stream"))
-    side_parts = []
+                   not sharded_upload and D.group_size <= 1 and not D.force_collective and len(uploads) > group)
     for g0 in range(0, len(uploads), group):
-        queue_uploads(g0 + group + ahead)
+        queued = queue_uploads(queued, g0 + group + ahead)
         cols_ = []
         for ci, (t, arrived) in enumerate(uploads[g0:g0 + group], start=g0):
             if arrived is not None:
@@ -2046,122 +2142,122 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
                 with D.torch.cuda.stream(D.tstream):
                     t[usable:] = blind_dev[ci]
             cols_.append(t)
-        # The blinding rows are 16-bit values whatever the column holds (prover.rs:281-289), so the bound the reference
-        # computes over the whole column is never below 16 bits -- a column of booleans or of a few tiny values then runs
-        # as ONE window of 2^16 buckets with everything in its first partition.  A commitment is a sum: the usable rows
-        # are committed under THEIR bound (the narrow-column shapes of the MSM) and the bf + 1 blinding rows as one more
-        # (fused, few-point) MSM per group; the two points are added.
-        split_tail = not sharded_upload and not (D.group_size > 1 or D.force_collective) and usable >= (1 << 12)
-        m_rows = usable if split_tail else hi_r - lo_r
-        htrace("advice group %d queued" % g0)
+        m_rows = usable if ps.split_tail else hi_r - lo_r
+        ps.htrace("advice group %d queued" % g0)
         bits_ = D.max_scalar_bits_many([t[lo_r:lo_r + m_rows] for t in cols_], m_rows)
-        htrace("advice group %d bits" % g0)
+        ps.htrace("advice group %d bits" % g0)
         if sharded_upload:
             bits_ = allreduce_max(bits_, group=D.group, device=D.dev)       # find_max_scalar_bits over the whole column
         bits_ = [max(b, 1) for b in bits_]
         for t in cols_:
             check(L.h2_dev_batch_mont(t[lo_r:hi_r].data_ptr(), hi_r - lo_r, D.stream), "h2_dev_batch_mont")
-        # ... for the columns whose usable rows are narrower than the blinding rows (and large enough for the narrow shapes
-        # to matter): the others are committed whole, under the bound of the whole column
-        for P in commit_lagrange_with_tail(cols_, bits_, split_tail):
+        for P in _commit_lagrange_with_tail(ps, cols_, bits_):
             transcript.write_point(P)
-        htrace("advice group %d committed" % g0)
+        ps.htrace("advice group %d committed" % g0)
         if sharded_upload and whole_advice_rows:
             for t in cols_:
                 allgather_rows(t, lo_r, hi_r, group=D.group, stream=D.tstream)
         if side_groups:
-            side_parts.append(D.intt_on_side_stream(cols_, dom, extend=D.coset_plan(dom) is None and coset_tabs is None))
+            ps.side_parts.append(D.intt_on_side_stream(cols_, dom, extend=D.coset_plan(dom) is None and ps.coset_tabs is None))
         advice_dev += cols_
-    del blind_dev
-    del uploads
-    mark("advice commit")
-    theta = transcript.squeeze_challenge_scalar()
-    # per-circuit state: every later phase walks `circuits` in order
-    circuits = [{"advice": advice_dev[ci * nadv:(ci + 1) * nadv], "instance": instance_dev_sets[ci],
-                 "instance_polys": instance_polys_sets[ci]} for ci in range(ncirc)]
+    for ci, C in enumerate(ps.circuits):
+        C.advice = advice_dev[ci * nadv:(ci + 1) * nadv]
+
+
+def _begin_advice_transforms(ps):
+    D, dom = ps.D, ps.dom
+    advice_dev = [t for C in ps.circuits for t in C.advice]
     # the advice columns are final: their coefficient forms (needed from the quotient on) are computed on the side stream
     # while the lookup / permutation phases run on the compute stream -- up to k = 20, where those phases are chains of
     # small latency-bound kernels (k = 18 lookup circuit 28.9 -> 27.6 ms); at k = 22 / 24 they fill the chip themselves and
     # the transforms only take their time away (60.1 vs 60.2 ms, 210 vs 211)
-    side_intt = None
-    if side_parts:
+    if ps.side_parts:
         # (group by group above; the events of one stream are ordered: the last one covers them all)
-        exts_ = [e for _, ext_g, _ in side_parts for e in (ext_g or [])]
-        side_intt = ([p_ for polys_g, _, _ in side_parts for p_ in polys_g],
-                     exts_ if all(ext_g is not None for _, ext_g, _ in side_parts) else None, side_parts[-1][2])
+        exts_ = [e for _, ext_g, _ in ps.side_parts for e in (ext_g or [])]
+        ps.side_intt = ([p_ for polys_g, _, _ in ps.side_parts for p_ in polys_g],
+                       exts_ if all(ext_g is not None for _, ext_g, _ in ps.side_parts) else None, ps.side_parts[-1][2])
+        ps.side_parts = []
     elif (os.environ.get("H2_SIDE_INTT", "1") != "0" and dom.k <= int(os.environ.get("H2_SIDE_INTT_MAX_K", "20"))
             and D.group_size <= 1 and not D.force_collective):
-        side_intt = D.intt_on_side_stream(advice_dev, dom, extend=D.coset_plan(dom) is None and coset_tabs is None)
+        ps.side_intt = D.intt_on_side_stream(advice_dev, dom, extend=D.coset_plan(dom) is None and ps.coset_tabs is None)
     # one proof over several ranks: the advice columns' inverse transforms are dealt by column now (a rank transforms every
     # P-th column) and the coefficient vectors cross xGMI under the lookup / permutation phases that follow
-    advice_arrival = None
     if D.group_size > 1:
-        advice_coeffs, advice_arrival = D.intt_columns_begin(advice_dev, dom, complete=whole_advice_rows, keep=True)
+        ps.advice_coeffs, ps.advice_arrival = D.intt_columns_begin(advice_dev, dom, complete=ps.whole_advice_rows, keep=True)
 
-    # ---- lookups: theta-compressed inputs / table, multiplicities (logup/prover.rs:63-240) ---------------------
+
+def _compress_of(ps, C, program, rows=None):
+    return _compress(ps.D, ps.dom, program, ps.theta, ps.pk.fixed_values, C.advice, C.instance, rows)
+
+
+def _lookup_multiplicities(ps):
+    """lookups: theta-compressed inputs / table, multiplicities (logup/prover.rs:63-240); the shuffles' compressed expressions"""
+    D, L, pk, n, usable, rng = ps.D, ps.L, ps.pk, ps.n, ps.usable, ps.rng
     # One proof over several ranks with the rows dealt (Device.row_range): the compressed INPUT expressions are needed on this
     # rank's rows only (the grand sums below read them there), and the multiplicities are integer counts -- an RCCL reduction:
     # every rank counts the hits of its own input rows in the (whole, replicated) compressed table, the counters are summed by
     # ONE all-reduce per lookup and become field elements afterwards.  The shuffles' expressions likewise: rows only.
-    lo_c, hi_c = D.row_range(n)
+    lo_c, hi_c = ps.lo, ps.hi
     rows_c = None if (lo_c, hi_c) == (0, n) else (lo_c, hi_c - lo_c)
-    for C in circuits:
-        def compress(program, C=C, rows=None):
-            return _compress(D, dom, program, theta, pk.fixed_values, C["advice"], C["instance"], rows)
-
-        C["lookups"] = []
+    for C in ps.circuits:
         for table_prog, set_progs in pk.lookup_programs:
-            st = {"table": compress(table_prog), "inputs": [[compress(pr, rows=rows_c) for pr in progs] for progs in set_progs]}
-            flat = [c for cols_ in st["inputs"] for c in cols_]
+            st = _Lookup(_compress_of(ps, C, table_prog), [[_compress_of(ps, C, pr, rows_c) for pr in progs] for progs in set_progs])
+            flat = [c for cols_ in st.inputs for c in cols_]
             m = D.empty(n)
             nbytes = L.h2_logup_scratch_bytes(n)
             ptrs = (_vp * len(flat))(*[c.data_ptr() for c in flat])
-            m_usable_bits = None
+            # (hasattr: OracleLib, the CPU library of tests/oracle_prover.py, has only the plain h2_dev_logup_multiplicity)
             if rows_c is None and hasattr(L, "h2_dev_logup_multiplicity_bits") and os.environ.get("H2_M_BITS", "1") != "0":
                 # ... and the width of the largest multiplicity: a range lookup's counts are a few bits wide, nowhere near
                 # the log2(rows x inputs) their sum allows -- m's commitment then takes the narrow-column shapes of the MSM
                 got_bits = ctypes.c_uint32(0)
-                check(L.h2_dev_logup_multiplicity_bits(st["table"].data_ptr(), ptrs, len(flat), usable, n, m.data_ptr(),
+                check(L.h2_dev_logup_multiplicity_bits(st.table.data_ptr(), ptrs, len(flat), usable, n, m.data_ptr(),
                                                        D.scratch(nbytes).data_ptr(), nbytes, ctypes.byref(got_bits), D.stream),
                       "h2_dev_logup_multiplicity_bits")
-                m_usable_bits = max(int(got_bits.value), 1)
+                st.m_usable_bits = max(int(got_bits.value), 1)
             elif rows_c is None:
-                check(L.h2_dev_logup_multiplicity(st["table"].data_ptr(), ptrs, len(flat), usable, n, m.data_ptr(),
+                check(L.h2_dev_logup_multiplicity(st.table.data_ptr(), ptrs, len(flat), usable, n, m.data_ptr(),
                                                   D.scratch(nbytes).data_ptr(), nbytes, D.stream), "h2_dev_logup_multiplicity")
             else:
                 from .parallel import allreduce_counts
 
                 with D.torch.cuda.stream(D.tstream):
                     counts = D.torch.empty(n + 1, dtype=D.torch.int32, device=D.dev)
-                check(L.h2_dev_logup_counts(st["table"].data_ptr(), ptrs, len(flat), usable, n, lo_c, hi_c, counts.data_ptr(),
+                check(L.h2_dev_logup_counts(st.table.data_ptr(), ptrs, len(flat), usable, n, lo_c, hi_c, counts.data_ptr(),
                                             D.scratch(nbytes).data_ptr(), nbytes, D.stream), "h2_dev_logup_counts")
                 missing = allreduce_counts(counts, group=D.group, stream=D.tstream)
                 if missing:
                     raise ValueError("logup: %d input value(s) are missing from the table" % missing)
                 check(L.h2_dev_logup_emit(counts.data_ptr(), usable, n, m.data_ptr(), D.stream), "h2_dev_logup_emit")
             D.set_rows(m, usable, [rng.u16() for _ in range(usable, n)])
-            st["m"], st["m_bits"], st["m_usable_bits"] = m, max(16, (usable * len(flat)).bit_length()), m_usable_bits
-            C["lookups"].append(st)
+            st.m, st.m_bits = m, max(16, (usable * len(flat)).bit_length())
+            C.lookups.append(st)
         # ---- shuffles: compressed expressions (shuffle/prover.rs:40-80) ------------------------------------------
-        C["shuffles"] = [[(compress(ip, rows=rows_c), compress(sp, rows=rows_c)) for ip, sp in group] for group in pk.shuffle_programs]
-    all_lookups = [st for C in circuits for st in C["lookups"]]
-    if all_lookups and all(st["m_usable_bits"] is not None for st in all_lookups):
-        split_m = not (D.group_size > 1 or D.force_collective) and usable >= (1 << 12)
+        C.shuffles = [[(_compress_of(ps, C, ip, rows_c), _compress_of(ps, C, sp, rows_c)) for ip, sp in group]
+                      for group in pk.shuffle_programs]
+    all_lookups = [st for C in ps.circuits for st in C.lookups]
+    if all_lookups and all(st.m_usable_bits is not None for st in all_lookups):
         # (committed whole, a column's bound covers its 16-bit blinding rows too)
-        m_bits_ = [st["m_usable_bits"] if split_m else max(st["m_usable_bits"], 16) for st in all_lookups]
-        for P in commit_lagrange_with_tail([st["m"] for st in all_lookups], m_bits_, split_m):
-            transcript.write_point(P)
+        m_bits_ = [st.m_usable_bits if ps.split_tail else max(st.m_usable_bits, 16) for st in all_lookups]
+        for P in _commit_lagrange_with_tail(ps, [st.m for st in all_lookups], m_bits_):
+            ps.transcript.write_point(P)
     elif all_lookups:
-        for P in D.msm_batch([st["m"] for st in all_lookups], params.g_lagrange, n, max(st["m_bits"] for st in all_lookups)):
-            transcript.write_point(P)
-    mark("lookups compress")
-    beta = transcript.squeeze_challenge_scalar()
-    gamma = transcript.squeeze_challenge_scalar()
+        for P in D.msm_batch([st.m for st in all_lookups], ps.params.g_lagrange, n, max(st.m_bits for st in all_lookups)):
+            ps.transcript.write_point(P)
 
-    # ---- permutation grand products (permutation/prover.rs:47-165) -----------------------------------
-    chunk = cs.degree() - 2
+
+def _blind_product_column(ps, blinding, z):
+    """the bf blinding rows of a product / sum column (prover.rs:446-465, :512-530): drawn now, written with the others"""
+    blinding.append((z, ps.n - ps.bf, [ps.rng.fr() for _ in range(ps.bf)]))
+    return z
+
+
+def _grand_products(ps):
+    """permutation grand products (permutation/prover.rs:47-165), lookup grand sums, shuffle products: the columns, their
+    commitments and the start of their inverse transforms"""
+    D, L, pk, cs, dom, n, usable, params = ps.D, ps.L, ps.pk, ps.cs, ps.dom, ps.n, ps.usable, ps.params
+    beta, gamma, chunk, nsets, circuits = ps.beta, ps.gamma, ps.chunk, ps.nsets, ps.circuits
     cols = cs.perm_columns
-    nsets = (len(cols) + chunk - 1) // chunk
     # Everything that has to be inverted before the grand products / sums can run -- the permutation denominators of
     # every set, (beta + f) of every lookup input and table, the shuffle products -- depends only on beta and gamma: it
     # is laid out in ONE buffer (per circuit instance) and inverted by ONE batch inversion, so the inversion's serial
@@ -2170,26 +2266,26 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
     # products, the scans -- runs on this rank's rows [lo_s, hi_s) only (a prefix scan exchanges one field element per rank,
     # Device.prefix_scan); the range is exactly what the rank's share of the z commitments consumes, and the ranks complete
     # each other's z columns over xGMI before the inverse transforms (Device.gather_rows).
-    lo_s, hi_s = D.row_range(n)
+    lo_s, hi_s = ps.lo, ps.hi
     m_s = hi_s - lo_s
     rows = lambda t: t[lo_s:hi_s]  # noqa: E731
     omega_lo = pow(dom.omega, lo_s, R_MOD)
-    fused_perm = getattr(D, "permutation_product", None) if (lo_s, hi_s) == (0, n) else None
-    fused_lookup = getattr(D, "logup_grand_sum", None) if (lo_s, hi_s) == (0, n) else None
-    for C in circuits:
-        lookups, shuffles = C["lookups"], C["shuffles"]
-        colvals = {"advice": C["advice"], "fixed": pk.fixed_values, "instance": C["instance"]}
+    fused_perm = D.permutation_product if (lo_s, hi_s) == (0, n) else None
+    fused_lookup = D.logup_grand_sum if (lo_s, hi_s) == (0, n) else None
+    colvals = [{"advice": C.advice, "fixed": pk.fixed_values, "instance": C.instance} for C in circuits]
+    for C, vals in zip(circuits, colvals):
+        lookups, shuffles = C.lookups, C.shuffles
         # a device whose vectors live on the HOST makes one call per set instead (h2_permutation_product: terms, inversion,
         # product and scan without num / den crossing PCIe around every step): its sets take no slot here
         pslots = 0 if fused_perm else nsets
-        lslots = 0 if fused_lookup else sum(len(cols_in) for st in lookups for cols_in in st["inputs"]) + len(lookups)
+        lslots = 0 if fused_lookup else sum(len(cols_in) for st in lookups for cols_in in st.inputs) + len(lookups)
         slots = pslots + lslots + len(shuffles)
         nums = D.empty(max(pslots, 1) * m_s)
         inv = D.empty(max(slots, 1) * m_s)
         slot = lambda i, inv=inv: inv[i * m_s:(i + 1) * m_s]  # noqa: E731
         for k_, si in enumerate(range(0, len(cols) if pslots else 0, chunk)):
             for ci in range(si, min(si + chunk, len(cols))):
-                values = colvals[cols[ci][0]][cols[ci][1]]
+                values = vals[cols[ci][0]][cols[ci][1]]
                 check(L.h2_dev_permutation_terms(nums[k_ * m_s:].data_ptr(), slot(k_).data_ptr(), rows(values).data_ptr(),
                                                  rows(pk.sigma_values[ci]).data_ptr(), m_s, _fr(beta), _fr(gamma),
                                                  _fr(pow(DELTA, ci, R_MOD) * omega_lo), _fr(dom.omega), 1 if ci == si else 0,
@@ -2198,307 +2294,304 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
         for st in lookups:
             if fused_lookup:            # (host vectors: h2_logup_grand_sum inverts on the device, set by set, further down)
                 continue
-            st["inv_inputs"] = []
-            for cols_in in st["inputs"]:
-                st["inv_inputs"].append([])
+            st.inv_inputs = []
+            for cols_in in st.inputs:
+                st.inv_inputs.append([])
                 for col in cols_in:                                     # beta + f_i
-                    st["inv_inputs"][-1].append(D.eval_op(1, slot(at), rows(col), c=beta, size=m_s))          # H2_OP_SUM_C
+                    st.inv_inputs[-1].append(D.eval_op(OP_SUM_C, slot(at), rows(col), c=beta, size=m_s))
                     at += 1
-            st["inv_table"] = D.eval_op(1, slot(at), rows(st["table"]), c=beta, size=m_s)  # beta + t
+            st.inv_table = D.eval_op(OP_SUM_C, slot(at), rows(st.table), c=beta, size=m_s)  # beta + t
             at += 1
-        C["shuffle_inv"] = []
+        C.shuffle_inv = []
         for group in shuffles:                                          # prod_i (beta^(i+1) + shuffle_i)
             dst = slot(at)
             for i, (_, shf) in enumerate(group):
                 if i == 0:
-                    D.eval_op(1, dst, rows(shf), c=beta, size=m_s)
+                    D.eval_op(OP_SUM_C, dst, rows(shf), c=beta, size=m_s)
                 else:
-                    D.eval_op(6, dst, rows(shf), dst, c=pow(beta, i + 1, R_MOD), size=m_s)       # H2_OP_LCBETA: (l + c) * r
-            C["shuffle_inv"].append(dst)
+                    D.eval_op(OP_LCBETA, dst, rows(shf), dst, c=pow(beta, i + 1, R_MOD), size=m_s)       # (l + c) * r
+            C.shuffle_inv.append(dst)
             at += 1
         assert at == slots
         if slots:
             check(L.h2_dev_batch_invert(inv.data_ptr(), D.empty(slots * m_s).data_ptr(), slots * m_s, D.stream), "h2_dev_batch_invert")
         if pslots:
-            D.eval_op(3, nums, nums, inv[:nsets * m_s])                                     # H2_OP_MUL over all sets
-        C["nums"], C["inv"] = nums, inv
+            D.eval_op(OP_MUL, nums, nums, inv[:nsets * m_s])                                # over all sets
+        C.nums, C.inv = nums, inv
+    del nums, inv, slot
 
     # ---- permutation grand products (permutation/prover.rs:89-165), circuit by circuit -------------------------
     blinding = []         # (z, first blinding row, values): drawn in the reference's order, written in one copy below
-    for C in circuits:
-        C["z"], last_z = [], 1
-        colvals = {"advice": C["advice"], "fixed": pk.fixed_values, "instance": C["instance"]}
+    for C, vals in zip(circuits, colvals):
+        last_z = 1
         for k_ in range(nsets):
             if fused_perm:
                 cis = range(k_ * chunk, min((k_ + 1) * chunk, len(cols)))
-                z, last_z = fused_perm([colvals[cols[ci][0]][cols[ci][1]] for ci in cis], [pk.sigma_values[ci] for ci in cis], n,
+                z, last_z = fused_perm([vals[cols[ci][0]][cols[ci][1]] for ci in cis], [pk.sigma_values[ci] for ci in cis], n,
                                        beta, gamma, pow(DELTA, k_ * chunk, R_MOD), dom.omega, last_z, usable)
             else:
-                z, last_z = D.prefix_scan(C["nums"][k_ * m_s:(k_ + 1) * m_s], n, last_z, True, usable)
-            blinding.append((z, n - bf, [rng.fr() for _ in range(bf)]))
-            C["z"].append(z)
-        del C["nums"]
+                z, last_z = D.prefix_scan(C.nums[k_ * m_s:(k_ + 1) * m_s], n, last_z, True, usable)
+            C.z.append(_blind_product_column(ps, blinding, z))
+        C.nums = None
     num = D.empty(m_s)
     # ---- lookup grand sums (logup/prover.rs:243-415; blinding prover.rs:446-465) -------------------------------
     for C in circuits:
-        for st in C["lookups"]:
-            st["z"] = []
+        for st in C.lookups:
             last = 0
-            for si, cols_in in enumerate(st["inputs"] if fused_lookup else ()):
-                z, last = fused_lookup(cols_in, st["table"] if si == 0 else None, st["m"] if si == 0 else None, n, beta, last, usable)
-                blinding.append((z, n - bf, [rng.fr() for _ in range(bf)]))
-                st["z"].append(z)
-            for si, inverted in enumerate(() if fused_lookup else st["inv_inputs"]):
-                src = inverted[0]                                       # sum_i 1 / (beta + f_i)
-                for other in inverted[1:]:
-                    src = D.eval_op(2, num, src, other, size=m_s)       # H2_OP_SUM
-                if si == 0:                                             # - m / (beta + t)
-                    D.eval_op(3, st["inv_table"], st["inv_table"], rows(st["m"]), size=m_s)
-                    src = D.eval_op(4, num, src, st["inv_table"], size=m_s)       # H2_OP_SUB
-                z, last = D.prefix_scan(src, n, last, False, usable)
-                blinding.append((z, n - bf, [rng.fr() for _ in range(bf)]))
-                st["z"].append(z)
+            for si, cols_in in enumerate(st.inputs):
+                if fused_lookup:
+                    z, last = fused_lookup(cols_in, st.table if si == 0 else None, st.m if si == 0 else None, n, beta, last, usable)
+                else:
+                    src = st.inv_inputs[si][0]                              # sum_i 1 / (beta + f_i)
+                    for other in st.inv_inputs[si][1:]:
+                        src = D.eval_op(OP_SUM, num, src, other, size=m_s)
+                    if si == 0:                                             # - m / (beta + t)
+                        D.eval_op(OP_MUL, st.inv_table, st.inv_table, rows(st.m), size=m_s)
+                        src = D.eval_op(OP_SUB, num, src, st.inv_table, size=m_s)
+                    z, last = D.prefix_scan(src, n, last, False, usable)
+                st.z.append(_blind_product_column(ps, blinding, z))
             if last != 0:
                 raise ValueError("lookup grand sum does not return to zero")   # sanity-checks feature of the reference
-            if not fused_lookup:
-                del st["inv_inputs"], st["inv_table"]
+            st.inv_inputs = st.inv_table = None
     # ---- shuffle products (shuffle/prover.rs:82-150; blinding prover.rs:512-530) -------------------------------
     for C in circuits:
-        C["shuffle_z"] = []
-        for group, inverted in zip(C["shuffles"], C["shuffle_inv"]):
+        for group, inverted in zip(C.shuffles, C.shuffle_inv):
             for i, (inp, _) in enumerate(group):
-                D.eval_op(6, inverted, rows(inp), inverted, c=pow(beta, i + 1, R_MOD), size=m_s)
+                D.eval_op(OP_LCBETA, inverted, rows(inp), inverted, c=pow(beta, i + 1, R_MOD), size=m_s)
             z, closing = D.prefix_scan(inverted, n, 1, True, usable)
             if closing != 1:
                 raise ValueError("shuffle product does not return to one")
-            blinding.append((z, n - bf, [rng.fr() for _ in range(bf)]))
-            C["shuffle_z"].append(z)
-        del C["inv"], C["shuffle_inv"]
+            C.shuffle_z.append(_blind_product_column(ps, blinding, z))
+        C.inv = C.shuffle_inv = None
     del num
     D.set_rows_many(blinding)
     # commit_lagrange_and_ifft (poly/commitment.rs:144-197) for every z, in the transcript's order: the permutation
     # products of every circuit, then the lookup sums of every circuit, then the shuffle products (prover.rs:595-625)
-    all_z = ([z for C in circuits for z in C["z"]] + [z for C in circuits for st in C["lookups"] for z in st["z"]] +
-             [z for C in circuits for z in C["shuffle_z"]])
+    all_z = ([z for C in circuits for z in C.z] + [z for C in circuits for st in C.lookups for z in st.z] +
+             [z for C in circuits for z in C.shuffle_z])
     # (a device whose vectors live on the HOST does both in one call per column, sharing the one upload:
     # gpu_multiexp_bound_and_fft, arithmetic.rs:375-410)
-    commit_ifft = getattr(D, "commit_lagrange_and_ifft", None) if (lo_s, hi_s) == (0, n) and not D.force_collective else None
+    commit_ifft = D.commit_lagrange_and_ifft if (lo_s, hi_s) == (0, n) and not D.force_collective else None
     z_commitments = commit_ifft(all_z, params.g_lagrange, dom) if commit_ifft else D.msm_batch(all_z, params.g_lagrange, n, 254)
     for P in z_commitments:
-        transcript.write_point(P)
+        ps.transcript.write_point(P)
     # (one proof over several ranks: every rank computed its own rows of the product columns; a column's rows go to the
     # rank that transforms it, and the coefficient vectors travel while the advice columns are taken to their cosets)
-    z_arrival = None
+    # The product columns and the multiplicities are transformed in place, sixteen to a launch: coefficients from here on.
     if not commit_ifft:
-        _, z_arrival = D.intt_columns_begin(all_z, dom, complete=False)
-    _, m_arrival = D.intt_columns_begin([st["m"] for C in circuits for st in C["lookups"]], dom, complete=True)
+        _, ps.z_arrival = D.intt_columns_begin(all_z, dom, complete=False)
+    _, ps.m_arrival = D.intt_columns_begin([st.m for C in circuits for st in C.lookups], dom, complete=True)
     for C in circuits:
-        C["z_polys"] = C["z"]                                       # (transformed in place, sixteen to a launch)
-        for st in C["lookups"]:
-            st["z_polys"], st["m_poly"] = st["z"], st["m"]
-            del st["table"], st["inputs"]
-        C["shuffle_polys"] = C["shuffle_z"]
-        del C["shuffles"]
-    mark("permutation")
-    htrace("before random_commitment.result")
-    transcript.write_point(random_commitment.result())
-    y = transcript.squeeze_challenge_scalar()
-    htrace("y squeezed")
+        for st in C.lookups:
+            st.table = st.inputs = None
+        C.shuffles = None
 
-    # ---- h(X): advice to coefficient form, extended cosets, the fused evaluator --------------------------
-    if side_intt is not None:
-        polys_, ext_, done_ = side_intt
+
+def _circuit_polys(C):
+    """the coefficient vectors of one circuit instance that the quotient, the evaluations and the openings read, in the
+    evaluator's groups: advice, instance, permutation z, lookup z, lookup m, shuffle z"""
+    return [list(C.advice_polys), list(C.instance_polys), list(C.z), [t for st in C.lookups for t in st.z],
+            [st.m for st in C.lookups], list(C.shuffle_z)]
+
+
+def _evalh_desc(ps, tables, advice, instance, perm_z, lookup_z, lookup_m, shuffle_z, k_domain, zeta_, omega_, rows=None):
+    """the h2_evalh_desc of one circuit instance over one evaluation domain: `tables` has the key's vectors there and the
+    other lists this circuit's -- coefficient forms (h2_evaluate_h_coeff) or values on the domain (h2_dev_evaluate_h)"""
+    pk, g = ps.pk, ps.pk.graph
+    return ev.Builder().build(
+        k=ps.dom.k, extended_k=k_domain, blinding_factors=ps.bf, chunk_len=ps.chunk,
+        constants=np.array([fr_to_mont_limbs(c) for c in g.constants], dtype=np.uint64), rotations=g.rotations,
+        calculations=g.calculations, value_parts=pk.value_parts, lookups=pk.lookup_calcs, shuffles=pk.shuffle_calcs,
+        fixed=[t.data_ptr() for t in tables["fixed"]], advice=[t.data_ptr() for t in advice],
+        instance=[t.data_ptr() for t in instance],
+        l0=tables["l0"].data_ptr(), l_last=tables["l_last"].data_ptr(), l_active_row=tables["l_active_row"].data_ptr(),
+        perm_z=[t.data_ptr() for t in perm_z], perm_columns=[(_ANY[kd], i) for kd, i in ps.cs.perm_columns],
+        perm_sigma=[t.data_ptr() for t in tables["sigma"]],
+        lookup_z=[t.data_ptr() for t in lookup_z], lookup_m=[t.data_ptr() for t in lookup_m],
+        shuffle_z=[t.data_ptr() for t in shuffle_z],
+        y=fr_to_mont_limbs(ps.y), beta=fr_to_mont_limbs(ps.beta), gamma=fr_to_mont_limbs(ps.gamma), theta=fr_to_mont_limbs(ps.theta),
+        delta=fr_to_mont_limbs(DELTA), zeta=fr_to_mont_limbs(zeta_), extended_omega=fr_to_mont_limbs(omega_),
+        flags=0 if pk.evalh_stats else ev.EVALH_INTERPRET,
+        row_begin=rows[0] if rows is not None else 0, row_count=rows[1] if rows is not None else 0)
+
+
+def _quotient_numerator(ps, points_of, tables, k_domain, zeta_, omega_, size, rows=None, fused=None):
+    """the numerator of h over one evaluation domain, every circuit folded in.
+    `rows` = (first, count): only these rows of the domain are evaluated (and valid in the result).  `fused` (host
+    vectors, one circuit instance): the device's h2_quotient_poly_coeff -- the result is h(X) in COEFFICIENT form"""
+    total = None
+    lo_, cnt_ = rows if rows is not None else (0, size)
+    for C in ps.circuits:
+        h_c = _quotient_numerator_of(ps, C, points_of, tables, k_domain, zeta_, omega_, size, rows, fused)
+        if total is None:
+            total = h_c
+        else:                                                                               # l * c + r
+            ps.D.eval_op(OP_LCTHETA, total[lo_:lo_ + cnt_], total[lo_:lo_ + cnt_], h_c[lo_:lo_ + cnt_], c=ps.y_step, size=cnt_)
+    return total
+
+
+def _quotient_numerator_of(ps, C, points_of, tables, k_domain, zeta_, omega_, size, rows=None, fused=None):
+    """the fused evaluator over one evaluation domain: `points_of` maps a list of coefficient vectors to their values there"""
+    D, L, pk, groups = ps.D, ps.L, ps.pk, _circuit_polys(C)
+    if points_of is None:
+        # the cuda shape of Evaluator::evaluate_h (plonk/evaluation.rs:1229-1241): COEFFICIENT forms in, the extended
+        # values of the numerator out, one h2_evaluate_h_coeff call (host slices: halo2-gpu-specific_amd/host_api.py)
+        coeff_tables = {"fixed": pk.fixed_polys, "sigma": pk.sigma_polys, "l0": pk.l0_poly, "l_last": pk.l_last_poly,
+                        "l_active_row": tables["l_active_row"]}
+        b = _evalh_desc(ps, coeff_tables, *groups, k_domain, zeta_, omega_)
+        if fused:           # ... divided by the vanishing polynomial and taken back to coefficients in the same call
+            out = fused(b.desc, ps.dom, pk.t_evaluations)
+        else:
+            out = D.empty(size)
+            check(L.h2_evaluate_h_coeff(ctypes.byref(b.desc), out.data_ptr()), "h2_evaluate_h_coeff")
+        ps.mark("evaluate_h")
+        return out
+    pre = C.advice_extended if size == ps.dom.extended_n else None    # already extended on the side stream (small proofs)
+    if pre is not None:
+        groups[0] = []
+    # every coefficient vector of this circuit instance that the evaluator reads, taken to the evaluation domain as ONE
+    # list (the coset route transforms them sixteen to a launch)
+    if ps.advice_arrival is not None:
+        # the advice columns' coefficients have been travelling since the commit phase; the product columns' are still on
+        # their way: the advice columns go to the evaluation domain first
+        ps.advice_arrival.wait()
+        first = points_of(groups[0])
+        for arrival in (ps.z_arrival, ps.m_arrival):
+            if arrival is not None:
+                arrival.wait()
+        flat = first + points_of([t for grp in groups[1:] for t in grp])
+    else:
+        flat = points_of([t for grp in groups for t in grp])
+    it = iter(flat)
+    cosets = [[next(it) for _ in grp] for grp in groups]             # the values, in the evaluator's groups again
+    if pre is not None:
+        cosets[0] = pre
+    del flat, it
+    ps.htrace("points_of done (launched)")
+    ps.mark("cosets")
+    b = _evalh_desc(ps, tables, *cosets, k_domain, zeta_, omega_, rows)
+    ps.htrace("descriptor built")
+    out = D.empty(size)
+    ps.htrace("output allocated")
+    check(L.h2_dev_evaluate_h(ctypes.byref(b.desc), out.data_ptr(), D.stream), "h2_dev_evaluate_h")
+    ps.htrace("h2_dev_evaluate_h returned")
+    ps.mark("evaluate_h")
+    return out
+
+
+def _quotient(ps):
+    """h(X): advice to coefficient form, extended cosets, the fused evaluator -> the pieces of h, n coefficients each"""
+    D, dom, circuits = ps.D, ps.dom, ps.circuits
+    nadv = len(circuits[0].advice)
+    if ps.side_intt is not None:
+        polys_, ext_, done_ = ps.side_intt
         D.tstream.wait_event(done_)
         for ci, C in enumerate(circuits):
-            C["advice_polys"] = polys_[ci * nadv:(ci + 1) * nadv]
-            C["advice_extended"] = ext_[ci * nadv:(ci + 1) * nadv] if ext_ is not None else None
-            C["advice"] = None                                       # the Lagrange values are not needed again
-        del advice_dev
-    elif advice_arrival is not None:
+            C.advice_polys = polys_[ci * nadv:(ci + 1) * nadv]
+            C.advice_extended = ext_[ci * nadv:(ci + 1) * nadv] if ext_ is not None else None
+            C.advice = None                                          # the Lagrange values are not needed again
+        ps.side_intt = None
+        del polys_, ext_
+    elif ps.advice_arrival is not None:
         for ci, C in enumerate(circuits):
-            C["advice_polys"] = advice_coeffs[ci * nadv:(ci + 1) * nadv]
-            C["advice"] = None
-        del advice_dev
+            C.advice_polys = ps.advice_coeffs[ci * nadv:(ci + 1) * nadv]
+            C.advice = None
+        ps.advice_coeffs = None
     else:
         for C in circuits:
-            C["advice_polys"] = D.intt_many(C["advice"], dom)           # in place: the Lagrange values are not needed again
+            C.advice_polys = D.intt_many(C.advice, dom)                 # in place: the Lagrange values are not needed again
     # the coefficient forms of the witness and of the product columns are final: evaluator, evaluations and openings read them
-    D.retain([t for C in circuits for t in list(C["advice_polys"]) + list(C["instance_polys"]) + list(C["z_polys"]) +
-              [z_ for st in C["lookups"] for z_ in st["z_polys"]] + [st["m_poly"] for st in C["lookups"]] + list(C["shuffle_polys"])])
-    g = pk.graph
+    D.retain([t for C in circuits for grp in _circuit_polys(C) for t in grp])
     plan = D.coset_plan(dom)
     if D.group_size <= 1:                      # on one device the proving key decides which tables exist
-        if coset_tabs is None:
+        if ps.coset_tabs is None:
             plan = None
         else:
-            plan = (dom.quotient_poly_degree, 1, sorted(coset_tabs))
+            plan = (dom.quotient_poly_degree, 1, sorted(ps.coset_tabs))
     # Several circuits share one quotient: the reference keeps folding `value = value * y + term` from one circuit into
     # the next (plonk/evaluation.rs:839-1100), i.e. h = sum_i y^(T (N - 1 - i)) h_i with T terms per circuit and h_i the
     # fold of circuit i alone -- each circuit runs through the evaluator on its own and the results are combined.
-    terms_per_circuit = (len(pk.value_parts) + (2 * nsets + 1 if nsets else 0) +
-                         sum(2 * len(st["z_polys"]) + 1 for st in circuits[0]["lookups"]) + 3 * len(circuits[0]["shuffle_polys"]))
-    y_step = pow(y, terms_per_circuit, R_MOD)
+    terms_per_circuit = (len(ps.pk.value_parts) + (2 * ps.nsets + 1 if ps.nsets else 0) +
+                         sum(2 * len(st.z) + 1 for st in circuits[0].lookups) + 3 * len(circuits[0].shuffle_z))
+    ps.y_step = pow(ps.y, terms_per_circuit, R_MOD)
+    return _quotient_extended(ps) if plan is None else _quotient_by_cosets(ps, plan)
 
-    def evaluate_quotient(points_of, tables, k_domain, zeta_, omega_, size, rows=None, fused=None):
-        """`rows` = (first, count): only these rows of the domain are evaluated (and valid in the result).  `fused` (host
-        vectors, one circuit instance): the device's h2_quotient_poly_coeff -- the result is h(X) in COEFFICIENT form"""
-        total = None
-        lo_, cnt_ = rows if rows is not None else (0, size)
-        for C in circuits:
-            h_c = evaluate_quotient_of(C, points_of, tables, k_domain, zeta_, omega_, size, rows, fused)
-            if total is None:
-                total = h_c
-            else:                                                                           # H2_OP_LCTHETA: l * c + r
-                D.eval_op(5, total[lo_:lo_ + cnt_], total[lo_:lo_ + cnt_], h_c[lo_:lo_ + cnt_], c=y_step, size=cnt_)
-        return total
 
-    def evaluate_quotient_of(C, points_of, tables, k_domain, zeta_, omega_, size, rows=None, fused=None):
-        """the fused evaluator over one evaluation domain: `points_of` maps a list of coefficient vectors to their values there"""
-        lookups = C["lookups"]
-        if points_of is None:
-            # the cuda shape of Evaluator::evaluate_h (plonk/evaluation.rs:1229-1241): COEFFICIENT forms in, the extended
-            # values of the numerator out, one h2_evaluate_h_coeff call (host slices: halo2-gpu-specific_amd/host_api.py)
-            b = ev.Builder().build(
-                k=dom.k, extended_k=k_domain, blinding_factors=bf, chunk_len=chunk,
-                constants=np.array([fr_to_mont_limbs(c) for c in g.constants], dtype=np.uint64), rotations=g.rotations,
-                calculations=g.calculations, value_parts=pk.value_parts, lookups=pk.lookup_calcs, shuffles=pk.shuffle_calcs,
-                fixed=[t.data_ptr() for t in pk.fixed_polys], advice=[t.data_ptr() for t in C["advice_polys"]],
-                instance=[t.data_ptr() for t in C["instance_polys"]],
-                l0=pk.l0_poly.data_ptr(), l_last=pk.l_last_poly.data_ptr(), l_active_row=tables["l_active_row"].data_ptr(),
-                perm_z=[t.data_ptr() for t in C["z_polys"]], perm_columns=[(_ANY[kd], i) for kd, i in cols],
-                perm_sigma=[t.data_ptr() for t in pk.sigma_polys],
-                lookup_z=[t.data_ptr() for st in lookups for t in st["z_polys"]],
-                lookup_m=[st["m_poly"].data_ptr() for st in lookups],
-                shuffle_z=[t.data_ptr() for t in C["shuffle_polys"]],
-                y=fr_to_mont_limbs(y), beta=fr_to_mont_limbs(beta), gamma=fr_to_mont_limbs(gamma), theta=fr_to_mont_limbs(theta),
-                delta=fr_to_mont_limbs(DELTA), zeta=fr_to_mont_limbs(zeta_), extended_omega=fr_to_mont_limbs(omega_),
-                flags=0 if pk.evalh_stats else ev.EVALH_INTERPRET)
-            if fused:           # ... divided by the vanishing polynomial and taken back to coefficients in the same call
-                out = fused(b.desc, dom, pk.t_evaluations)
-                mark("evaluate_h")
-                return out
-            out = D.empty(size)
-            check(L.h2_evaluate_h_coeff(ctypes.byref(b.desc), out.data_ptr()), "h2_evaluate_h_coeff")
-            mark("evaluate_h")
-            return out
-        pre = C.get("advice_extended") if size == en else None    # already extended on the side stream (small proofs)
-        # every coefficient vector of this circuit instance that the evaluator reads, taken to the evaluation domain as ONE
-        # list (the coset route transforms them sixteen to a launch)
-        groups = [[] if pre is not None else list(C["advice_polys"]), list(C["instance_polys"]), list(C["z_polys"]),
-                  [t for st in lookups for t in st["z_polys"]], [st["m_poly"] for st in lookups], list(C["shuffle_polys"])]
-        if advice_arrival is not None:
-            # the advice columns' coefficients have been travelling since the commit phase; the product columns' are still on
-            # their way: the advice columns go to the evaluation domain first
-            advice_arrival.wait()
-            first = points_of(groups[0])
-            for arrival in (z_arrival, m_arrival):
-                if arrival is not None:
-                    arrival.wait()
-            flat = first + points_of([t for grp in groups[1:] for t in grp])
+def _quotient_extended(ps):
+    """one device: the whole extended domain at once"""
+    D, L, pk, dom, n = ps.D, ps.L, ps.pk, ps.dom, ps.n
+    en = dom.extended_n
+    tables = {"fixed": pk.fixed_cosets, "sigma": pk.sigma_cosets, "l0": pk.l0, "l_last": pk.l_last,
+              "l_active_row": pk.l_active_row}
+    from_coeffs = D.quotient_from_coeffs
+    # (host vectors, one circuit instance: the three steps in one call, the 2^extended_k values never leave the device)
+    fused = D.quotient_poly_coeff if from_coeffs and len(ps.circuits) == 1 else None
+    h = _quotient_numerator(ps, None if from_coeffs else (lambda ts: D.coeffs_to_extended(ts, dom)), tables, dom.extended_k, ZETA,
+                            dom.extended_omega, en, fused=fused)
+    if not fused:
+        # vanishing construct: divide, back to coefficients (vanishing/prover.rs:69-112)
+        check(L.h2_dev_divide_by_vanishing_poly(h.data_ptr(), en, pk.t_evaluations.data_ptr(), len(dom.t_evaluations),
+                                                D.stream), "h2_dev_divide_by_vanishing_poly")
+        D.extended_to_coeff(h, dom)
+    return [h[i * n:(i + 1) * n] for i in range(dom.quotient_poly_degree)]
+
+
+def _quotient_by_cosets(ps, plan):
+    """one proof over several ranks: the extended domain by coset.  On coset j (points
+    g_j w^i, extended indices c i + j) every rotation stays inside the coset, the vanishing polynomial is the
+    constant gamma_j - 1 (gamma_j = g_j^n) and h(X) = sum_m X^(n m) h_m(X) reads P_j(X) = sum_m gamma_j^m h_m(X): the
+    evaluator runs on n points per coset with zeta := g_j, extended_omega := omega, extended_k := k; the inverse
+    coset transform gives P_j; one n-vector per coset is exchanged; the pieces are h_m = sum_j Vinv[m][j] P_j."""
+    from .parallel import allgather_rows, coset_unmix_matrix, exchange_cosets, scatter_cosets
+
+    D, dom, n, circuits, coset_tabs = ps.D, ps.dom, ps.n, ps.circuits, ps.coset_tabs
+    c, shards, owned = plan
+    mine = {}
+    # More ranks than cosets (a multiple G of them): the G ranks of a coset share its work instead of repeating it --
+    # every G-th column's coset transform each, row slices exchanged, the evaluator on n / G rows each, the quotient's
+    # rows all-gathered inside the group (parallel.exchange_row_slices; DESIGN.md section 6)
+    sub = D.coset_rank_group(c)
+    used_rots = list(ps.pk.graph.rotations) + ([0, 1, ps.last_rot] if (ps.nsets or circuits[0].lookups or circuits[0].shuffle_z) else [0])
+    halo = (max(0, -min(used_rots)), max(0, max(used_rots)))
+    if sub is not None and (n % sub[1] or n // sub[1] <= halo[0] + halo[1] + 1):
+        sub = None
+    for j in owned:
+        g_j = ZETA * pow(dom.extended_omega, j, R_MOD) % R_MOD
+        if sub is None:
+            lo_g, m_g = 0, n
+            h_j = _quotient_numerator(ps, lambda ts, j=j: D.coeffs_to_coset(ts, dom, j), coset_tabs[j], dom.k, g_j, dom.omega, n)
         else:
-            flat = points_of([t for grp in groups for t in grp])
-        cut, at = [], 0
-        for grp in groups:
-            cut.append(flat[at:at + len(grp)])
-            at += len(grp)
-        advice_cosets = pre if pre is not None else cut[0]
-        instance_cosets, z_cosets, lookup_z_cosets, lookup_m_cosets, shuffle_cosets = cut[1:]
-        del flat, cut
-        htrace("points_of done (launched)")
-        mark("cosets")
-        b = ev.Builder().build(
-            k=dom.k, extended_k=k_domain, blinding_factors=bf, chunk_len=chunk,
-            constants=np.array([fr_to_mont_limbs(c) for c in g.constants], dtype=np.uint64), rotations=g.rotations,
-            calculations=g.calculations, value_parts=pk.value_parts, lookups=pk.lookup_calcs, shuffles=pk.shuffle_calcs,
-            fixed=[t.data_ptr() for t in tables["fixed"]], advice=[t.data_ptr() for t in advice_cosets],
-            instance=[t.data_ptr() for t in instance_cosets],
-            l0=tables["l0"].data_ptr(), l_last=tables["l_last"].data_ptr(), l_active_row=tables["l_active_row"].data_ptr(),
-            perm_z=[t.data_ptr() for t in z_cosets], perm_columns=[(_ANY[kd], i) for kd, i in cols],
-            perm_sigma=[t.data_ptr() for t in tables["sigma"]],
-            lookup_z=[t.data_ptr() for t in lookup_z_cosets], lookup_m=[t.data_ptr() for t in lookup_m_cosets],
-            shuffle_z=[t.data_ptr() for t in shuffle_cosets],
-            y=fr_to_mont_limbs(y), beta=fr_to_mont_limbs(beta), gamma=fr_to_mont_limbs(gamma), theta=fr_to_mont_limbs(theta),
-            delta=fr_to_mont_limbs(DELTA), zeta=fr_to_mont_limbs(zeta_), extended_omega=fr_to_mont_limbs(omega_),
-            flags=0 if pk.evalh_stats else ev.EVALH_INTERPRET,
-            row_begin=rows[0] if rows is not None else 0, row_count=rows[1] if rows is not None else 0)
-        htrace("descriptor built")
-        out = D.empty(size)
-        htrace("output allocated")
-        check(L.h2_dev_evaluate_h(ctypes.byref(b.desc), out.data_ptr(), D.stream), "h2_dev_evaluate_h")
-        htrace("h2_dev_evaluate_h returned")
-        mark("evaluate_h")
-        return out
-
-    if plan is None:
-        # ---- one device: the whole extended domain at once ------------------------------------------------------
-        tables = {"fixed": pk.fixed_cosets, "sigma": pk.sigma_cosets, "l0": pk.l0, "l_last": pk.l_last,
-                  "l_active_row": pk.l_active_row}
-        from_coeffs = getattr(D, "quotient_from_coeffs", False)
-        # (host vectors, one circuit instance: the three steps in one call, the 2^extended_k values never leave the device)
-        fused = getattr(D, "quotient_poly_coeff", None) if from_coeffs and len(circuits) == 1 else None
-        h = evaluate_quotient(None if from_coeffs else (lambda ts: D.coeffs_to_extended(ts, dom)), tables, ek, ZETA,
-                              dom.extended_omega, en, fused=fused)
-        if not fused:
-            # vanishing construct: divide, back to coefficients (vanishing/prover.rs:69-112)
-            check(L.h2_dev_divide_by_vanishing_poly(h.data_ptr(), en, pk.t_evaluations.data_ptr(), len(dom.t_evaluations),
-                                                    D.stream), "h2_dev_divide_by_vanishing_poly")
-            D.extended_to_coeff(h, dom)
-        pieces = [h[i * n:(i + 1) * n] for i in range(dom.quotient_poly_degree)]
+            m_g = n // sub[1]
+            lo_g = sub[2] * m_g
+            h_j = _quotient_numerator(ps, lambda ts, j=j: D.coeffs_to_coset_rows(ts, dom, j, sub, halo), coset_tabs[j], dom.k, g_j,
+                                      dom.omega, n, rows=(lo_g, m_g))
+        D.eval_op(OP_MUL_C, h_j[lo_g:lo_g + m_g], h_j[lo_g:lo_g + m_g], c=dom.t_evaluations[j % len(dom.t_evaluations)],
+                  size=m_g)                                                                   # / (gamma_j - 1)
+        if sub is not None:
+            allgather_rows(h_j, lo_g, lo_g + m_g, group=sub[0], stream=D.tstream)
+        mine[j] = D.coset_to_coeff(h_j, dom, j)
+    # Everything after the quotient -- the un-mixing, the h pieces' commitments, the evaluations, the multiopen argument --
+    # works on coefficient RANGES (Device.row_range): a rank needs only its own n / P coefficients of every coset
+    # polynomial, so their owners scatter slices (c x n / P x 32 B per rank) instead of broadcasting whole vectors.
+    if D.group_size > 1 and (ps.lo, ps.hi) != (0, n):
+        polys_j = scatter_cosets(mine, c, shards, ps.lo, ps.hi, group=D.group, stream=D.tstream)
+    elif D.group_size > 1:
+        polys_j = exchange_cosets(mine, c, shards, group=D.group, stream=D.tstream)
     else:
-        # ---- one proof over several ranks: the extended domain by coset (DESIGN.md section 6).  On coset j (points
-        # g_j w^i, extended indices c i + j) every rotation stays inside the coset, the vanishing polynomial is the
-        # constant gamma_j - 1 (gamma_j = g_j^n) and h(X) = sum_m X^(n m) h_m(X) reads P_j(X) = sum_m gamma_j^m h_m(X): the
-        # evaluator runs on n points per coset with zeta := g_j, extended_omega := omega, extended_k := k; the inverse
-        # coset transform gives P_j; one n-vector per coset is exchanged; the pieces are h_m = sum_j Vinv[m][j] P_j.
-        from .parallel import coset_unmix_matrix, exchange_cosets, scatter_cosets
+        polys_j = [mine[j] for j in range(c)]
+    gammas = [pow(ZETA * pow(dom.extended_omega, j, R_MOD) % R_MOD, n, R_MOD) for j in range(c)]
+    unmix = coset_unmix_matrix(gammas, dom.quotient_poly_degree)
+    pieces = [D.lincomb_range(D.empty(n), polys_j, row, n) for row in unmix]
+    del polys_j, mine
+    coset_tabs.trim()
+    return pieces
 
-        c, shards, owned = plan
-        mine = {}
-        # More ranks than cosets (a multiple G of them): the G ranks of a coset share its work instead of repeating it --
-        # every G-th column's coset transform each, row slices exchanged, the evaluator on n / G rows each, the quotient's
-        # rows all-gathered inside the group (parallel.exchange_row_slices; DESIGN.md section 6)
-        sub = D.coset_rank_group(c)
-        used_rots = list(g.rotations) + ([0, 1, last_rot] if (nsets or circuits[0]["lookups"] or circuits[0]["shuffle_polys"]) else [0])
-        halo = (max(0, -min(used_rots)), max(0, max(used_rots)))
-        if sub is not None and (n % sub[1] or n // sub[1] <= halo[0] + halo[1] + 1):
-            sub = None
-        for j in owned:
-            g_j = ZETA * pow(dom.extended_omega, j, R_MOD) % R_MOD
-            if sub is None:
-                h_j = evaluate_quotient(lambda ts, j=j: D.coeffs_to_coset(ts, dom, j), coset_tabs[j], dom.k, g_j, dom.omega, n)
-                D.eval_op(0, h_j, h_j, c=dom.t_evaluations[j % len(dom.t_evaluations)])      # H2_OP_MUL_C: / (gamma_j - 1)
-            else:
-                from .parallel import allgather_rows
 
-                m_g = n // sub[1]
-                lo_g = sub[2] * m_g
-                h_j = evaluate_quotient(lambda ts, j=j: D.coeffs_to_coset_rows(ts, dom, j, sub, halo), coset_tabs[j], dom.k, g_j,
-                                        dom.omega, n, rows=(lo_g, m_g))
-                D.eval_op(0, h_j[lo_g:lo_g + m_g], h_j[lo_g:lo_g + m_g], c=dom.t_evaluations[j % len(dom.t_evaluations)], size=m_g)
-                allgather_rows(h_j, lo_g, lo_g + m_g, group=sub[0], stream=D.tstream)
-            mine[j] = D.coset_to_coeff(h_j, dom, j)
-        # Everything after the quotient -- the un-mixing, the h pieces' commitments, the evaluations, the multiopen argument --
-        # works on coefficient RANGES (Device.row_range): a rank needs only its own n / P coefficients of every coset
-        # polynomial, so their owners scatter slices (c x n / P x 32 B per rank) instead of broadcasting whole vectors.
-        if D.group_size > 1 and D.row_range(n) != (0, n):
-            polys_j = scatter_cosets(mine, c, shards, *D.row_range(n), group=D.group, stream=D.tstream)
-        elif D.group_size > 1:
-            polys_j = exchange_cosets(mine, c, shards, group=D.group, stream=D.tstream)
-        else:
-            polys_j = [mine[j] for j in range(c)]
-        gammas = [pow(ZETA * pow(dom.extended_omega, j, R_MOD) % R_MOD, n, R_MOD) for j in range(c)]
-        unmix = coset_unmix_matrix(gammas, dom.quotient_poly_degree)
-        pieces = [D.lincomb_range(D.empty(n), polys_j, row, n) for row in unmix]
-        del polys_j, mine
-        coset_tabs.trim()
-    mark("vanishing transforms")
-    for P in D.msm_batch(pieces, params.g, n, 254):
-        transcript.write_point(P)
-    x = transcript.squeeze_challenge_scalar()
+def _evaluations(ps, pieces):
+    """evaluations (prover.rs:700-790): every (polynomial, point) pair of the proof in one batched launch
+    -> (h(X), {(key, rotation): value})"""
+    D, pk, cs, dom, n, x, last_rot, circuits = ps.D, ps.pk, ps.cs, ps.dom, ps.n, ps.x, ps.last_rot, ps.circuits
     xn = pow(x, n, R_MOD)
-    mark("vanishing construct")
-
-    # ---- evaluations (prover.rs:700-790): every (polynomial, point) pair of the proof in one batched launch ------
     # h(X) = sum_i x^(n i) piece_i (vanishing/prover.rs:120-124)
     D.retain(pieces)
     h_poly = D.lincomb_range(D.empty(n), pieces, [pow(xn, i, R_MOD) for i in range(len(pieces))], n)
@@ -2522,42 +2615,42 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
     # every circuit, fixed, the random polynomial, sigma, then per circuit the permutation / lookup / shuffle products
     for ci, C in enumerate(circuits):
         for c, rot in cs.instance_queries:
-            want(("instance", ci, c), C["instance_polys"][c], rot)
+            want(("instance", ci, c), C.instance_polys[c], rot)
     for ci, C in enumerate(circuits):
         for c, rot in cs.advice_queries:
-            want(("advice", ci, c), C["advice_polys"][c], rot)
+            want(("advice", ci, c), C.advice_polys[c], rot)
     for c, rot in cs.fixed_queries:
         want(("fixed", c), pk.fixed_polys[c], rot)
-    want(("random",), random_poly, 0)
+    want(("random",), ps.random_poly, 0)
     for i, p in enumerate(pk.sigma_polys):
         want(("sigma", i), p, 0)
     for ci, C in enumerate(circuits):
-        want_set_evals("z%d" % ci, C["z_polys"])
+        want_set_evals("z%d" % ci, C.z)
     for ci, C in enumerate(circuits):
-        for li, st in enumerate(C["lookups"]):                         # logup/prover.rs:419-446
-            want(("lookup_m", ci, li), st["m_poly"], 0)
-            want_set_evals("lookup_z%d_%d" % (ci, li), st["z_polys"])
+        for li, st in enumerate(C.lookups):                            # logup/prover.rs:419-446
+            want(("lookup_m", ci, li), st.m, 0)
+            want_set_evals("lookup_z%d_%d" % (ci, li), st.z)
     for ci, C in enumerate(circuits):
-        for i, p in enumerate(C["shuffle_polys"]):                     # shuffle/prover.rs:196-212
+        for i, p in enumerate(C.shuffle_z):                            # shuffle/prover.rs:196-212
             want(("shuffle_z", ci, i), p, 0)
             want(("shuffle_z", ci, i), p, 1)
     want(("h",), h_poly, 0, write=False)                               # opened, not written (vanishing/prover.rs:140-155)
     values = D.eval_polynomial_ranges([p for _, p, _ in wanted], n, [dom.rotate_omega(x, r) for _, _, r in wanted])
     evals = {(key, rot): v for (key, _, rot), v in zip(wanted, values)}
     for key, rot in written:
-        transcript.write_scalar(evals[(key, rot)])
-    mark("evaluations")
+        ps.transcript.write_scalar(evals[(key, rot)])
+    return h_poly, evals
 
-    def evaluate(key, poly, rot):
-        return evals[(key, rot)]
 
-    # ---- multiopen query list in the reference's order (prover.rs:792-840): per circuit its instance, advice,
-    # permutation, lookup and shuffle openings; then fixed, sigma, h and the random polynomial -----------------------
+def _multiopen_queries(ps, h_poly, evals):
+    """multiopen query list in the reference's order (prover.rs:792-840): per circuit its instance, advice,
+    permutation, lookup and shuffle openings; then fixed, sigma, h and the random polynomial -> (queries, polys)"""
+    pk, cs, dom, x, last_rot = ps.pk, ps.cs, ps.dom, ps.x, ps.last_rot
     polys, queries = {}, []
 
     def query(key, poly, rot):
         polys[key] = poly
-        queries.append((key, rot, dom.rotate_omega(x, rot), evaluate(key, poly, rot)))
+        queries.append((key, rot, dom.rotate_omega(x, rot), evals[(key, rot)]))
 
     def open_sets(name, polys_):
         for i, p in enumerate(polys_):
@@ -2566,16 +2659,16 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
         for i in reversed(range(len(polys_) - 1)):
             query((name, i), polys_[i], last_rot)
 
-    for ci, C in enumerate(circuits):
+    for ci, C in enumerate(ps.circuits):
         for c, rot in cs.instance_queries:
-            query(("instance", ci, c), C["instance_polys"][c], rot)
+            query(("instance", ci, c), C.instance_polys[c], rot)
         for c, rot in cs.advice_queries:
-            query(("advice", ci, c), C["advice_polys"][c], rot)
-        open_sets("z%d" % ci, C["z_polys"])
-        for li, st in enumerate(C["lookups"]):
-            query(("lookup_m", ci, li), st["m_poly"], 0)
-            open_sets("lookup_z%d_%d" % (ci, li), st["z_polys"])
-        for i, p in enumerate(C["shuffle_polys"]):
+            query(("advice", ci, c), C.advice_polys[c], rot)
+        open_sets("z%d" % ci, C.z)
+        for li, st in enumerate(C.lookups):
+            query(("lookup_m", ci, li), st.m, 0)
+            open_sets("lookup_z%d_%d" % (ci, li), st.z)
+        for i, p in enumerate(C.shuffle_z):
             query(("shuffle_z", ci, i), p, 0)
             query(("shuffle_z", ci, i), p, 1)
     for c, rot in cs.fixed_queries:
@@ -2583,22 +2676,8 @@ def create_proof_ext(device, params, pk, advice, rng, use_gwc, timings=None, ins
     for i, p in enumerate(pk.sigma_polys):
         query(("sigma", i), p, 0)
     query(("h",), h_poly, 0)
-    query(("random",), random_poly, 0)
-    (_gwc if use_gwc else _shplonk)(D, params, transcript, queries, polys, n)
-    D.release_retained()
-    mark("multiopen")
-    if _host_trace:
-        import sys
-
-        base = _host_trace[0][1]
-        sys.stderr.write("host trace (ms): " + ", ".join("%s %.2f" % (nm, (t - base) * 1e3) for nm, t in _host_trace) + "\n")
-    if timings is not None:
-        for (_, t0), (name, t1) in zip(marks, marks[1:]):
-            timings[name] = timings.get(name, 0.0) + (t1 - t0)
-        if D.group_size > 1:
-            # per phase: seconds / bytes / calls of this rank's collectives (parallel.COMM_TRACE), next to `timings`
-            D.last_comm = _par.comm_trace_end()
-    return transcript.finalize()
+    query(("random",), ps.random_poly, 0)
+    return queries, polys
 
 
 def _gwc(D, params, transcript, queries, polys, n):
@@ -2607,7 +2686,7 @@ def _gwc(D, params, transcript, queries, polys, n):
     eval_sum pair; here they never left the device and one lincomb forms the batch.  One proof over several ranks: every
     vector pass runs on the rank's coefficient range (Device.*_range(s)); the commitments are range-split anyway."""
     v = transcript.squeeze_challenge_scalar()
-    quotient_sum = getattr(D, "quotient_sum", None) if D.row_range(n) == (0, n) else None
+    quotient_sum = D.quotient_sum if D.row_range(n) == (0, n) else None
     groups = {}
     for qu in queries:
         groups.setdefault(qu[1], []).append(qu)          # BTreeMap<Rotation, Vec<Q>> (gwc.rs:40-49)
@@ -2641,7 +2720,7 @@ def _shplonk(D, params, transcript, queries, polys, n):
     vpow = [pow(v, R - 1 - r, R_MOD) for r in range(R)]
     # a device whose vectors live on the HOST computes the whole sum in one call (h2_quotient_sum: the combinations, the
     # subtractions and the synthetic divisions stay on the device, h(X) crosses PCIe once)
-    quotient_sum = getattr(D, "quotient_sum", None) if D.row_range(n) == (0, n) else None
+    quotient_sum = D.quotient_sum if D.row_range(n) == (0, n) else None
     # quotient contribution of every rotation set: (sum_i y^(m-1-i) (p_i - r_i)) / prod (X - point)
     quotients, fused_sets = [], []
     ping, pong = D.empty(n), D.empty(n)
@@ -2759,8 +2838,6 @@ def check_witness(device, pk, advice, instances=(), seed=0, max_failures=1024, m
     Out of scope: MockProver's CellNotAssigned and ConstraintPoisoned (a dense witness has no unassigned cells; cells in rows
     >= usable are read as the caller supplied them), gate rows in the blinding region, any change to create_proof*, and the
     Rust shims under integration/.  `timings` (a dict): filled with the seconds of each phase (synchronising between them)."""
-    import time
-
     D, L, torch = device, device.L, device.torch
     cs, dom = pk.cs, pk.domain
     n = dom.n
@@ -2798,8 +2875,7 @@ def check_witness(device, pk, advice, instances=(), seed=0, max_failures=1024, m
     for ci, (adv_in, inst_in) in enumerate(zip(advice_sets, instance_sets)):
         if len(adv_in) != cs.num_advice:
             raise ValueError("check_witness: %d advice columns for a circuit of %d" % (len(adv_in), cs.num_advice))
-        if len(inst_in) != cs.num_instance:
-            raise ValueError("InvalidInstances")
+        inst = _instance_columns(D, cs, n, usable, inst_in)
         adv = []
         for col in adv_in:
             t, arrived = D.upload_async(col)          # a copy on the device: the caller's column is only read
@@ -2809,13 +2885,6 @@ def check_witness(device, pk, advice, instances=(), seed=0, max_failures=1024, m
                 check(L.h2_dev_batch_unmont(t.data_ptr(), n, D.stream), "h2_dev_batch_unmont")
             check(L.h2_dev_batch_mont(t.data_ptr(), n, D.stream), "h2_dev_batch_mont")
             adv.append(t)
-        inst = []
-        for vals in inst_in:
-            if len(vals) > usable:
-                raise ValueError("InstanceTooLarge")
-            t = D.zeros(n)
-            D.set_rows(t, 0, list(vals))
-            inst.append(t)
         phase("upload")
         fixed = pk.fixed_values
         if gate_prog[1]:

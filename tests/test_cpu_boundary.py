@@ -30,6 +30,11 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(L, name), "libhalo2_hip.so does not export %s" % name
         assert name in SYMBOLS, "python binding table misses %s" % name
     assert sorted(SYMBOLS) == names
+    # ... and the names prover.py gives Device.eval_op's operations are the header's H2_OP_* values
+    from halo2_gpu_specific_amd import prover
+
+    ops = dict(re.findall(r"\bH2_(OP_[A-Z_]+)\s*=\s*(\d+)", open(os.path.join(ROOT, "include", "halo2_hip.h")).read()))
+    assert len(ops) == 9 and all(getattr(prover, name) == int(value) for name, value in ops.items()), ops
 
 
 def test_every_entry_point_cites_the_reference():

@@ -69,6 +69,33 @@ def test_host_slice_api_gives_the_resident_provers_bytes(oracle, device, which, 
         assert prover.create_proof_ext(H, hparams, hpk, [adv, adv2], ProverRng(5), False, instances=[(), ()]) == want
 
 
+def test_a_proof_that_raises_leaves_no_registration_behind(oracle, device):
+    """a proof that raises after it has retained vectors (a lookup input that is not in the table) unregisters them: nothing
+    is left for the next proof on the same device object to clear, and a proof on ANOTHER HostApiDevice, whose vectors may
+    land on the freed addresses, gives the resident prover's bytes"""
+    from halo2_gpu_specific_amd import host_api, prover
+    from halo2_gpu_specific_amd.rng import ProverRng
+
+    k, cs = 6, lookup_shuffle_cs()
+    syn = rp.LookupShuffle.synthesize(k)
+    fixed, copies, inst = cols_to_arr(syn[1]), [(l[0], l[1], r[0], r[1]) for l, r in syn[2]], syn[3]
+    bad = [c[:] for c in syn[0]]
+    bad[4][2] = 5                                           # e[2] is not in the table u
+    params = srs(oracle, device, k)
+    H = host_api.HostApiDevice()
+    hparams = host_api.params_like(H, params)
+    hpk = prover.keygen(H, hparams, cs, fixed, copies)
+    with pytest.raises(prover.H2Error):
+        prover.create_proof_ext(H, hparams, hpk, cols_to_arr(bad), ProverRng(1), False, instances=inst)
+    assert H._retained == []
+    H2 = host_api.HostApiDevice()
+    hparams2 = host_api.params_like(H2, params)
+    hpk2 = prover.keygen(H2, hparams2, cs, fixed, copies)
+    pk = prover.keygen(device, params, cs, fixed, copies)
+    want = prover.create_proof_ext(device, params, pk, cols_to_arr(syn[0]), ProverRng(1), False, instances=inst)
+    assert prover.create_proof_ext(H2, hparams2, hpk2, cols_to_arr(syn[0]), ProverRng(1), False, instances=inst) == want
+
+
 def test_host_slice_device_needs_a_gpu_and_touches_no_oracle():
     import inspect
 

@@ -25,20 +25,32 @@ def cols_to_arr(cols):
     return [ints_to_arr(c) for c in cols]
 
 
-@pytest.mark.parametrize("which,k", [("mini", 5), ("mini", 8), ("rot", 6), ("lookup", 6)])   # ("mini", 8): BASELINE configs[0], literally
-def test_cpu_prover_bytes_match_big_integer_prover(oracle, which, k):
+@pytest.mark.parametrize("which,k,ncirc", [
+    pytest.param("mini", 5, 1, id="mini-5"), pytest.param("mini", 8, 1, id="mini-8"),     # ("mini", 8): BASELINE configs[0], literally
+    pytest.param("rot", 6, 1, id="rot-6"), pytest.param("lookup", 6, 1, id="lookup-6"),
+    # two circuit instances in one proof (`circuits: &[ConcreteCircuit]`, plonk/prover.rs:206-232): the per-circuit state of
+    # every phase, as tests/test_gpu_plonk.py::test_several_circuit_instances_match_big_integer_prover builds them
+    pytest.param("mini", 5, 2, id="mini-5-two-instances"), pytest.param("lookup", 6, 2, id="lookup-6-two-instances")])
+def test_cpu_prover_bytes_match_big_integer_prover(oracle, which, k, ncirc):
     import oracle_prover as op
     from halo2_gpu_specific_amd import circuits, prover
     from halo2_gpu_specific_amd.rng import ProverRng
+    from test_plonk_host import _second_lookup_shuffle_witness
 
     insts = ()
     if which == "lookup":
         ref_cs, cs = rp.LookupShuffle, lookup_shuffle_cs()
         adv, fixed, copies, insts = ref_cs.synthesize(k)
+        if ncirc == 2:
+            adv_b, inst_b = _second_lookup_shuffle_witness(k)
+            adv, insts = [adv, adv_b], [insts, inst_b]
     else:
         ref_cs = rp.MiniPlonk if which == "mini" else rp.RotGate
         cs = circuits.mini_plonk() if which == "mini" else rot_gate_cs()
         adv, fixed, copies = ref_cs.synthesize(k)
+        if ncirc == 2:
+            adv, insts = [ref_cs.synthesize(k, a=5)[0], ref_cs.synthesize(k, a=7)[0]], [(), ()]
+    adv_arr = [cols_to_arr(a) for a in adv] if ncirc == 2 else cols_to_arr(adv)
     rpk = rp.keygen(ref_cs, k, S_TRAPDOOR, fixed, copies)
     for kw in ({}, {"force_cosets": True}):
         D = op.OracleDevice(threads=2, **kw)
@@ -48,7 +60,7 @@ def test_cpu_prover_bytes_match_big_integer_prover(oracle, which, k):
         assert pk.perm_commitments == rpk.perm_commitments
         assert pk.transcript_repr == rpk.transcript_repr
         for seed, use_gwc in ((1, False), (3, True)):
-            proof = prover.create_proof_ext(D, params, pk, cols_to_arr(adv), ProverRng(seed), use_gwc, instances=insts)
+            proof = prover.create_proof_ext(D, params, pk, adv_arr, ProverRng(seed), use_gwc, instances=insts)
             want = rp.create_proof(rpk, adv, ProverRng(seed), use_gwc=use_gwc, instances=insts)
             first = next((i for i in range(min(len(proof), len(want))) if proof[i] != want[i]), None)
             assert first is None and len(proof) == len(want), "differs at byte %s (field %s)" % (first, first and first // 32)
@@ -113,6 +125,40 @@ def test_advice_uploads_are_queued_a_few_groups_ahead(oracle, monkeypatch):
     monkeypatch.setenv("H2_SIDE_GROUPS", "0")
     del calls[:]
     assert prover.create_proof_ext(D, params, pk, adv, ProverRng(5), False) == proofs[0] and calls == [16]
+
+
+def test_a_proof_that_raises_releases_what_it_retained(oracle):
+    """a proof that raises half way (a lookup input that is not in the table: the random polynomial is retained by then) must
+    not leave its registrations behind -- on the host-slice device they name memory that is about to be freed, and only the
+    next proof on the SAME device object cleared them"""
+    import oracle_prover as op
+    from halo2_gpu_specific_amd import prover
+    from halo2_gpu_specific_amd.rng import ProverRng
+
+    k, log = 6, []
+
+    class Recording(op.OracleDevice):
+        def retain(self, vectors, owner=None):
+            if owner is None:
+                log.append(("retain", len(vectors)))
+            return super().retain(vectors, owner)
+
+        def release_retained(self):
+            log.append(("release", 0))
+            return super().release_retained()
+
+    adv, fixed, copies, insts = rp.LookupShuffle.synthesize(k)
+    D = Recording(threads=2)
+    params = oracle_params(oracle, D, k)
+    pk = op.keygen(D, params, lookup_shuffle_cs(), cols_to_arr(fixed), [(l[0], l[1], r[0], r[1]) for l, r in copies])
+    bad = [c[:] for c in adv]
+    bad[4][2] = 5                                           # e[2] is not in the table u
+    del log[:]
+    with pytest.raises(prover.H2Error):
+        prover.create_proof_ext(D, params, pk, cols_to_arr(bad), ProverRng(1), False, instances=insts)
+    assert any(name == "retain" and count >= 1 for name, count in log), log
+    last = {name: i for i, (name, _) in enumerate(log)}
+    assert last["release"] > last["retain"], log
 
 
 def test_product_device_still_needs_a_gpu():
