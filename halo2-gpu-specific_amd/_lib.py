@@ -139,10 +139,12 @@ SYMBOLS = {
     "h2_dev_fixed_base_mul": (ctypes.c_int, [_vp, _vp, _sz, _vp, _vp]),
     "h2_g1_ntt_scratch_bytes": (_sz, [_u32]),
     "h2_dev_g1_ntt": (ctypes.c_int, [_vp, _vp, _u32, ctypes.c_int, _vp, _sz, _vp]),
+    "h2_dev_g1_mul_each": (ctypes.c_int, [_vp, _vp, _sz, _vp, _vp]),
     "h2_dev_points_decompress": (ctypes.c_int, [_vp, _sz, _vp, _vp]),
     "h2_dev_points_compress": (ctypes.c_int, [_vp, _sz, _vp, _vp]),
     "h2_pairing_check": (ctypes.c_int, [_vp, _vp, _sz, ctypes.POINTER(ctypes.c_int)]),
     "h2_g2_mul_generator": (ctypes.c_int, [_vp, _vp]),
+    "h2_g2_mul": (ctypes.c_int, [_vp, _vp, _vp]),
     "h2_g2_compress": (ctypes.c_int, [_vp, _vp]),
     "h2_g2_decompress": (ctypes.c_int, [_vp, _vp]),
     "h2_evalh_prepare": (ctypes.c_int, [_vp, _vp]),

@@ -10,6 +10,7 @@
 #include "check.hpp"
 #include "common.hpp"
 #include "evalh.hpp"
+#include "g1mul.hpp"
 #include "g1ntt.hpp"
 #include "g1util.hpp"
 #include "msm.hpp"
@@ -925,6 +926,16 @@ int h2_dev_g1_ntt(const void* d_in, void* d_out, uint32_t log_n, int inverse, vo
         DeviceCtx* ctx = current_ctx();
         return g1_ntt_launch(ctx, (const uint64_t*)d_in, (uint64_t*)d_out, log_n, inverse == 1, d_scratch,
                              pick_stream(ctx, stream));
+    });
+}
+
+int h2_dev_g1_mul_each(const void* d_points, const void* d_scalars, size_t n, void* d_out, void* stream) {
+    if (int rc = g1_mul_each_args(d_points, d_scalars, n, d_out)) return rc;
+    if (n == 0) return H2_OK;
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return g1_mul_each_launch((const uint64_t*)d_points, (const Fr*)d_scalars, n, (uint64_t*)d_out,
+                                  pick_stream(ctx, stream));
     });
 }
 

@@ -1,5 +1,5 @@
 // pairing.cpp -- host-only: the Fq2 / Fq6 / Fq12 tower, G2, the optimal ate Miller loop, the final exponentiation and the
-// four C-ABI entries over them (include/halo2_hip.h: h2_pairing_check, h2_g2_mul_generator, h2_g2_compress,
+// five C-ABI entries over them (include/halo2_hip.h: h2_pairing_check, h2_g2_mul_generator, h2_g2_mul, h2_g2_compress,
 // h2_g2_decompress).  See pairing.hpp for the tower and DESIGN.md for the algorithm choices: affine Miller steps (one Fq2
 // inversion each), a dense Fq12 product per line, the easy part of the final exponentiation by conjugation, inversion and
 // the q^2 Frobenius, the hard part (q^4 - q^2 + 1) / r by plain square-and-multiply.  Every exponent is derived from the two
@@ -532,6 +532,17 @@ int h2_g2_mul_generator(const uint64_t scalar[4], uint64_t out_xy[16]) {
     fq_load(scalar, probe);
     if (!limbs_below(probe.l, FrParams::MOD)) return invalid("h2_g2_mul_generator: the scalar is not below r");
     g2_write(g2_mul(g2_generator(), scalar), out_xy);
+    return H2_OK;
+}
+
+int h2_g2_mul(const uint64_t xy[16], const uint64_t scalar[4], uint64_t out_xy[16]) {
+    if (!xy || !scalar || !out_xy) return invalid("h2_g2_mul: null argument");
+    Fq probe;  // (only the limb split is used)
+    fq_load(scalar, probe);
+    if (!limbs_below(probe.l, FrParams::MOD)) return invalid("h2_g2_mul: the scalar is not below r");
+    G2Affine p;
+    if (const char* why = g2_read(xy, p, true)) return invalid(why);
+    g2_write(g2_mul(p, scalar), out_xy);
     return H2_OK;
 }
 

@@ -1,5 +1,5 @@
 """G2 and the pairing check of the verifier -- host code of libhalo2_hip.so (csrc/pairing.cpp: h2_pairing_check,
-h2_g2_mul_generator, h2_g2_compress, h2_g2_decompress), usable with no device visible.
+h2_g2_mul_generator, h2_g2_mul, h2_g2_compress, h2_g2_decompress), usable with no device visible.
 
 A G2 point is a numpy array of 16 u64: x.c0, x.c1, y.c0, y.c1 in Montgomery form, identity all zeros (the library's 128-byte
 layout).  A G1 point is what the rest of the package uses on the host: (x, y) canonical integers, None for the identity.
@@ -41,6 +41,18 @@ def g2_mul_generator(s):
     scalar = np.array([(s >> (64 * i)) & _M64 for i in range(4)], dtype=np.uint64)
     out = np.zeros(16, dtype=np.uint64)
     if lib().h2_g2_mul_generator(scalar.ctypes.data, out.ctypes.data) != 0:
+        raise PointError(lib().h2_last_error().decode())
+    return out
+
+
+def g2_mul(point, scalar):
+    """[scalar] point for a G2 point of the order-r subgroup -- the G2 side of an SRS update, [s]G2 -> [s tau]G2; PointError
+    for a point off the twist or outside the subgroup"""
+    point = np.ascontiguousarray(point, dtype=np.uint64).reshape(16)
+    scalar %= R_MOD
+    limbs = np.array([(scalar >> (64 * i)) & _M64 for i in range(4)], dtype=np.uint64)
+    out = np.zeros(16, dtype=np.uint64)
+    if lib().h2_g2_mul(point.ctypes.data, limbs.ctypes.data, out.ctypes.data) != 0:
         raise PointError(lib().h2_last_error().decode())
     return out
 

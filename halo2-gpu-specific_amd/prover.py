@@ -1111,6 +1111,24 @@ class Params:
             raise ParamsError(report)
         return report
 
+    def update(self, device, tau=None, tables=None, s_g2=None):
+        """One ceremony contribution -> (new Params, contribution): the SRS of s tau from this SRS of s, without knowing s.
+        new.g[i] = [tau^i] g[i] (h2_dev_g1_mul_each over a copy of g: this object stays valid), new.g_lagrange by
+        from_powers, new.s_g2 = [tau] s_g2; `contribution` is the 64 compressed bytes of [tau]G2, what
+        params_update.verify_update checks the pair (self, new) against.
+
+        tau: an integer in [1, r); None draws 64 bytes of os.urandom, reduced mod r and redrawn when 0; 0 or a value outside
+        the range raises ValueError.  Needs n >= 2 and an [s]G2 -- self.s_g2 (Params.unsafe_setup sets it) or `s_g2` in the
+        forms `verify` accepts (16 limbs or the 64 bytes of an SRS file's additional_data) -- else ValueError; so does a
+        Device in a process group.  `tables`: as the constructor's, for the new object.
+
+        The column tau^i is zeroed on the device before it is released.  tau itself is a Python integer, which CANNOT be
+        wiped: its digits may stay in this process's memory until it exits.  Make a contribution that matters in a process of
+        its own that does nothing else (tools/params_update.py), and let it end."""
+        from .params_update import update_params
+
+        return update_params(device, self, tau=tau, tables=tables, s_g2=s_g2)
+
     @staticmethod
     def synthetic(device, k, seed=0x48414C4F32):
         """Timing-only parameters: two tables of valid curve points with no common trapdoor, so proofs made

@@ -432,6 +432,15 @@ size_t h2_g1_ntt_scratch_bytes(uint32_t log_n);
 int h2_dev_g1_ntt(const void *d_in, void *d_out, uint32_t log_n, int inverse, void *d_scratch, size_t scratch_bytes,
                   void *stream);
 
+/* A table of points times a column of scalars, point by point: d_out[i] = [d_scalars[i]] d_points[i] for i < n.  The work of
+ * an SRS update, g[i] -> [tau^i] g[i] (the reference has no such entry point: its only constructor of an SRS is
+ * Params::unsafe_setup).  Points affine Montgomery, 64 B each, identity (0,0); scalars Montgomery Fr, as
+ * h2_dev_fixed_base_mul takes them.  Every output is the exact group element normalised to the one affine form; a zero
+ * scalar or an identity input gives (0,0).  d_out may equal d_points.  One lane per point over signed 3-bit digits of the
+ * scalar (csrc/g1mul.hip).  Asynchronous on `stream`.  H2_ERR_INVALID, without touching the device, for a null pointer with
+ * n > 0 or n > 2^31; H2_OK for n = 0. */
+int h2_dev_g1_mul_each(const void *d_points, const void *d_scalars, size_t n, void *d_out, void *stream);
+
 /* ---- evaluate_h: the quotient numerator h(X) on the extended coset ------------------------------
  * Evaluator::evaluate_h -- plonk/evaluation.rs:778-1226 (CPU twin) / :1229-1985 (cuda).
  * The Rust side flattens its `Evaluator` (plonk/evaluation.rs:270-296) into this plain descriptor:
@@ -807,6 +816,10 @@ int h2_pairing_check(const uint64_t *g1_xy, const uint64_t *g2_xy, size_t pairs,
 /* out_xy = [scalar] G2 for the plain (not Montgomery) little-endian scalar < r: the `s_g2` that Params::unsafe_setup
  * writes as additional_data (poly/commitment.rs:113-116).  A scalar of r or above is H2_ERR_INVALID. */
 int h2_g2_mul_generator(const uint64_t scalar[4], uint64_t out_xy[16]);
+/* out_xy = [scalar] P for a G2 point P in the layout above and a scalar as h2_g2_mul_generator takes it: the step of an SRS
+ * update on the G2 side, [s]G2 -> [s tau]G2.  P must be on the twist and in the order-r subgroup (the identity is);
+ * otherwise, and for a scalar of r or above, H2_ERR_INVALID.  out_xy may be xy. */
+int h2_g2_mul(const uint64_t xy[16], const uint64_t scalar[4], uint64_t out_xy[16]);
 /* The 64-byte G2 encoding of the SRS file's additional_data and of ParamsVerifier::{write, read} (poly/commitment.rs:392-433):
  * x.c0 then x.c1, 32 bytes little-endian each, bit 7 of byte 63 = the parity of the canonical y.c0 (of y.c1 when y.c0 is
  * zero), identity = zeros -- the G1 convention above extended to Fq2, and like it a convention of this build.  Compress
