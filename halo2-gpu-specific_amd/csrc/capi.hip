@@ -848,7 +848,7 @@ int h2_msm_shape(size_t n, uint32_t max_bits, uint32_t* c, uint32_t* windows, ui
 }
 
 int h2_ntt_shape(uint32_t log_n, uint32_t in_log, h2_ntt_pass_shape* out, size_t cap, size_t* count) {
-    static_assert(sizeof(h2_ntt_pass_shape) == 9 * sizeof(uint32_t), "h2_ntt_pass_shape is nine words");
+    static_assert(sizeof(h2_ntt_pass_shape) == 7 * sizeof(uint32_t), "h2_ntt_pass_shape is seven words");
     if (!count || (cap && !out)) return bad("h2_ntt_shape: null argument");
     if (log_n > 28 || in_log > log_n) return bad("h2_ntt_shape: log_n <= 28 and in_log <= log_n");
     *count = ntt_shape_query(log_n, in_log, (uint32_t*)out, cap);

@@ -162,28 +162,23 @@ __device__ __forceinline__ void lds_put(uint4* lo, uint4* hi, uint32_t i, const 
     hi[i] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
 }
 
-// LAZY: the lazy domain of field.hpp -- values below 4p in LDS and between the passes, products by fp_mul_wide (no final
-// subtraction), bare additions; canonical residues come back at the last pass's store.  Same field elements, same output.
-// FB != 0: the pass geometry as compile-time constants (B = FB bits, 4 columns per tile, no zero-padding skip, RADIX4 lanes):
-// the stage loop unrolls with constant strides, the LDS planes sit at immediate offsets and the loops over a tile collapse to
-// one iteration -- the same instructions on the same operands minus most of the index arithmetic.  FB = 0: everything from `a`.
-// CW: the twiddles this pass reads from tables -- the butterfly twiddles in LDS and the tabulated inter-pass twiddles (tw_direct)
-// -- are (plain value, quotient) pairs and multiply by fp_mul_const: 115 multiply-adds per product instead of 136 (field.hpp).
-// Twiddles COMPOSED at run time (lo x hi of the two-level tables, the coset scales, pre3 / post3) stay Montgomery products.
+// Every pass works in the lazy domain of field.hpp -- values below 4p in LDS and between the passes, products by fp_mul_wide
+// (no final subtraction), bare additions; canonical residues come back at the last pass's store.
+// CW (the radix-4 passes): the twiddles this pass reads from tables -- the butterfly twiddles in LDS and the tabulated
+// inter-pass twiddles (tw_direct) -- are (plain value, quotient) pairs and multiply by fp_mul_const: 115 multiply-adds per
+// product instead of 136 (field.hpp).  Twiddles COMPOSED at run time (lo x hi of the two-level tables, the coset scales,
+// pre3 / post3) stay Montgomery products.
 // DP: tw_direct holds pairs too (the 2^16-entry table of a middle pass: 4 MiB, read out of L2).  The LAST pass's complete table
 // stays in Montgomery form whatever CW says: as pairs it is 64 B per element streamed from HBM next to the 64 B of data, and the
 // pass -- 2.1 GB per launch at 2^24 -- stopped following its instruction count (590 us either way, profiles/r6_ntt_constw.txt).
-template <bool RADIX4, bool LAZY, uint32_t FB = 0, bool CW = false, bool DP = false>
+template <bool RADIX4, bool DP = false>
 __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
-    static_assert(!CW || LAZY, "the constant-operand product returns values of the lazy domain");
+    constexpr bool CW = RADIX4;
     static_assert(!DP || CW, "pairs in tw_direct only next to pairs in tw_bfly");
-    // x * w for a canonical twiddle w: canonical arithmetic, or any x < 2^256 -> a value below 2p
-    auto tmul = [](const Fr& x, const Fr& w) -> Fr {
-        if constexpr (LAZY) return fp_mul_wide(x, w);
-        else return fp_mul(x, w);
-    };
-    const uint32_t B = FB ? FB : a.B, R = 1u << B, log_c = FB ? 2u : a.log_c, C = 1u << log_c;
-    const uint32_t zskip = FB ? 0u : a.zskip;
+    // x * w for a canonical twiddle w: any x < 2^256 -> a value below 2p
+    auto tmul = [](const Fr& x, const Fr& w) -> Fr { return fp_mul_wide(x, w); };
+    const uint32_t B = a.B, R = 1u << B, log_c = a.log_c, C = 1u << log_c;
+    const uint32_t zskip = a.zskip;
     uint4* t_lo = h2_smem;                  // R*C low halves
     uint4* t_hi = t_lo + (R << log_c);      // R*C high halves
     uint4* w_lo = t_hi + (R << log_c);      // R/2 butterfly twiddles, low / high halves
@@ -203,10 +198,9 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
     };
     auto bmul = [](const Fr& x, const Tw& t) __attribute__((always_inline)) -> Fr {
         if constexpr (CW) return fp_mul_const(x, t.w, t.q);
-        else if constexpr (LAZY) return fp_mul_wide(x, t.w);
-        else return fp_mul(x, t.w);
+        else return fp_mul_wide(x, t.w);
     };
-    const uint32_t nthreads = FB ? ((RADIX4 ? (R >> 2) : (R >> 1)) << log_c) : blockDim.x;  // == max(R/2 * C, 1) (RADIX4: half)
+    const uint32_t nthreads = blockDim.x;  // == max(R/2 * C, 1) (RADIX4: half)
     const uint32_t tid = threadIdx.x;
     const Fr* const in_p = a.batch ? a.in_b[blockIdx.y] : a.in;   // (wave-uniform: scalar loads from the kernel arguments)
     Fr* const out_p = a.batch ? a.out_b[blockIdx.y] : a.out;
@@ -372,50 +366,29 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
                 Fr x0 = lds_get(t_lo, t_hi, i0), x1 = lds_get(t_lo, t_hi, i0 + step);
                 Fr x2 = lds_get(t_lo, t_hi, i0 + 2 * step), x3 = lds_get(t_lo, t_hi, i0 + 3 * step);
                 const bool unit = s == 0 || (by_r && r == 0);  // the twiddles of index r are 1 (wave-uniform test)
-                if constexpr (LAZY) {
-                    // rows below 4p: the operands of a product go in as they are, the others are brought below 2p
-                    x0 = fp_lazy_red2p(x0);
-                    x2 = fp_lazy_red2p(x2);
-                    if (!unit) {
-                        const Tw wa = tw_get(r << (B - 1 - s));
-                        x1 = bmul(x1, wa);
-                        x3 = bmul(x3, wa);
-                    } else {
-                        x1 = fp_lazy_red2p(x1);
-                        x3 = fp_lazy_red2p(x3);
-                    }
-                    const Fr y0 = fp_lazy_add_red(x0, x1), y1 = fp_lazy_sub_red(x0, x1);   // below 2p: added to next
-                    Fr y2 = fp_lazy_add(x2, x3), y3 = fp_lazy_sub(x2, x3);                  // below 4p: multiplied next
-                    y2 = unit ? fp_lazy_red2p(y2) : bmul(y2, tw_get(r << (B - 2 - s)));
-                    y3 = bmul(y3, tw_get((r + h) << (B - 2 - s)));
-                    lds_put(t_lo, t_hi, i0, fp_lazy_add(y0, y2));
-                    lds_put(t_lo, t_hi, i0 + 2 * step, fp_lazy_sub(y0, y2));
-                    lds_put(t_lo, t_hi, i0 + step, fp_lazy_add(y1, y3));
-                    lds_put(t_lo, t_hi, i0 + 3 * step, fp_lazy_sub(y1, y3));
+                // rows below 4p: the operands of a product go in as they are, the others are brought below 2p
+                x0 = fp_lazy_red2p(x0);
+                x2 = fp_lazy_red2p(x2);
+                if (!unit) {
+                    const Tw wa = tw_get(r << (B - 1 - s));
+                    x1 = bmul(x1, wa);
+                    x3 = bmul(x3, wa);
                 } else {
-                    if (!unit) {
-                        const Tw wa = tw_get(r << (B - 1 - s));
-                        x1 = bmul(x1, wa);
-                        x3 = bmul(x3, wa);
-                    }
-                    Fr y0 = fp_add(x0, x1), y1 = fp_sub(x0, x1), y2 = fp_add(x2, x3), y3 = fp_sub(x2, x3);
-                    if (!unit) y2 = bmul(y2, tw_get(r << (B - 2 - s)));
-                    y3 = bmul(y3, tw_get((r + h) << (B - 2 - s)));
-                    lds_put(t_lo, t_hi, i0, fp_add(y0, y2));
-                    lds_put(t_lo, t_hi, i0 + 2 * step, fp_sub(y0, y2));
-                    lds_put(t_lo, t_hi, i0 + step, fp_add(y1, y3));
-                    lds_put(t_lo, t_hi, i0 + 3 * step, fp_sub(y1, y3));
+                    x1 = fp_lazy_red2p(x1);
+                    x3 = fp_lazy_red2p(x3);
                 }
+                const Fr y0 = fp_lazy_add_red(x0, x1), y1 = fp_lazy_sub_red(x0, x1);   // below 2p: added to next
+                Fr y2 = fp_lazy_add(x2, x3), y3 = fp_lazy_sub(x2, x3);                  // below 4p: multiplied next
+                y2 = unit ? fp_lazy_red2p(y2) : bmul(y2, tw_get(r << (B - 2 - s)));
+                y3 = bmul(y3, tw_get((r + h) << (B - 2 - s)));
+                lds_put(t_lo, t_hi, i0, fp_lazy_add(y0, y2));
+                lds_put(t_lo, t_hi, i0 + 2 * step, fp_lazy_sub(y0, y2));
+                lds_put(t_lo, t_hi, i0 + step, fp_lazy_add(y1, y3));
+                lds_put(t_lo, t_hi, i0 + 3 * step, fp_lazy_sub(y1, y3));
             }
             __syncthreads();
         };
-        if constexpr (FB != 0) {
-#pragma unroll
-            for (uint32_t s = 0; s + 1 < FB; s += 2) round4(s);
-            s0 = FB & ~1u;
-        } else {
-            for (; s0 + 1 < B; s0 += 2) round4(s0);
-        }
+        for (; s0 + 1 < B; s0 += 2) round4(s0);
     }
     const uint32_t nbf = total >> 1;
     for (uint32_t s = s0; s < B; s++) {
@@ -440,16 +413,10 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
             const uint32_t iu = (i << log_c) + c, iv = ((i + h) << log_c) + c;
             Fr u = lds_get(t_lo, t_hi, iu), v = lds_get(t_lo, t_hi, iv);
             const bool skip = s == 0 || (by_r && r == 0);
-            if constexpr (LAZY) {
-                u = fp_lazy_red2p(u);
-                v = skip ? fp_lazy_red2p(v) : bmul(v, tw_get(r << (B - 1 - s)));
-                lds_put(t_lo, t_hi, iu, fp_lazy_add(u, v));
-                lds_put(t_lo, t_hi, iv, fp_lazy_sub(u, v));
-            } else {
-                if (!skip) v = bmul(v, tw_get(r << (B - 1 - s)));
-                lds_put(t_lo, t_hi, iu, fp_add(u, v));
-                lds_put(t_lo, t_hi, iv, fp_sub(u, v));
-            }
+            u = fp_lazy_red2p(u);
+            v = skip ? fp_lazy_red2p(v) : bmul(v, tw_get(r << (B - 1 - s)));
+            lds_put(t_lo, t_hi, iu, fp_lazy_add(u, v));
+            lds_put(t_lo, t_hi, iv, fp_lazy_sub(u, v));
         }
         __syncthreads();
     }
@@ -474,8 +441,7 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
             for (uint32_t q = 0; q < NE; q++) {
                 const uint32_t i = idx[q] & n_mask;
                 const Fr w = fp_mul(fp_load(a.sc_lo + (i & ((1u << LO_BITS) - 1))), fp_load(a.sc_hi + (i >> LO_BITS)));
-                if constexpr (LAZY) y[q] = fp_reduce_once(fp_mul_wide(y[q], w));
-                else y[q] = fp_mul(y[q], w);
+                y[q] = fp_reduce_once(fp_mul_wide(y[q], w));
             }
         } else if (a.is_last && a.has_post3 && !a.hi_scaled) {
 #pragma unroll
@@ -484,10 +450,9 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
                 Fr w;
 #pragma unroll
                 for (int l = 0; l < 8; l++) w.l[l] = m == 0 ? a.post3[0].l[l] : (m == 1 ? a.post3[1].l[l] : a.post3[2].l[l]);
-                if constexpr (LAZY) y[q] = fp_reduce_once(fp_mul_wide(y[q], w));
-                else y[q] = fp_mul(y[q], w);
+                y[q] = fp_reduce_once(fp_mul_wide(y[q], w));
             }
-        } else if (LAZY && a.is_last) {
+        } else if (a.is_last) {
             // the transform's output is canonical (an intermediate pass hands its values on below 4p: the next pass's
             // inter-pass twiddle product takes them as they are)
 #pragma unroll
@@ -500,8 +465,8 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
 }
 
 // ---------------------------------------------------------------- the common pass, tile ends fused
-// The fixed geometry of k_ntt_pass<true, true, 8, ...> (8 bits, 4 columns, 256 lanes, four elements per lane, lazy domain,
-// nothing skipped; one tile per workgroup, blockIdx.y the vector) with the two ends of a tile taken out of LDS.
+// The radix-4 pass at one fixed geometry (8 bits, 4 columns, 256 lanes, four elements per lane, nothing skipped; one tile
+// per workgroup, blockIdx.y the vector; twiddle tables as pairs, k_ntt_pass's CW) with the two ends of a tile taken out of LDS.
 // The four rows a lane loads are the inputs of ONE unit of the first stage pair, and the four rows a unit of the last stage
 // pair produces are the four a lane stores.  So the first pair runs on the loaded registers (after pre3, the coset pre-scale
 // and the inter-pass twiddle, as before) and writes its outputs to LDS, and the last pair's outputs go through the
@@ -515,15 +480,14 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
 //     writes of the unfused load phase were).
 // The first pair needs ONE butterfly twiddle (index 1 of stage 1, entry 64 of the table) before the tile's first barrier, i.e.
 // before the LDS copy of the table is ordered against its readers: every lane reads that one from the table in memory.
-template <bool CW, bool DP>
+template <bool DP>
 __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
-    static_assert(!DP || CW, "pairs in tw_direct only next to pairs in tw_bfly");
     constexpr uint32_t B = 8, R = 1u << B, log_c = 2, C = 1u << log_c;
     auto tmul = [](const Fr& x, const Fr& w) -> Fr { return fp_mul_wide(x, w); };
     uint4* t_lo = h2_smem;                  // the planes of k_ntt_pass, at the same offsets
     uint4* t_hi = t_lo + (R << log_c);
     uint4* w_lo = t_hi + (R << log_c);
-    uint4* w_hi = w_lo + (R >> 1) + (CW ? 0 : 1);
+    uint4* w_hi = w_lo + (R >> 1);
     uint4* q_lo = w_hi + (R >> 1);
     uint4* q_hi = q_lo + (R >> 1);
     struct Tw {
@@ -532,13 +496,10 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     auto tw_get = [&](uint32_t i) __attribute__((always_inline)) -> Tw {
         Tw t;
         t.w = lds_get(w_lo, w_hi, i);
-        if constexpr (CW) t.q = lds_get(q_lo, q_hi, i);
+        t.q = lds_get(q_lo, q_hi, i);
         return t;
     };
-    auto bmul = [](const Fr& x, const Tw& t) __attribute__((always_inline)) -> Fr {
-        if constexpr (CW) return fp_mul_const(x, t.w, t.q);
-        else return fp_mul_wide(x, t.w);
-    };
+    auto bmul = [](const Fr& x, const Tw& t) __attribute__((always_inline)) -> Fr { return fp_mul_const(x, t.w, t.q); };
     // stages s and s + 1 on the rows p, p + h, p + 2h, p + 3h (h = 2^s) of one column, in registers, twiddle index r = p mod h:
     // the arithmetic of k_ntt_pass's round4, operation for operation; x0 .. x3 come back in row order
     auto unit4 = [&](Fr& x0, Fr& x1, Fr& x2, Fr& x3, const uint32_t s, const uint32_t r, const bool unit, const Tw* w3 = nullptr) __attribute__((always_inline)) {
@@ -600,22 +561,14 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     const uint32_t n_mask = (a.log_n >= 32) ? 0xffffffffu : ((1u << a.log_n) - 1);
 
     if (tid < (R >> 1)) {
-        if constexpr (CW) {
-            lds_put(w_lo, w_hi, tid, fp_load(a.tw_bfly + 2 * tid));
-            lds_put(q_lo, q_hi, tid, fp_load(a.tw_bfly + 2 * tid + 1));
-        } else {
-            lds_put(w_lo, w_hi, tid, fp_load(a.tw_bfly + tid));
-        }
+        lds_put(w_lo, w_hi, tid, fp_load(a.tw_bfly + 2 * tid));
+        lds_put(q_lo, q_hi, tid, fp_load(a.tw_bfly + 2 * tid + 1));
     }
 
     // stage 1's twiddle of index 1 for the first stage pair, straight from the table (wave-uniform address)
     Tw tw64;
-    if constexpr (CW) {
-        tw64.w = fp_load(a.tw_bfly + 2 * (R >> 2));
-        tw64.q = fp_load(a.tw_bfly + 2 * (R >> 2) + 1);
-    } else {
-        tw64.w = fp_load(a.tw_bfly + (R >> 2));
-    }
+    tw64.w = fp_load(a.tw_bfly + 2 * (R >> 2));
+    tw64.q = fp_load(a.tw_bfly + 2 * (R >> 2) + 1);
 
     constexpr uint32_t NE = 4;
     {
@@ -769,43 +722,25 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
 // ---------------------------------------------------------------- pass geometry (shared by the plan builder and the launcher)
 struct PassShape {
     uint32_t log_c, threads;
-    bool radix4, lazy, fixed, cw;
+    bool radix4;  // two stages per LDS round trip, tabulated twiddles as (plain value, quotient) pairs
+    bool fixed;   // the common geometry: 8 bits, tiles of 4 columns, 256 lanes (k_ntt_pass8 when nothing is skipped)
 };
 // `avail`: the columns a tile can take -- log2 of the stride (s_log) for the passes before the last, of the DFT count for the last
 static PassShape pass_shape(uint32_t L, uint32_t B, uint32_t avail) {
-    static const int env_logc = getenv("H2_NTT_LOGC") ? atoi(getenv("H2_NTT_LOGC")) : -1;
-    // two stages per LDS round trip: four elements per lane, half the threads per tile (H2_NTT_RADIX4=0: one stage)
-    static const bool radix4 = !(getenv("H2_NTT_RADIX4") && atoi(getenv("H2_NTT_RADIX4")) == 0);
-    // the lazy domain (field.hpp: values below 4p between load and store, products without their final subtraction);
-    // H2_NTT_LAZY=0 keeps canonical residues everywhere -- same output either way
-    static const bool lazy = !(getenv("H2_NTT_LAZY") && atoi(getenv("H2_NTT_LAZY")) == 0);
-    // the common pass -- 8 bits, tiles of 4 columns, nothing skipped -- has its geometry compiled in (H2_NTT_FIXED=0: generic)
-    static const bool fixed = !(getenv("H2_NTT_FIXED") && atoi(getenv("H2_NTT_FIXED")) == 0);
-    // tabulated twiddles as (plain value, quotient) pairs, multiplied by fp_mul_const (H2_NTT_CONSTW=0: Montgomery tables)
-    static const bool constw = !(getenv("H2_NTT_CONSTW") && atoi(getenv("H2_NTT_CONSTW")) == 0);
     PassShape sh{};
-    uint32_t log_c = (B < 8) ? (10 - B) : 2;  // generic LDS radix-2 kernel: tile = R rows x C columns, about 1024 elements
-    if (env_logc >= 0 && B == 8) log_c = (uint32_t)env_logc;
+    uint32_t log_c = (B < 8) ? (10 - B) : 2;  // tile = R rows x C columns, about 1024 elements
     if (avail < log_c) log_c = avail;
     sh.log_c = log_c;
     uint32_t threads = ((1u << B) >> 1) << log_c;
+    // four elements per lane, half the threads per tile
     // (transforms below 2^18 are latency-bound chains of a few tiles: more lanes per tile finish them sooner)
-    sh.radix4 = radix4 && B >= 2 && threads >= 128 && L >= 18;
+    sh.radix4 = B >= 2 && threads >= 128 && L >= 18;
     if (sh.radix4) threads >>= 1;
     if (threads < 64) threads = 64;
     if (threads > 512) threads = 512;
     sh.threads = threads;
-    sh.lazy = lazy;
-    sh.fixed = fixed && sh.radix4 && lazy && B == 8 && log_c == 2 && threads == 256;
-    sh.cw = constw && sh.radix4 && lazy;
+    sh.fixed = sh.radix4 && B == 8 && log_c == 2 && threads == 256;
     return sh;
-}
-
-// the common pass through k_ntt_pass8 (H2_NTT_FUSE=0: k_ntt_pass<true, true, 8, ...>, the ends of a tile through LDS).
-// Read once, like H2_NTT_FIXED.
-static bool pass8_fuse() {
-    static const bool v = !(getenv("H2_NTT_FUSE") && atoi(getenv("H2_NTT_FUSE")) == 0);
-    return v;
 }
 
 // Rows of the first pass that zero padding leaves live: in_len = 2^(L - z) of 2^L elements prunes the first min(z, B) stages
@@ -819,30 +754,28 @@ static uint32_t pass_zskip(uint32_t L, uint32_t B, size_t p, bool last, uint32_t
 }
 
 // Which kernel a pass runs: one enumerator per launch of ntt_run_chunk (the values are h2_ntt_shape's kernel ids,
-// H2_NTT_KERNEL_* in halo2_hip.h).  The launcher switches on this and h2_ntt_shape reports it: the conditions live here only.
+// H2_NTT_KERNEL_* in halo2_hip.h).  The launcher indexes pass_fn with this and h2_ntt_shape reports it: the conditions live
+// here only.
 enum NttKernel : uint32_t {
-    NK_PASS8_CW_DP = H2_NTT_KERNEL_PASS8_CW_DP,      // k_ntt_pass8<true, true>
-    NK_PASS8_CW = H2_NTT_KERNEL_PASS8_CW,            // k_ntt_pass8<true, false>
-    NK_PASS8 = H2_NTT_KERNEL_PASS8,                  // k_ntt_pass8<false, false>
-    NK_FIXED_CW_DP = H2_NTT_KERNEL_FIXED_CW_DP,      // k_ntt_pass<true, true, 8, true, true>
-    NK_FIXED_CW = H2_NTT_KERNEL_FIXED_CW,            // k_ntt_pass<true, true, 8, true, false>
-    NK_R4_LAZY_CW_DP = H2_NTT_KERNEL_R4_LAZY_CW_DP,  // k_ntt_pass<true, true, 0, true, true>
-    NK_R4_LAZY_CW = H2_NTT_KERNEL_R4_LAZY_CW,        // k_ntt_pass<true, true, 0, true, false>
-    NK_FIXED = H2_NTT_KERNEL_FIXED,                  // k_ntt_pass<true, true, 8>
-    NK_R4_LAZY = H2_NTT_KERNEL_R4_LAZY,              // k_ntt_pass<true, true>
-    NK_R4 = H2_NTT_KERNEL_R4,                        // k_ntt_pass<true, false>
-    NK_R2_LAZY = H2_NTT_KERNEL_R2_LAZY,              // k_ntt_pass<false, true>
-    NK_R2 = H2_NTT_KERNEL_R2,                        // k_ntt_pass<false, false>
+    NK_PASS8_DP = H2_NTT_KERNEL_PASS8_DP,
+    NK_PASS8 = H2_NTT_KERNEL_PASS8,
+    NK_R4_DP = H2_NTT_KERNEL_R4_DP,
+    NK_R4 = H2_NTT_KERNEL_R4,
+    NK_R2 = H2_NTT_KERNEL_R2,
 };
-static NttKernel pass_kernel(const PassShape& sh, uint32_t zskip, bool fuse, bool last) {
-    const bool dp = sh.cw && !last;  // pairs in tw_direct: the middle passes' tables (a first pass has none)
-    const bool fixed = sh.fixed && zskip == 0;
-    if (fixed && fuse) return sh.cw ? (dp ? NK_PASS8_CW_DP : NK_PASS8_CW) : NK_PASS8;
-    if (sh.cw && fixed) return dp ? NK_FIXED_CW_DP : NK_FIXED_CW;
-    if (sh.cw) return dp ? NK_R4_LAZY_CW_DP : NK_R4_LAZY_CW;
-    if (fixed) return NK_FIXED;
-    if (sh.radix4) return sh.lazy ? NK_R4_LAZY : NK_R4;
-    return sh.lazy ? NK_R2_LAZY : NK_R2;
+using PassFn = void (*)(PassArgs);
+static const PassFn pass_fn[H2_NTT_KERNEL_COUNT] = {
+    k_ntt_pass8<true>,        // NK_PASS8_DP
+    k_ntt_pass8<false>,       // NK_PASS8
+    k_ntt_pass<true, true>,   // NK_R4_DP
+    k_ntt_pass<true, false>,  // NK_R4
+    k_ntt_pass<false>,        // NK_R2
+};
+static NttKernel pass_kernel(const PassShape& sh, uint32_t zskip, bool last) {
+    if (!sh.radix4) return NK_R2;
+    const bool dp = !last;  // pairs in tw_direct: the middle passes' tables (a first pass has none)
+    if (sh.fixed && zskip == 0) return dp ? NK_PASS8_DP : NK_PASS8;
+    return dp ? NK_R4_DP : NK_R4;
 }
 
 // ---------------------------------------------------------------- plans
@@ -850,6 +783,13 @@ static std::string plan_key(uint32_t log_n, const uint64_t omega[4]) {
     char buf[128];
     snprintf(buf, sizeof buf, "%u:%016llx%016llx%016llx%016llx", log_n, (unsigned long long)omega[3],
              (unsigned long long)omega[2], (unsigned long long)omega[1], (unsigned long long)omega[0]);
+    return buf;
+}
+
+// the eight limbs of an element, most significant first: the key of a table cached per divisor or generator
+static std::string fr_key(const Fr& v) {
+    char buf[72];
+    snprintf(buf, sizeof buf, "%08x%08x%08x%08x%08x%08x%08x%08x", v.l[7], v.l[6], v.l[5], v.l[4], v.l[3], v.l[2], v.l[1], v.l[0]);
     return buf;
 }
 
@@ -1011,6 +951,82 @@ static bool last_table_make_room(DeviceCtx* ctx, size_t need, bool allow_evict) 
     return ctx->ntt_last_table_bytes + need <= budget;
 }
 
+// A pinned last-pass table: the pin is dropped when the guard goes -- after the pass that reads the table has been launched,
+// or when anything on the way there throws (H2_HIP): a leaked pin would keep the table from ever being evicted and its plan
+// from ever being released.
+struct LastTablePin {
+    NttPlan::LastTable* t = nullptr;
+    LastTablePin() = default;
+    LastTablePin(LastTablePin&& o) noexcept : t(o.t) { o.t = nullptr; }
+    LastTablePin& operator=(LastTablePin&& o) noexcept {
+        std::swap(t, o.t);
+        return *this;
+    }
+    ~LastTablePin() {
+        if (t) {
+            std::lock_guard<std::mutex> g(g_tab_mu);
+            t->users--;
+        }
+    }
+};
+
+// The last pass of a large transform reads its inter-pass twiddles from a complete table (32 B x n, streamed in the order
+// of its loads) instead of composing each from two: one product per element instead of two, on a pass that is bound by
+// VALU issue and has the HBM time to spare (2^24: 1.84 -> see DESIGN 3.2).  One table per divisor folded into it (`d`, null:
+// none), inside the per-device budget (ntt_table_budget: the least recently used idle table leaves first).  Finds the table
+// or builds and publishes it, and returns it pinned; H2_NTT_LAST_TABLE=0, a size outside 2^18 .. 2^H2_NTT_LAST_TABLE_MAX_LOG,
+// no room in the budget or a failed allocation return none: the pass then composes its twiddles (lo x hi).
+static LastTablePin last_table_pin(DeviceCtx* ctx, NttPlan* pl, uint32_t B, const Fr* d, hipStream_t stream) {
+    static const bool last_table = !(getenv("H2_NTT_LAST_TABLE") && atoi(getenv("H2_NTT_LAST_TABLE")) == 0);
+    static const uint32_t last_table_max = getenv("H2_NTT_LAST_TABLE_MAX_LOG") ? (uint32_t)atoi(getenv("H2_NTT_LAST_TABLE_MAX_LOG")) : 26u;
+    const uint32_t L = pl->log_n;
+    LastTablePin pinned;
+    if (!last_table || L < 18 || L > last_table_max) return pinned;
+    const std::string key = d ? fr_key(*d) : std::string();
+    const size_t bytes = sizeof(Fr) << L;   // (Montgomery form also under CW: see k_ntt_pass's DP)
+    auto pin = [&]() -> NttPlan::LastTable* {  // with g_tab_mu held
+        auto it = pl->last_direct.find(key);
+        if (it == pl->last_direct.end() || it->second.ptr == nullptr) return nullptr;
+        it->second.users++;
+        it->second.last_use = ++g_tick;
+        return &it->second;
+    };
+    bool may_evict = false;
+    {
+        std::lock_guard<std::mutex> g(g_tab_mu);
+        pinned.t = pin();
+        if (!pinned.t) may_evict = ++pl->last_misses[key] >= 2;   // see last_table_make_room
+    }
+    if (pinned.t || !last_table_make_room(ctx, bytes, may_evict)) return pinned;
+    // built outside the lock (a table is 0.5 .. 2 GiB of powers); a second builder of the same table loses
+    Fr* tab = nullptr;
+    if (hipMalloc(&tab, bytes) != hipSuccess) {
+        (void)hipGetLastError();  // no room on the device: this transform composes its twiddles
+        tab = nullptr;
+    } else {
+        hipLaunchKernelGGL(k_last_table, dim3((1u << L) / 256), dim3(256), 0, stream, tab, pl->w, B, L, d ? *d : pl->w,
+                           d ? 1u : 0u, 0u);
+        H2_HIP(hipStreamSynchronize(stream));  // complete before other streams can find it
+    }
+    Fr* loser = nullptr;
+    {
+        std::lock_guard<std::mutex> g(g_tab_mu);
+        pinned.t = pin();
+        if (pinned.t) {
+            loser = tab;
+        } else if (tab) {
+            NttPlan::LastTable& e = pl->last_direct[key];
+            e.ptr = tab;
+            e.bytes = bytes;
+            ctx->ntt_last_table_bytes += bytes;
+            pl->last_misses[key] = 0;  // evicted later, it has to miss twice again before it displaces others
+            pinned.t = pin();
+        }
+    }
+    if (loser) (void)hipFree(loser);
+    return pinned;
+}
+
 PlanRef ntt_get_plan(DeviceCtx* ctx, uint32_t log_n, const uint64_t omega[4], hipStream_t stream) {
     std::string key = plan_key(log_n, omega);
     {
@@ -1039,7 +1055,7 @@ PlanRef ntt_get_plan(DeviceCtx* ctx, uint32_t log_n, const uint64_t omega[4], hi
         for (size_t p = 0; p < pl->bits.size(); p++) {
             const uint32_t B = pl->bits[p];
             const bool last = p + 1 == pl->bits.size();
-            pl->cw.push_back(pass_shape(log_n, B, last ? consumed : log_n - consumed - B).cw ? 1 : 0);
+            pl->cw.push_back(pass_shape(log_n, B, last ? consumed : log_n - consumed - B).radix4 ? 1 : 0);
             consumed += B;
         }
     }
@@ -1123,13 +1139,7 @@ static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr
 // The two-level table of g^i (i < 2^log_n) with `d` folded into the high level, cached with the plan: the coset transforms
 // of a proof use quotient_poly_degree generators per direction, again and again.
 ScaleTabRef ntt_scale_table(NttPlan* pl, const Fr& g, const Fr* d, hipStream_t stream) {
-    char kb[200];
-    int at = 0;
-    for (int l = 7; l >= 0; l--) at += snprintf(kb + at, sizeof kb - at, "%08x", g.l[l]);
-    kb[at++] = d ? '*' : '.';
-    if (d)
-        for (int l = 7; l >= 0; l--) at += snprintf(kb + at, sizeof kb - at, "%08x", d->l[l]);
-    const std::string key(kb, (size_t)at);
+    const std::string key = d ? fr_key(g) + '*' + fr_key(*d) : fr_key(g) + '.';
     {
         std::lock_guard<std::mutex> lk(pl->mu);
         auto it = pl->scale_tabs.find(key);
@@ -1229,7 +1239,7 @@ static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr
             a.batch = cnt;
             for (uint32_t i = 0; i < cnt; i++) { a.in_b[i] = srcs[i]; a.out_b[i] = dsts[i]; }
         }
-        hipLaunchKernelGGL((k_ntt_pass<false, false>), dim3(1, cnt), dim3(64), 4 * sizeof(Fr), stream, a);
+        hipLaunchKernelGGL(pass_fn[NK_R2], dim3(1, cnt), dim3(64), 4 * sizeof(Fr), stream, a);
         H2_HIP(hipGetLastError());
         return;
     }
@@ -1277,9 +1287,7 @@ static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr
         a.zskip = pass_zskip(L, B, p, last, in_len);
         if (last && p > 0 && a.post3_uniform && L > LO_BITS) {
             // iNTT: fold the divisor into the high twiddle table used by the last pass's inter-pass twiddles
-            char key[80];
-            snprintf(key, sizeof key, "%08x%08x%08x%08x%08x%08x%08x%08x", post3[0].l[7], post3[0].l[6], post3[0].l[5],
-                     post3[0].l[4], post3[0].l[3], post3[0].l[2], post3[0].l[1], post3[0].l[0]);
+            const std::string key = fr_key(post3[0]);
             Fr* scaled = nullptr;
             {
                 std::lock_guard<std::mutex> g(pl->mu);
@@ -1298,130 +1306,41 @@ static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr
             a.tw_hi = scaled;
             a.hi_scaled = 1;
         }
-        // The last pass of a large transform reads its inter-pass twiddles from a complete table (32 B x n, streamed in the
-        // order of its loads) instead of composing each from two: one product per element instead of two, on a pass that
-        // is bound by VALU issue and has the HBM time to spare (2^24: 1.84 -> see DESIGN 3.2).  One table per divisor
-        // folded into it, inside the per-device budget (ntt_table_budget: the least recently used idle table leaves
-        // first); H2_NTT_LAST_TABLE=0, no room in the budget or a failed allocation leave the lo x hi form.
-        static const bool last_table = !(getenv("H2_NTT_LAST_TABLE") && atoi(getenv("H2_NTT_LAST_TABLE")) == 0);
-        static const uint32_t last_table_max = getenv("H2_NTT_LAST_TABLE_MAX_LOG") ? (uint32_t)atoi(getenv("H2_NTT_LAST_TABLE_MAX_LOG")) : 26u;
-        NttPlan::LastTable* used_table = nullptr;
-        // the pin is dropped when this pass has been launched -- or when anything on the way there throws (H2_HIP): a leaked
-        // pin would keep the table from ever being evicted and its plan from ever being released
-        struct Pin {
-            NttPlan::LastTable* t = nullptr;
-            ~Pin() {
-                if (t) {
-                    std::lock_guard<std::mutex> g(g_tab_mu);
-                    t->users--;
-                }
-            }
-        } pinned;
-        if (last && p > 0 && last_table && L >= 18 && L <= last_table_max) {
-            const bool scaled = a.hi_scaled != 0;
-            std::string key;
-            if (scaled) {
-                char kb[80];
-                snprintf(kb, sizeof kb, "%08x%08x%08x%08x%08x%08x%08x%08x", post3[0].l[7], post3[0].l[6], post3[0].l[5],
-                         post3[0].l[4], post3[0].l[3], post3[0].l[2], post3[0].l[1], post3[0].l[0]);
-                key = kb;
-            }
-            const size_t bytes = sizeof(Fr) << L;   // (Montgomery form also under CW: see k_ntt_pass's DP)
-            auto pin = [&]() -> NttPlan::LastTable* {  // with g_tab_mu held
-                auto it = pl->last_direct.find(key);
-                if (it == pl->last_direct.end() || it->second.ptr == nullptr) return nullptr;
-                it->second.users++;
-                it->second.last_use = ++g_tick;
-                return &it->second;
-            };
-            bool may_evict = false;
-            {
-                std::lock_guard<std::mutex> g(g_tab_mu);
-                used_table = pin();
-                if (!used_table) may_evict = ++pl->last_misses[key] >= 2;   // see last_table_make_room
-            }
-            pinned.t = used_table;
-            if (!used_table && last_table_make_room(ctx, bytes, may_evict)) {
-                // built outside the lock (a table is 0.5 .. 2 GiB of powers); a second builder of the same table loses
-                Fr* tab = nullptr;
-                if (hipMalloc(&tab, bytes) != hipSuccess) {
-                    (void)hipGetLastError();  // no room on the device: this transform composes its twiddles
-                    tab = nullptr;
-                } else {
-                    hipLaunchKernelGGL(k_last_table, dim3((1u << L) / 256), dim3(256), 0, stream, tab, pl->w, B, L,
-                                       scaled ? post3[0] : pl->w, scaled ? 1u : 0u, 0u);
-                    H2_HIP(hipStreamSynchronize(stream));  // complete before other streams can find it
-                }
-                Fr* loser = nullptr;
-                {
-                    std::lock_guard<std::mutex> g(g_tab_mu);
-                    used_table = pin();
-                    if (used_table) {
-                        loser = tab;
-                    } else if (tab) {
-                        NttPlan::LastTable& e = pl->last_direct[key];
-                        e.ptr = tab;
-                        e.bytes = bytes;
-                        ctx->ntt_last_table_bytes += bytes;
-                        pl->last_misses[key] = 0;  // evicted later, it has to miss twice again before it displaces others
-                        used_table = pin();
-                    }
-                }
-                if (loser) (void)hipFree(loser);
-                pinned.t = used_table;
-            }
-            if (used_table != nullptr) {
-                a.tw_direct = used_table->ptr;
-                a.direct_kmajor = 1;
-            }
+        // (the pin is dropped when this pass has been launched -- or when anything on the way there throws)
+        LastTablePin last_tab;
+        if (last && p > 0) last_tab = last_table_pin(ctx, pl, B, a.hi_scaled ? &post3[0] : nullptr, stream);
+        if (last_tab.t != nullptr) {
+            a.tw_direct = last_tab.t->ptr;
+            a.direct_kmajor = 1;
         }
         {
             const PassShape sh = pass_shape(L, B, last ? consumed : a.s_log);
-            const bool cw = pl->cw[p] != 0;   // (== sh.cw: the plan's tables were built for it)
+            const bool cw = pl->cw[p] != 0;   // (== sh.radix4: the plan's tables were built for it)
             a.log_c = sh.log_c;
             a.radix4 = sh.radix4 ? 1u : 0u;
             const uint32_t R = 1u << B, C = 1u << sh.log_c, threads = sh.threads;
             const uint32_t ntiles = (1u << L) / (R * C);
             // tile planes + butterfly twiddles: R/2 values and a pad, or (CW) R/2 pairs exactly -- 40 KiB for the common pass
             const size_t lds = cw ? ((size_t)R * C + R) * sizeof(Fr) : ((size_t)R * C + (R >> 1) + 2) * sizeof(Fr);
-            if (lds > 64 * 1024) {  // beyond the default dynamic LDS limit: raise it once
+            if (lds > 64 * 1024) {  // beyond the default dynamic LDS limit: raise it once (k_ntt_pass8's tile is 40 KiB)
                 static bool raised[64] = {};  // per device
                 const int dev = ctx->device;
                 if (dev < 0 || dev >= 64 || !raised[dev]) {
-                    H2_HIP(hipFuncSetAttribute((const void*)k_ntt_pass<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    H2_HIP(hipFuncSetAttribute((const void*)k_ntt_pass<true, true, 0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    H2_HIP(hipFuncSetAttribute((const void*)k_ntt_pass<true, true, 0, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    H2_HIP(hipFuncSetAttribute((const void*)k_ntt_pass<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    H2_HIP(hipFuncSetAttribute((const void*)k_ntt_pass<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    H2_HIP(hipFuncSetAttribute((const void*)k_ntt_pass<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                    for (NttKernel k : {NK_R4_DP, NK_R4, NK_R2})
+                        H2_HIP(hipFuncSetAttribute((const void*)pass_fn[k], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                     if (dev >= 0 && dev < 64) raised[dev] = true;
                 }
             }
-#define H2_NTT_LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(ntiles, cnt), dim3(threads), lds, stream, a)
-            switch (pass_kernel(sh, a.zskip, pass8_fuse(), last)) {
-                case NK_PASS8_CW_DP: H2_NTT_LAUNCH(k_ntt_pass8<true, true>); break;
-                case NK_PASS8_CW: H2_NTT_LAUNCH(k_ntt_pass8<true, false>); break;
-                case NK_PASS8: H2_NTT_LAUNCH(k_ntt_pass8<false, false>); break;
-                case NK_FIXED_CW_DP: H2_NTT_LAUNCH(k_ntt_pass<true, true, 8, true, true>); break;
-                case NK_FIXED_CW: H2_NTT_LAUNCH(k_ntt_pass<true, true, 8, true, false>); break;
-                case NK_R4_LAZY_CW_DP: H2_NTT_LAUNCH(k_ntt_pass<true, true, 0, true, true>); break;
-                case NK_R4_LAZY_CW: H2_NTT_LAUNCH(k_ntt_pass<true, true, 0, true, false>); break;
-                case NK_FIXED: H2_NTT_LAUNCH(k_ntt_pass<true, true, 8>); break;
-                case NK_R4_LAZY: H2_NTT_LAUNCH(k_ntt_pass<true, true>); break;
-                case NK_R4: H2_NTT_LAUNCH(k_ntt_pass<true, false>); break;
-                case NK_R2_LAZY: H2_NTT_LAUNCH(k_ntt_pass<false, true>); break;
-                case NK_R2: H2_NTT_LAUNCH(k_ntt_pass<false, false>); break;
-            }
-#undef H2_NTT_LAUNCH
+            hipLaunchKernelGGL(pass_fn[pass_kernel(sh, a.zskip, last)], dim3(ntiles, cnt), dim3(threads), lds, stream, a);
         }
-        // (`pinned` unpins here: launched -- an eviction from here on synchronises the device before it frees)
+        // (`last_tab` unpins here: launched -- an eviction from here on synchronises the device before it frees)
         consumed += B;
     }
     H2_HIP(hipGetLastError());
 }
 
-// The plan of a transform as the launcher will run it (h2_ntt_shape): per pass 9 words -- bits, log_c, threads, radix4, lazy,
-// fixed, cw, zskip, kernel id.  Host only: nothing is allocated or launched.
+// The plan of a transform as the launcher will run it (h2_ntt_shape): per pass 7 words -- bits, log_c, threads, radix4,
+// fixed, zskip, kernel id.  Host only: nothing is allocated or launched.
 size_t ntt_shape_query(uint32_t log_n, uint32_t in_log, uint32_t* out, size_t cap) {
     std::vector<uint32_t> bits;
     ntt_split(log_n, bits);
@@ -1431,9 +1350,8 @@ size_t ntt_shape_query(uint32_t log_n, uint32_t in_log, uint32_t* out, size_t ca
         const bool last = p + 1 == bits.size();
         const PassShape sh = pass_shape(log_n, B, last ? consumed : log_n - consumed - B);
         const uint32_t zskip = pass_zskip(log_n, B, p, last, 1u << in_log);
-        const uint32_t row[9] = {B, sh.log_c, sh.threads, sh.radix4, sh.lazy, sh.fixed, sh.cw, zskip,
-                                 (uint32_t)pass_kernel(sh, zskip, pass8_fuse(), last)};
-        for (int i = 0; i < 9; i++) out[9 * p + i] = row[i];
+        const uint32_t row[7] = {B, sh.log_c, sh.threads, sh.radix4, sh.fixed, zskip, (uint32_t)pass_kernel(sh, zskip, last)};
+        for (int i = 0; i < 7; i++) out[7 * p + i] = row[i];
         consumed += B;
     }
     return bits.size();

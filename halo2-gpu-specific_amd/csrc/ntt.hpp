@@ -17,7 +17,7 @@ struct NttPlan {
     std::vector<const Fr*> tw_bfly;    // per pass: (w^(n/R))^e, e < R/2
     std::vector<const Fr*> tw_direct;  // per pass: full inter-pass twiddle table or nullptr
     // per pass: 1 = its tw_bfly / tw_direct / last-pass tables hold (plain value, floor(value 2^256 / r)) PAIRS, the operands of
-    // the constant-operand product fp_mul_const (the radix-4 lazy passes of transforms >= 2^18; H2_NTT_CONSTW=0: none)
+    // the constant-operand product fp_mul_const (the radix-4 passes: transforms >= 2^18)
     std::vector<uint8_t> cw;
     size_t table_bytes = 0;            // of `tables` and the per-pass direct tables
     std::mutex mu;                     // guards scaled_hi, last_direct
@@ -130,7 +130,7 @@ void ntt_run_many(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr* const*
                   uint32_t in_len, const Fr* pre3, const Fr* post3, hipStream_t stream, const Fr* scale_tab = nullptr,
                   uint32_t scale_mode = 0);
 Fr fr_from_u64x4(const uint64_t v[4]);
-// h2_ntt_shape: the passes of a 2^log_n transform over 2^in_log live inputs, 9 words each into out[0 .. 9 * min(passes, cap));
+// h2_ntt_shape: the passes of a 2^log_n transform over 2^in_log live inputs, 7 words each into out[0 .. 7 * min(passes, cap));
 // returns the number of passes.  Uses the launcher's own ntt_split / pass_shape / kernel selector and knobs.
 size_t ntt_shape_query(uint32_t log_n, uint32_t in_log, uint32_t* out, size_t cap);
 

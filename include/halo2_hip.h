@@ -665,27 +665,18 @@ typedef struct {
     uint32_t bits;    /* width of the pass: 2^bits rows per tile */
     uint32_t log_c;   /* 2^log_c columns per tile */
     uint32_t threads; /* lanes per workgroup */
-    uint32_t radix4;  /* two stages per LDS round trip */
-    uint32_t lazy;    /* values below 4p between load and store */
-    uint32_t fixed;   /* the compiled-in geometry: 8 bits, 4 columns, 256 lanes */
-    uint32_t cw;      /* constant-operand twiddles, (value, quotient) pairs */
+    uint32_t radix4;  /* two stages per LDS round trip, constant-operand twiddles ((value, quotient) pairs) */
+    uint32_t fixed;   /* the common geometry: 8 bits, 4 columns, 256 lanes */
     uint32_t zskip;   /* leading stages pruned by zero padding: min(log_n - in_log, bits) on the first of several passes */
     uint32_t kernel;  /* H2_NTT_KERNEL_* */
 } h2_ntt_pass_shape;
 enum {
-    H2_NTT_KERNEL_PASS8_CW_DP = 0,   /* k_ntt_pass8<true, true> */
-    H2_NTT_KERNEL_PASS8_CW = 1,      /* k_ntt_pass8<true, false> */
-    H2_NTT_KERNEL_PASS8 = 2,         /* k_ntt_pass8<false, false> */
-    H2_NTT_KERNEL_FIXED_CW_DP = 3,   /* k_ntt_pass<true, true, 8, true, true> */
-    H2_NTT_KERNEL_FIXED_CW = 4,      /* k_ntt_pass<true, true, 8, true, false> */
-    H2_NTT_KERNEL_R4_LAZY_CW_DP = 5, /* k_ntt_pass<true, true, 0, true, true> */
-    H2_NTT_KERNEL_R4_LAZY_CW = 6,    /* k_ntt_pass<true, true, 0, true, false> */
-    H2_NTT_KERNEL_FIXED = 7,         /* k_ntt_pass<true, true, 8> */
-    H2_NTT_KERNEL_R4_LAZY = 8,       /* k_ntt_pass<true, true> */
-    H2_NTT_KERNEL_R4 = 9,            /* k_ntt_pass<true, false> */
-    H2_NTT_KERNEL_R2_LAZY = 10,      /* k_ntt_pass<false, true> */
-    H2_NTT_KERNEL_R2 = 11,           /* k_ntt_pass<false, false> */
-    H2_NTT_KERNEL_COUNT = 12
+    H2_NTT_KERNEL_PASS8_DP = 0, /* k_ntt_pass8<true>: the common 8-bit pass, not last */
+    H2_NTT_KERNEL_PASS8 = 1,    /* k_ntt_pass8<false>: the common 8-bit pass, last */
+    H2_NTT_KERNEL_R4_DP = 2,    /* k_ntt_pass<true, true>: another width or padding to skip, from 2^18, not last */
+    H2_NTT_KERNEL_R4 = 3,       /* k_ntt_pass<true, false>: the same, last */
+    H2_NTT_KERNEL_R2 = 4,       /* k_ntt_pass<false>: every pass below 2^18 */
+    H2_NTT_KERNEL_COUNT = 5
 };
 int h2_ntt_shape(uint32_t log_n, uint32_t in_log, h2_ntt_pass_shape *out, size_t cap, size_t *count);
 int h2_dev_msm(const void *d_scalars, const void *d_bases, size_t n, uint32_t max_bits, void *d_scratch,

@@ -28,25 +28,18 @@ ORACLE_THREADS = 8
 
 # h2_ntt_shape's kernel ids (H2_NTT_KERNEL_* in include/halo2_hip.h): one per launch of ntt_run_chunk
 KERNELS = (
-    "k_ntt_pass8<true, true>",
-    "k_ntt_pass8<true, false>",
-    "k_ntt_pass8<false, false>",
-    "k_ntt_pass<true, true, 8, true, true>",
-    "k_ntt_pass<true, true, 8, true, false>",
-    "k_ntt_pass<true, true, 0, true, true>",
-    "k_ntt_pass<true, true, 0, true, false>",
-    "k_ntt_pass<true, true, 8>",
+    "k_ntt_pass8<true>",
+    "k_ntt_pass8<false>",
     "k_ntt_pass<true, true>",
     "k_ntt_pass<true, false>",
-    "k_ntt_pass<false, true>",
-    "k_ntt_pass<false, false>",
+    "k_ntt_pass<false>",
 )
 ALL_KERNELS = frozenset(range(len(KERNELS)))
-# with no knob set: the fused common pass (middle and last), the generic constant-operand kernel (a first pass of
-# another width or with padding to skip; the 9-bit last pass), and below 2^18 the radix-2 lazy kernel
-DEFAULT_KERNELS = frozenset({0, 1, 5, 6, 10})
+# the common pass (middle and last), the radix-4 kernel (a first pass of another width or with padding to skip; the 9-bit
+# last pass), and below 2^18 the radix-2 kernel: every kernel runs with no knob set
+DEFAULT_KERNELS = ALL_KERNELS
 
-SHAPE_FIELDS = ("bits", "log_c", "threads", "radix4", "lazy", "fixed", "cw", "zskip", "kernel")
+SHAPE_FIELDS = ("bits", "log_c", "threads", "radix4", "fixed", "zskip", "kernel")
 
 OPS = ("ntt", "intt", "coeff_to_extended", "extended_to_coeff", "coset_ntt", "coset_intt")
 # where the entry point allows both, source == destination and source != destination
@@ -70,21 +63,11 @@ BATCH_COUNTS = (1, 2, 16, 17)
 BATCH_OPS = ("ntt_batch", "intt_batch", "coset_ntt_batch", "coeff_to_extended_batch")
 
 # one child process per setting (each knob is read once per process)
-KNOBS = ("H2_NTT_CONSTW", "H2_NTT_LAZY", "H2_NTT_RADIX4", "H2_NTT_FIXED", "H2_NTT_NINE", "H2_NTT_NO_ZSKIP",
-         "H2_NTT_LAST_TABLE", "H2_NTT_FUSE", "H2_NTT_LOGC", "H2_NTT_LAST_TABLE_MAX_LOG", "H2_NTT_TABLE_BUDGET")
+KNOBS = ("H2_NTT_NINE", "H2_NTT_NO_ZSKIP", "H2_NTT_LAST_TABLE", "H2_NTT_LAST_TABLE_MAX_LOG", "H2_NTT_TABLE_BUDGET")
 KNOB_SETTINGS = (
-    {"H2_NTT_CONSTW": "0"},
-    {"H2_NTT_LAZY": "0"},
-    {"H2_NTT_RADIX4": "0"},
-    {"H2_NTT_FIXED": "0"},
     {"H2_NTT_NINE": "0"},
     {"H2_NTT_NO_ZSKIP": "1"},
     {"H2_NTT_LAST_TABLE": "0"},
-    # the unfused common pass is compared with the fused one by test_gpu_ntt_fused.py; these two settings are here for the
-    # three instantiations that only H2_NTT_FUSE=0 reaches (k_ntt_pass<true, true, 8, ...>; without the constant-operand
-    # twiddles k_ntt_pass<true, true, 8>), compared with the oracle like the rest
-    {"H2_NTT_FUSE": "0"},
-    {"H2_NTT_FUSE": "0", "H2_NTT_CONSTW": "0"},
 )
 CHILD_SIZES = (17, 18, 19, 20)
 CHILD_INPUTS = ("random", "rm1")

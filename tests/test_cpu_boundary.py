@@ -191,8 +191,8 @@ NTT_PASS_WIDTHS = {  # the comment in ntt_split: as many 8-bit passes as possibl
 
 def test_ntt_shape_reports_the_documented_plan():
     """h2_ntt_shape, log_n 0 .. 28 and every padding: the pass widths ntt_split documents, summing to log_n; zskip = min(z, B)
-    on the first of several passes and 0 elsewhere; the fixed geometry is 8 bits, 4 columns, 256 lanes; radix-4 and the
-    constant-operand twiddles from 2^18 only; a kernel id inside the enumeration"""
+    on the first of several passes and 0 elsewhere; the fixed geometry is 8 bits, 4 columns, 256 lanes; radix-4 (and with it
+    the constant-operand twiddles) from 2^18 only; a kernel id inside the enumeration"""
     import ntt_matrix_cases as mc
 
     L = h2.lib()
@@ -206,8 +206,8 @@ def test_ntt_shape_reports_the_documented_plan():
             for i, p in enumerate(passes):
                 assert p["zskip"] == (min(z, p["bits"]) if i == 0 and len(passes) > 1 else 0), (log_n, in_log, i)
                 if p["fixed"]:
-                    assert (p["bits"], p["log_c"], p["threads"]) == (8, 2, 256) and p["radix4"] and p["lazy"]
-                assert p["lazy"] == 1 and p["radix4"] == p["cw"] == (1 if log_n >= 18 else 0), (log_n, p)
+                    assert (p["bits"], p["log_c"], p["threads"]) == (8, 2, 256) and p["radix4"]
+                assert p["radix4"] == (1 if log_n >= 18 else 0), (log_n, p)
                 assert p["fixed"] == (1 if log_n >= 18 and p["bits"] == 8 and p["log_c"] == 2 else 0), (log_n, p)
                 assert 64 <= p["threads"] <= 512 and p["kernel"] in mc.ALL_KERNELS
                 consumed = sum(q["bits"] for q in passes[:i])
@@ -215,16 +215,16 @@ def test_ntt_shape_reports_the_documented_plan():
                 assert p["log_c"] <= avail
                 last = i + 1 == len(passes)
                 if log_n < 18:
-                    assert mc.KERNELS[p["kernel"]] == "k_ntt_pass<false, true>"
+                    assert mc.KERNELS[p["kernel"]] == "k_ntt_pass<false>"
                 elif p["fixed"] and p["zskip"] == 0:
-                    assert mc.KERNELS[p["kernel"]] == ("k_ntt_pass8<true, false>" if last else "k_ntt_pass8<true, true>")
+                    assert mc.KERNELS[p["kernel"]] == ("k_ntt_pass8<false>" if last else "k_ntt_pass8<true>")
                 else:
-                    assert mc.KERNELS[p["kernel"]] == "k_ntt_pass<true, true, 0, true, %s>" % ("false" if last else "true")
+                    assert mc.KERNELS[p["kernel"]] == "k_ntt_pass<true, %s>" % ("false" if last else "true")
 
 
 def test_ntt_shape_bad_arguments():
     L = h2.lib()
-    out = np.zeros((8, 9), dtype=np.uint32)
+    out = np.zeros((8, 7), dtype=np.uint32)
     count = ctypes.c_size_t(77)
     assert L.h2_ntt_shape(29, 0, out.ctypes.data, 8, ctypes.byref(count)) == 1     # H2_ERR_INVALID: beyond the 2-adicity
     assert L.h2_ntt_shape(20, 21, out.ctypes.data, 8, ctypes.byref(count)) == 1    # more live inputs than points
@@ -240,14 +240,14 @@ def test_ntt_shape_bad_arguments():
 
 def test_ntt_matrix_enumerates_without_a_gpu_and_reaches_every_default_kernel():
     """tests/ntt_matrix_cases.py, the rows of tests/test_gpu_ntt_matrix.py: enumerated here with h2_ntt_shape alone.  At least
-    one row maps to every kernel reachable with default knobs and to no other, so a change of ntt_split or pass_shape that
+    one row with default knobs maps to each of the five kernels of ntt_run_chunk, so a change of ntt_split or pass_shape that
     silently moves the coverage fails on any machine; the paddings sit around the first pass's width"""
     import ntt_matrix_cases as mc
 
     L = h2.lib()
     reach = mc.matrix_kernel_ids(L)
     assert set(reach) == set(mc.DEFAULT_KERNELS), {mc.KERNELS[k]: v[:3] for k, v in reach.items()}
-    assert len(mc.KERNELS) == 12 and mc.DEFAULT_KERNELS < mc.ALL_KERNELS
+    assert len(mc.KERNELS) == 5 and mc.DEFAULT_KERNELS == mc.ALL_KERNELS == frozenset(range(5))
     assert mc.MATRIX_SIZES == (9, 10, 16, 17) + tuple(range(18, 25))
     for log_n in mc.MATRIX_SIZES:
         cases = mc.matrix_cases(L, log_n)
@@ -268,14 +268,12 @@ def test_ntt_matrix_enumerates_without_a_gpu_and_reaches_every_default_kernel():
         cases = mc.child_cases(L, log_n)
         assert {c.op for c in cases} == set(mc.OPS) and {c.inp for c in cases} == {"random", "rm1"}
         assert {c.z for c in cases} == {0, 1, mc.first_width(L, log_n)}
-    assert [s for s in mc.KNOB_SETTINGS if len(s) == 1 and "H2_NTT_FUSE" not in s] == [
-        {"H2_NTT_CONSTW": "0"}, {"H2_NTT_LAZY": "0"}, {"H2_NTT_RADIX4": "0"}, {"H2_NTT_FIXED": "0"}, {"H2_NTT_NINE": "0"},
-        {"H2_NTT_NO_ZSKIP": "1"}, {"H2_NTT_LAST_TABLE": "0"}]
+    assert list(mc.KNOB_SETTINGS) == [{"H2_NTT_NINE": "0"}, {"H2_NTT_NO_ZSKIP": "1"}, {"H2_NTT_LAST_TABLE": "0"}]
 
 
 def test_ntt_shape_under_every_knob_reaches_every_kernel():
     """the knob settings of the matrix's child processes, here with h2_ntt_shape alone (a child process each: the knobs are
-    read once): together with the default rows they reach all twelve kernels of ntt_run_chunk"""
+    read once): each setting's rows run the kernels recorded here, all five of ntt_run_chunk between them"""
     import ntt_matrix_cases as mc
 
     code = (
@@ -287,9 +285,9 @@ def test_ntt_shape_under_every_knob_reaches_every_kernel():
         "        ids |= mc.kernel_ids(L, log_n, c.z)\n"
         "print('KERNELS', *sorted(ids))\n"
     ) % (ROOT, os.path.join(ROOT, "tests"))
-    reached = set(mc.DEFAULT_KERNELS)
-    # what each setting's rows run: the settings that reach nothing new run the default kernels in other geometries
-    want = [{2, 8, 10}, {9, 11}, {10}, {5, 6, 10}, {0, 1, 5, 10}, {0, 1, 5, 6, 10}, {0, 1, 5, 6, 10}, {3, 4, 5, 6, 10}, {7, 8, 10}]
+    reached = set()
+    # what each setting's rows run: the same kernels as the default rows, in other geometries and with other twiddle sources
+    want = [{0, 1, 2, 4}, {0, 1, 2, 3, 4}, {0, 1, 2, 3, 4}]
     assert len(want) == len(mc.KNOB_SETTINGS)
     for knobs, want_ids in zip(mc.KNOB_SETTINGS, want):
         env = {k: v for k, v in os.environ.items() if k not in mc.KNOBS}
