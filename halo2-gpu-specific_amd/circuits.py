@@ -2,7 +2,7 @@
 (commented out in the reference tree; the only create_proof-running circuit without selectors -- SURVEY.md 8(d))."""
 import numpy as np
 
-from .circuit import ConstraintSystem
+from .circuit import R_MOD, Constant, ConstraintSystem
 
 
 def mini_plonk():
@@ -260,8 +260,6 @@ def shuffle_gates(width=4, theta=111, beta=222):
     """`MyConfig::configure` of examples/shuffle.rs:50-107: a shuffle argument written out as GATES -- fixed q_shuffle,
     q_first, q_last; advice original[W], shuffled[W] and a running product z with z(first) = z(last) = 1 and
     z(X) (compress(original) + beta) = z(wX) (compress(shuffled) + beta), theta and beta being CONSTANTS of the circuit"""
-    from .circuit import Constant
-
     cs = ConstraintSystem("shuffle-gates-%d-%d-%d" % (width, theta, beta))
     q_shuffle, q_first, q_last = cs.fixed_column(), cs.fixed_column(), cs.fixed_column()
     original = [cs.advice_column() for _ in range(width)]
@@ -291,8 +289,6 @@ def shuffle_gates_witness(k, width=4, height=32, theta=111, beta=222, seed=0x534
     running product z[0] = 1, z[i + 1] = z[i] (compress(original_i) + beta) / (compress(shuffled_i) + beta).
     Returns (advice[2 W + 1], fixed[3]) as lists of n integers."""
     import random
-
-    from .circuit import R_MOD
 
     n = 1 << k
     assert height + 1 <= n - 6

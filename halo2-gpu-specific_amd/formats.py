@@ -24,10 +24,12 @@ import struct
 
 import numpy as np
 
-from . import circuit
 from ._lib import check
-from .prover import Params
-from .transcript import point_to_bytes
+from .cs_format import _Reader, _u32, cs_fetch, cs_store
+from .pairing import g1_limbs, g2_compress, g2_decompress
+from .params import Params
+from .transcript import _MONT_INV_Q, Q_MOD, point_from_bytes, point_to_bytes
+from .verifier import ParamsVerifier
 
 
 def params_write(device, params, path, additional_data=b""):
@@ -95,16 +97,12 @@ def _checked(device, params, additional, verify, seed):
 
 def params_additional_data(params):
     """the additional_data `params_write` should carry for a verifier: the compressed [s]G2 of Params.unsafe_setup"""
-    from .pairing import g2_compress
-
     return g2_compress(params.s_g2)
 
 
 def params_verifier_write(pv, path, device=None):
     """ParamsVerifier::write (poly/commitment.rs:392-404).  The Lagrange points are compressed on the host unless they live
     on a device and `device` is given (h2_dev_points_compress)."""
-    from .pairing import g2_compress
-
     size = pv.public_inputs_size
     with open(path, "wb") as f:
         f.write(struct.pack("<II", pv.k, size))
@@ -118,8 +116,6 @@ def params_verifier_write(pv, path, device=None):
             with torch.cuda.stream(device.tstream):
                 f.write(out.cpu().numpy().tobytes())
         else:
-            from .transcript import _MONT_INV_Q, Q_MOD
-
             raw = np.ascontiguousarray(pv.lagrange_host()[:size], dtype=np.uint64).tobytes()
             for i in range(size):
                 x, y = (int.from_bytes(raw[64 * i + 32 * j:64 * i + 32 * j + 32], "little") * _MONT_INV_Q % Q_MOD for j in range(2))
@@ -130,10 +126,6 @@ def params_verifier_read(path, device=None):
     """ParamsVerifier::read (poly/commitment.rs:406-433) -> verifier.ParamsVerifier.  With a `device` the Lagrange points
     are decompressed there and stay resident; without one they are decompressed on the host (public inputs are few) and
     uploaded when a device first commits to them.  IOError / ValueError for a file that is cut short or holds a bad point."""
-    from .pairing import g1_limbs, g2_decompress
-    from .transcript import point_from_bytes
-    from .verifier import ParamsVerifier
-
     with open(path, "rb") as f:
         head = f.read(8 + 32 + 64 + 64)
         if len(head) != 168:
@@ -186,190 +178,7 @@ def witness_fetch(path, k):
 #   fixed commitments, permutation commitments (32 B compressed each, plonk.rs:60-67) |
 #   fixed columns: u32 count, each u32 n + n x 32 B raw (Montgomery) Fr (helpers.rs:182-199, 237-253) |
 #   permutation mapping: u32 columns, u32 length per column, then (u32 column, u32 row) pairs (helpers.rs:114-179)
-# Every integer is a little-endian u32; rotations are stored as `i32 as u32`; field constants as their canonical
-# 32-byte little-endian representation.  Selectors are compiled away before a key is written (keygen.rs:357).
-_ANY = {"advice": 0, "fixed": 1, "instance": 2}          # plonk/circuit.rs:79-86
-_ANY_NAME = {v: k for k, v in _ANY.items()}
-_E_CONSTANT, _E_FIXED, _E_ADVICE, _E_INSTANCE, _E_NEGATED, _E_SUM, _E_PRODUCT, _E_SCALED = range(8)   # helpers.rs:590-599
-
-
-def _u32(v):
-    return struct.pack("<I", v & 0xFFFFFFFF)
-
-
-class _Reader:
-    def __init__(self, buf):
-        self.buf, self.pos = buf, 0
-
-    def take(self, n):
-        if self.pos + n > len(self.buf):
-            raise IOError("truncated circuit data")
-        out = self.buf[self.pos:self.pos + n]
-        self.pos += n
-        return out
-
-    def u32(self):
-        return struct.unpack("<I", self.take(4))[0]
-
-    def i32(self):
-        return struct.unpack("<i", self.take(4))[0]
-
-    def fr(self):
-        v = int.from_bytes(self.take(32), "little")
-        if v >= circuit.R_MOD:
-            raise IOError("non-canonical field element in circuit data")
-        return v
-
-
-def _expression_store(cs, e, out):
-    """Expression::store (helpers.rs:687-757)"""
-    if isinstance(e, circuit.Constant):
-        out += [_u32(_E_CONSTANT), (e.v % circuit.R_MOD).to_bytes(32, "little")]
-    elif isinstance(e, circuit.Query):
-        code, kind = {circuit.Fixed: (_E_FIXED, "fixed"), circuit.Advice: (_E_ADVICE, "advice"),
-                      circuit.Instance: (_E_INSTANCE, "instance")}[type(e)]
-        out += [_u32(code), _u32(cs.get_any_query_index((kind, e.column), e.rotation)), _u32(e.column), _u32(e.rotation)]
-    elif isinstance(e, circuit.Negated):
-        out.append(_u32(_E_NEGATED))
-        _expression_store(cs, e.e, out)
-    elif isinstance(e, (circuit.Sum, circuit.Product)):
-        out.append(_u32(_E_SUM if isinstance(e, circuit.Sum) else _E_PRODUCT))
-        _expression_store(cs, e.a, out)
-        _expression_store(cs, e.b, out)
-    elif isinstance(e, circuit.Scaled):
-        out.append(_u32(_E_SCALED))
-        _expression_store(cs, e.e, out)
-        out.append((e.c % circuit.R_MOD).to_bytes(32, "little"))
-    else:
-        raise TypeError("cannot serialise %r" % (e,))
-
-
-def _expression_fetch(r):
-    """Expression::fetch (helpers.rs:628-685)"""
-    code = r.u32()
-    if code == _E_CONSTANT:
-        return circuit.Constant(r.fr())
-    if code in (_E_FIXED, _E_ADVICE, _E_INSTANCE):
-        r.u32()  # query_index: implied by the query lists
-        column, rotation = r.u32(), r.i32()
-        return {_E_FIXED: circuit.Fixed, _E_ADVICE: circuit.Advice, _E_INSTANCE: circuit.Instance}[code](column, rotation)
-    if code == _E_NEGATED:
-        return circuit.Negated(_expression_fetch(r))
-    if code in (_E_SUM, _E_PRODUCT):
-        a = _expression_fetch(r)
-        b = _expression_fetch(r)
-        return (circuit.Sum if code == _E_SUM else circuit.Product)(a, b)
-    if code == _E_SCALED:
-        e = _expression_fetch(r)
-        return circuit.Scaled(e, r.fr())
-    raise IOError("unknown expression code %d" % code)
-
-
-def _expressions_store(cs, exprs, out):
-    out.append(_u32(len(exprs)))
-    for e in exprs:
-        _expression_store(cs, e, out)
-
-
-def _expressions_fetch(r):
-    return [_expression_fetch(r) for _ in range(r.u32())]
-
-
-def _queried_cells(e, cells):
-    """the (column, rotation) pairs a gate polynomial touches, in first-use order (Gate::queried_cells)"""
-    if isinstance(e, circuit.Query):
-        cell = (e.name, e.column, e.rotation)
-        if cell not in cells:
-            cells.append(cell)
-    for child in ("e", "a", "b"):
-        if hasattr(e, child):
-            _queried_cells(getattr(e, child), cells)
-
-
-def cs_store(cs):
-    """write_cs (helpers.rs:406-456) -> bytes"""
-    out = [_u32(cs.num_advice), _u32(cs.num_instance), _u32(0), _u32(cs.num_fixed), _u32(len(cs.num_advice_queries))]
-    out += [_u32(v) for v in cs.num_advice_queries]
-    out += [_u32(0), _u32(0)]                                   # selector_map, constants: no selectors / constant columns
-    for queries in (cs.advice_queries, cs.instance_queries, cs.fixed_queries):
-        out.append(_u32(len(queries)))
-        for column, rotation in queries:
-            out += [_u32(column), _u32(rotation)]
-    out.append(_u32(len(cs.perm_columns)))
-    for kind, index in cs.perm_columns:
-        out += [_u32(index), _u32(_ANY[kind])]
-    out.append(_u32(len(cs.lookups)))
-    for _, table, sets in cs.lookups:
-        out.append(_u32(len(sets)))
-        for st in sets:
-            out.append(_u32(len(st)))
-            for inputs in st:
-                _expressions_store(cs, inputs, out)
-        _expressions_store(cs, table, out)
-    out.append(_u32(len(cs.shuffles)))
-    for group in cs.shuffles:
-        out.append(_u32(len(group)))
-        for _, inputs, shuffle in group:
-            _expressions_store(cs, inputs, out)
-            _expressions_store(cs, shuffle, out)
-    out.append(_u32(len(cs.range_checks)))                      # range_check arguments (helpers.rs:444-451)
-    for origin, sort, vmin, vmax, step in cs.range_checks:
-        out += [_u32(origin), _u32(sort), _u32(vmin), _u32(vmax), _u32(step)]
-    out.append(_u32(0))                                         # named_advices
-    out.append(_u32(len(cs.gates)))
-    for _, polys in cs.gates:
-        _expressions_store(cs, polys, out)
-        cells = []
-        for p in polys:
-            _queried_cells(p, cells)
-        out.append(_u32(len(cells)))
-        for kind, column, rotation in cells:
-            out += [_u32(column), _u32(_ANY[kind]), _u32(rotation)]
-    return b"".join(out)
-
-
-def cs_fetch(r, name="circuit"):
-    """read_cs (helpers.rs:458-561) -> ConstraintSystem; refuses what this prover does not implement (selectors that
-    were not compiled away, constant columns)"""
-    cs = circuit.ConstraintSystem(name)
-    cs.num_advice, cs.num_instance = r.u32(), r.u32()
-    if r.u32():
-        raise IOError("circuit data with live selectors")
-    cs.num_fixed = r.u32()
-    cs.num_advice_queries = [r.u32() for _ in range(r.u32())]
-    selector_map = [r.u32() for _ in range(r.u32())]
-    constants = [r.u32() for _ in range(r.u32())]
-    del selector_map, constants                                 # keygen-time information only
-    lists = []
-    for _ in range(3):
-        lists.append([(r.u32(), r.i32()) for _ in range(r.u32())])
-    cs.advice_queries, cs.instance_queries, cs.fixed_queries = lists
-    for _ in range(r.u32()):
-        index, kind = r.u32(), r.u32()
-        cs.perm_columns.append((_ANY_NAME[kind], index))
-    for _ in range(r.u32()):
-        sets = [[_expressions_fetch(r) for _ in range(r.u32())] for _ in range(r.u32())]
-        table = _expressions_fetch(r)
-        cs.lookups.append(("", table, sets))
-    for _ in range(r.u32()):
-        group = []
-        for _ in range(r.u32()):
-            inputs = _expressions_fetch(r)
-            group.append(("", inputs, _expressions_fetch(r)))
-        cs.shuffles.append(group)
-    for _ in range(r.u32()):                                    # range_check arguments (helpers.rs:520-536)
-        cs.range_checks.append((r.u32(), r.u32(), r.u32(), r.u32(), r.u32()))
-    for _ in range(r.u32()):                                    # named_advices: (String, u32)
-        r.take(r.u32())
-        r.u32()
-    for _ in range(r.u32()):
-        polys = _expressions_fetch(r)
-        for _ in range(r.u32()):
-            r.take(12)                                          # queried cells: recomputable from the polynomials
-        cs.gates.append(("", polys))
-    return cs
-
-
+# Every integer is a little-endian u32 (the constraint system's own encoding: cs_format.py).
 def circuit_data_write(path, device, params, pk):
     """CircuitData::write for a key made by prover.keygen"""
     cs, n = pk.cs, params.n

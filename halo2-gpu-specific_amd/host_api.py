@@ -16,12 +16,21 @@ step-by-step forms `h2_permutation_terms`, `h2_batch_invert`, `h2_prefix_product
 `HostSliceLib.calls`; nothing is staged through device tensors by hand any more (`STAGED` is empty).  The proof bytes are
 those of the resident prover.
 """
+import concurrent.futures
+import contextlib
 import ctypes
+import threading
+import time
+import weakref
 
 import numpy as np
 
-from . import prover as P
 from ._lib import check, lib
+from .assigned import ASSIGNED_STATUS_WORDS
+from .device import Device, max_scalar_bits
+from .domain import DELTA, _fr
+from .params import Params
+from .transcript import R_MOD, fr_from_mont_limbs, fr_to_mont_limbs, jacobians_to_affine
 
 _vp = ctypes.c_void_p
 STAGED = ()
@@ -46,8 +55,6 @@ class _TimedLib:
     of a proof's wall time is the host's own handling of its vectors (allocating, first-touching and freeing them)"""
 
     def __init__(self, inner):
-        import threading
-
         self._inner, self._mu = inner, threading.Lock()
         self._active, self._since = 0, 0.0
         self.busy_seconds = self.summed_seconds = 0.0
@@ -59,8 +66,6 @@ class _TimedLib:
             self.by_call = {}
 
     def __getattr__(self, name):
-        import time
-
         fn = getattr(self._inner, name)
         if not callable(fn):
             return fn
@@ -87,12 +92,10 @@ class _TimedLib:
 
 
 class HostSliceLib:
-    """the entry points prover.py calls (h2_dev_* signatures), each forwarded to the host-slice entry point the Rust patch
+    """the entry points device.py and prover.py call (h2_dev_* signatures), each forwarded to the host-slice entry point the Rust patch
     binds; pointers are host addresses"""
 
     def __init__(self, torch, dev, workers=4):
-        import concurrent.futures
-
         self.R = _TimedLib(lib())
         self.torch, self.dev = torch, dev
         self.calls = {}
@@ -262,7 +265,7 @@ class _NullStream:
 
 
 class _HostCuda:
-    """the stream plumbing of prover.Device with host tensors: nothing is asynchronous (every entry point returns with
+    """the stream plumbing of device.Device with host tensors: nothing is asynchronous (every entry point returns with
     its result in host memory)"""
     Stream = Event = _NullStream
 
@@ -270,8 +273,6 @@ class _HostCuda:
         self._torch = torch
 
     def stream(self, _):
-        import contextlib
-
         return contextlib.nullcontext()
 
     def set_device(self, _):
@@ -290,8 +291,8 @@ class _HostTorch:
         return getattr(self._torch, name)
 
 
-class HostApiDevice(P.Device):
-    """prover.Device whose vectors are host tensors and whose library is `HostSliceLib` (see the module docstring).
+class HostApiDevice(Device):
+    """device.Device whose vectors are host tensors and whose library is `HostSliceLib` (see the module docstring).
     `quotient_from_coeffs`: create_proof_ext hands the evaluator COEFFICIENT forms and makes one h2_evaluate_h_coeff
     call per circuit instance, as `Evaluator::evaluate_h` under the cuda / hip feature does."""
     quotient_from_coeffs = True
@@ -357,7 +358,7 @@ class HostApiDevice(P.Device):
         return self.torch.from_numpy(a.view(np.int32 if a.dtype == np.uint32 else np.int64))
 
     def _assigned_call(self, num, nforms, den, dforms, rows, counts, outs, count, n, out_form):
-        status = np.zeros(count * P.ASSIGNED_STATUS_WORDS, dtype=np.uint32)
+        status = np.zeros(count * ASSIGNED_STATUS_WORDS, dtype=np.uint32)
         self.L._count("h2_assigned_resolve")
         check(self.L.R.h2_assigned_resolve(num, nforms, den, dforms, rows, counts, outs, count, n, out_form, status.ctypes.data),
               "h2_assigned_resolve")
@@ -379,7 +380,7 @@ class HostApiDevice(P.Device):
         # (a job carries an address, not a tensor: a pool thread keeps its last job alive until the next one arrives, and a
         # page-locked block that cannot go back to the allocator's cache costs the next proof a fresh hipHostMalloc)
         jobs = [(ci, c.data_ptr() + 32 * lo, min(step, n - lo)) for ci, c in enumerate(cols) for lo in range(0, n, step)]
-        one = lambda job: (job[0], P.max_scalar_bits(_bytes_at(job[1], 32 * job[2]).view(np.uint64).reshape(-1, 4)))       # noqa: E731
+        one = lambda job: (job[0], max_scalar_bits(_bytes_at(job[1], 32 * job[2]).view(np.uint64).reshape(-1, 4)))       # noqa: E731
         done = [one(j) for j in jobs] if parts == 1 else list(self.L.pool.map(one, jobs))
         bits = [0] * len(cols)
         for ci, b in done:
@@ -390,24 +391,18 @@ class HostApiDevice(P.Device):
         return "extended", None
 
     def msm_async(self, scalars, bases, n, max_bits=254):
-        import concurrent.futures
-
         fut = concurrent.futures.Future()
         fut.set_result(self.msm(scalars, bases, n, max_bits))
         return fut
 
     def intt(self, t, dom):
         """lagrange_to_coeff in place (poly/domain.rs:233-266): one h2_intt call (no scratch vector on the host side)"""
-        from .prover import _fr
-
         check(self.L.h2_dev_intt(t.data_ptr(), None, _fr(dom.omega_inv), _fr(dom.ifft_divisor), dom.k, None), "h2_intt")
         return t
 
     def intt_to(self, t, dom):
         """the coefficient form of a column whose values are kept: h2_intt_to reads `t` and writes a new vector (the reference
         clones the column and transforms the clone in place, plonk/prover.rs:643-646)"""
-        from .prover import _fr
-
         out = self.empty(dom.n)
         wi, dv = _fr(dom.omega_inv), _fr(dom.ifft_divisor)
         self.L._count("h2_intt_to")
@@ -416,7 +411,7 @@ class HostApiDevice(P.Device):
 
     def intt_on_side_stream(self, cols, dom, extend=False):
         ptrs = [(t.data_ptr(), self.empty(dom.n)) for t in cols]                 # (addresses for the worker threads)
-        wi, dv = P._fr(dom.omega_inv), P._fr(dom.ifft_divisor)
+        wi, dv = _fr(dom.omega_inv), _fr(dom.ifft_divisor)
 
         def one(job):
             self.L._count("h2_intt_to")
@@ -432,8 +427,6 @@ class HostApiDevice(P.Device):
         """one grand-product column of the permutation argument by ONE host-slice call (h2_permutation_product: the set's
         value / sigma columns in, z out; permutation/prover.rs:72-165) -> (z, z[probe]).  `fused_permutation=False` at
         construction keeps the step-by-step calls (h2_permutation_terms, h2_batch_invert, h2_eval_op, h2_prefix_product)."""
-        from .prover import DELTA, _fr
-
         z = self.empty(n)
         vp = (_vp * len(values))(*[t.data_ptr() for t in values])
         sp = (_vp * len(sigmas))(*[t.data_ptr() for t in sigmas])
@@ -445,8 +438,6 @@ class HostApiDevice(P.Device):
     def logup_grand_sum(self, inputs, table, m, n, beta, init, probe):
         """one grand-sum column of a logup lookup by ONE host-slice call (h2_logup_grand_sum: the set's compressed inputs -- and,
         for the first set, the table and its multiplicities -- in, z out; plonk/logup/prover.rs:243-347) -> (z, z[probe])"""
-        from .prover import _fr
-
         z = self.empty(n)
         ip = (_vp * len(inputs))(*[t.data_ptr() for t in inputs])
         scalars = [_fr(beta), _fr(init)]
@@ -459,8 +450,6 @@ class HostApiDevice(P.Device):
         """h(X) in coefficient form by ONE host-slice call (h2_quotient_poly_coeff: evaluate_h from coefficient forms, the
         division by the vanishing polynomial and extended_to_coeff on the device; only n * quotient_poly_degree coefficients
         cross PCIe)"""
-        from .prover import _fr
-
         out_len = dom.n * dom.quotient_poly_degree
         out = self.empty(out_len)
         scalars = [_fr(v) for v in (dom.g_coset, dom.g_coset_inv, dom.extended_omega_inv, dom.extended_ifft_divisor)]
@@ -473,8 +462,6 @@ class HostApiDevice(P.Device):
         """sum over `sets` = [(polys, coeffs, low, points)] of (sum_i coeffs[i] polys[i] - low) / prod_j (X - points[j]) by ONE
         host-slice call (h2_quotient_sum; poly/multiopen/shplonk/prover.rs:95-153, :205-219) -> (the n coefficients, the
         remainders of the divisions as integers or None)"""
-        from .prover import R_MOD, fr_from_mont_limbs, fr_to_mont_limbs
-
         def flat(values):
             return np.array([fr_to_mont_limbs(v % R_MOD) for v in values], dtype=np.uint64).reshape(-1, 4)
 
@@ -499,8 +486,6 @@ class HostApiDevice(P.Device):
         """Params::commit_lagrange_and_ifft (poly/commitment.rs:144-197 -> gpu_multiexp_bound_and_fft, arithmetic.rs:375-410):
         one h2_msm_intt call per column -- the commitment over `bases` and, sharing the one upload, the column taken to its
         coefficient form in place.  -> the commitments (affine), as msm_batch returns them"""
-        from .prover import _fr, jacobians_to_affine
-
         if not cols:
             return []
         out = np.zeros((len(cols), 12), dtype=np.uint64)
@@ -519,8 +504,6 @@ class HostApiDevice(P.Device):
         """final host vectors -> registered with the library: every later host-slice call that READS one of them (the evaluator's
         columns, h2_eval_polynomial, h2_lincomb operands, h2_kate_division) uses a device copy uploaded once.  `owner`: kept
         for the owner's life (the proving key); otherwise until release_retained (the end of the proof)."""
-        import weakref
-
         if not self.register_polys:
             return
         R = self.L.R
@@ -554,10 +537,8 @@ def _unregister(R, ptrs):
 def params_like(device, params):
     """`params` (tables of a HIP device) as the reference's Params: host vectors, registered with the library once
     (crate::hip::register_params in the patch) -- one device copy + shifted-base table per process"""
-    import weakref
-
     g, gl = device._pin(params.g.cpu().contiguous()), device._pin(params.g_lagrange.cpu().contiguous())
-    out = P.Params(device, params.k, g, gl, tables=False)
+    out = Params(device, params.k, g, gl, tables=False)
     R = device.L.R
     for t in (g, gl):
         check(R.h2_bases_register(t.data_ptr(), params.n), "h2_bases_register")

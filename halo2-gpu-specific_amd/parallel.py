@@ -16,6 +16,8 @@ The path shards over independent units; DESIGN.md section 6 has
     (bench.py's NTT leg: one polynomial per GPU, no collective).
 """
 import ctypes
+import os
+import time
 
 import numpy as np
 
@@ -47,9 +49,7 @@ def g1_sum(points):
 
 
 def _empty_like(t):
-    """an uninitialised vector of which only a part will be written (poisoned under H2_POISON_EMPTY=1, prover.POISON_EMPTY)"""
-    import os
-
+    """an uninitialised vector of which only a part will be written (poisoned under H2_POISON_EMPTY=1, device.POISON_EMPTY)"""
     import torch
 
     out = torch.empty_like(t)
@@ -143,16 +143,12 @@ class _traced:
 
     def __enter__(self):
         if COMM_TRACE is not None:
-            import time
-
             self._sync()
             self.t0 = time.perf_counter()
         return self
 
     def __exit__(self, *exc):
         if self.t0 is not None and COMM_TRACE is not None:
-            import time
-
             self._sync()
             COMM_TRACE.append([None, self.name, time.perf_counter() - self.t0, self.nbytes])
         return False
@@ -323,8 +319,6 @@ def broadcast_columns_begin(cols, owners, group=None, stream=None, side=None):
     arrival = _Arrival(works, stream)
     if COMM_TRACE is not None:
         # a traced proof: the transfer alone, serialised (the timed proofs run it under the next phase's compute)
-        import time
-
         stream.synchronize()
         t0 = time.perf_counter()
         arrival.wait()
@@ -336,7 +330,7 @@ def broadcast_columns_begin(cols, owners, group=None, stream=None, side=None):
 
 # ---- coset sharding of the extended-domain phase ---------------------------------------------------------------------
 def coset_plan(c, world, rank):
-    """c cosets (the quotient_poly_degree = degree - 1 cosets that determine the quotient, prover.Device.coset_plan) over
+    """c cosets (the quotient_poly_degree = degree - 1 cosets that determine the quotient, device.Device.coset_plan) over
     `world` ranks: shards = min(c, world) groups; rank r works on the cosets j = r mod shards (ranks beyond c replicate
     a shard).  Returns (shards, owned cosets)."""
     shards = min(c, world)
@@ -445,7 +439,7 @@ def exchange_row_slices(columns, owners, n, G, g, halo_lo, halo_hi, group=None, 
 # range its share of every range-split MSM consumes).  Elementwise passes and linear combinations need nothing else; the
 # three operations with a dependency ACROSS the range -- prefix scans, Kate division, Horner evaluation -- exchange one field
 # element per rank (an all-gather of world x 32 B) and finish locally.  The helpers below are that arithmetic on host
-# integers; the device work is prover.py's.
+# integers; the device work is device.py's.
 MASK64 = (1 << 64) - 1
 
 

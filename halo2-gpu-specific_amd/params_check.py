@@ -23,7 +23,9 @@ from collections import namedtuple
 import numpy as np
 
 from ._lib import check
+from .domain import Domain
 from .pairing import g1_limbs, g1_neg, g2_decompress, g2_generator, pairing_check
+from .rng import ProverRng
 
 NONCANONICAL, IDENTITY, OFF_CURVE = 0, 1, 2           # H2_SRS_* (include/halo2_hip.h): h2_check_record.kind
 FORBID_IDENTITY = 1                                   # H2_SRS_FORBID_IDENTITY
@@ -137,10 +139,7 @@ def _bisect(n, fails):
 
 
 def verify_params(device, params, s_g2=None, seed=None, locate=True, max_failures=64):
-    """`Params.verify` (prover.py) -- see there and the module text"""
-    from .prover import Domain
-    from .rng import ProverRng
-
+    """`Params.verify` (params.py) -- see there and the module text"""
     D, torch = device, device.torch
     if D.group_size > 1 or D.force_collective:
         raise ValueError("Params.verify: one device is the scope -- not a Device in a process group")

@@ -28,10 +28,14 @@ their tau made.  A multi-party transcript (who contributed, in which order, each
 tau in Python.  The column tau^i is zeroed on the device before it is released, but `tau` itself is a Python integer:
 Python cannot wipe it, and copies of its digits may sit anywhere in the interpreter's heap until the process ends.  Run an
 update that matters in a process of its own that does nothing else and exits (tools/params_update.py)."""
+import hashlib
 import os
+import time
 from collections import namedtuple
 
 from ._lib import check
+from .arithmetic import OP_CONSTANT
+from .domain import _fr
 from .pairing import PointError, g1_neg, g2_compress, g2_decompress, g2_generator, g2_mul, g2_mul_generator, pairing_check
 from .params_check import ParamsError, describe as describe_params, parse_s_g2
 from .transcript import Q_MOD, R_MOD
@@ -51,8 +55,6 @@ def draw_tau():
 
 def tau_from_seed(seed):
     """a tau in [1, r) that is a function of `seed` alone -- FOR TESTS ONLY: whoever knows the seed knows tau"""
-    import hashlib
-
     digest = hashlib.blake2b(b"params_update test seed" + int(seed).to_bytes(16, "little", signed=True), digest_size=64).digest()
     return int.from_bytes(digest, "little") % (R_MOD - 1) + 1
 
@@ -75,13 +77,8 @@ def g1_mul_each(device, points, scalars, out=None):
 
 
 def update_params(device, params, tau=None, tables=None, s_g2=None, timings=None):
-    """`Params.update` (prover.py) -- see there and the module text.  `timings`: a dict that receives the milliseconds of
+    """`Params.update` (params.py) -- see there and the module text.  `timings`: a dict that receives the milliseconds of
     each phase (powers, scale, g1_ntt, g2_mul, total), with a synchronisation between them (tools/params_update.py --bench)."""
-    import time
-
-    from .arithmetic import OP_CONSTANT
-    from .prover import Params, _fr
-
     D, L, torch = device, device.L, device.torch
     if D.group_size > 1 or D.force_collective:
         raise ValueError("Params.update: one device is the scope -- not a Device in a process group")
@@ -119,7 +116,7 @@ def update_params(device, params, tau=None, tables=None, s_g2=None, timings=None
         constant.zero_()
         scalars.zero_()
     phase("scale")
-    new = Params.from_powers(D, k, g, tables)
+    new = type(params).from_powers(D, k, g, tables)
     phase("g1_ntt")
     new.s_g2 = g2_mul(s_g2, tau)
     contribution = contribution_of(tau)

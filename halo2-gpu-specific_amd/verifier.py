@@ -12,12 +12,16 @@
 A rejected proof is the return value False; what was wrong with it is a typed error (VerifyError and its subclasses,
 transcript.TranscriptError, pairing.PointError) that `pair_msm` raises and `verify_proof*` turn into False.
 """
+import time
+
 import numpy as np
 
 from . import circuit as hc
 from ._lib import check
 from .pairing import PointError, g1_limbs, g1_neg, g2_decompress, g2_generator, pairing_check
-from .prover import DELTA, Domain, _intermediate_sets, _horner, _lagrange_interpolate, _vanishing, vk_digest
+from .cs_format import vk_digest
+from .domain import DELTA, Domain
+from .multiopen import _horner, _intermediate_sets, _lagrange_interpolate, _vanishing
 from .transcript import (Blake2bRead, R_MOD, TranscriptError, fr_to_mont_limbs, g1_add_affine, point_from_bytes)
 
 G1_GENERATOR = (1, 2)
@@ -542,8 +546,6 @@ def verify_proof_ext(device, params, vk, proof, instances=(), use_gwc=True, circ
     """verifier.rs:128-507 (`verify_proof_ext`): True iff the proof is accepted.  params: a ParamsVerifier; vk: a VerifyingKey
     (or a ProvingKey); instances / circuits as `pair_msm`.  timings: a dict that receives the seconds of the four phases;
     report: a dict that receives the reason of a rejection under "error"."""
-    import time
-
     marks = [time.perf_counter()]
     try:
         vk = _as_vk(vk)
@@ -615,8 +617,6 @@ class BatchVerifier:
         return r
 
     def finalize(self):
-        import time
-
         marks = [time.perf_counter()]
         try:
             sets, spans = [], []

@@ -12,7 +12,7 @@ from check_reference import COPY, GATE, LOOKUP, SHUFFLE, reference_check
 
 import halo2_gpu_specific_amd as h2
 from halo2_gpu_specific_amd import circuit as hc
-from halo2_gpu_specific_amd import circuits, prover
+from halo2_gpu_specific_amd import check, circuits, prover
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import prover_fuzz  # noqa: E402
@@ -111,7 +111,7 @@ def test_records_to_failures_sorting_and_truncation():
 
 def test_assert_satisfied_message_names_gates_lookups_and_columns():
     cs = tiny()
-    text = [prover._describe_failure(f) for f in prover.check_failures(cs, [(GATE, 1, 0, 3), (LOOKUP, 0, 2 << 16 | 1, 7),
+    text = [check._describe_failure(f) for f in prover.check_failures(cs, [(GATE, 1, 0, 3), (LOOKUP, 0, 2 << 16 | 1, 7),
                                                                             (SHUFFLE, 0, 0, 2), (COPY, 0, 0, 5)])]
     assert text == ["gate 1 'rot' polynomial 0 is not satisfied at row 3",
                     "lookup 0 'in t' (input set 2, input 1): row 7 is not in the table",

@@ -200,19 +200,19 @@ def test_rational_refuses_bad_shapes_and_rows_without_a_device():
 
 
 def test_a_rational_without_a_device_is_an_error():
-    from halo2_gpu_specific_amd import prover
+    from halo2_gpu_specific_amd import witness
     from assigned_cases import is_zero_circuit, is_zero_witness
 
     cs = is_zero_circuit()
     w = is_zero_witness(6, 1, blinding=cs.blinding_factors())
     with pytest.raises(ValueError, match="resolved on a device"):
-        prover._witness_sets(cs, w["n"], w["dense"], (), False, None)
+        witness._witness_sets(cs, w["n"], w["dense"], (), False, None)
 
 
 def test_witness_without_a_rational_goes_through_untouched():
     """the caller's arrays themselves come back, unwritten, and nothing asks the device for anything (the one handed in here
     has no attribute to touch)"""
-    from halo2_gpu_specific_amd import prover
+    from halo2_gpu_specific_amd import witness
     from assigned_cases import is_zero_circuit, is_zero_witness
 
     cs = is_zero_circuit()
@@ -220,10 +220,10 @@ def test_witness_without_a_rational_goes_through_untouched():
     adv = w["resolved"] + []
     before = [a.copy() for a in adv]
     for kw in ({}, {"device": object()}, {"device": object(), "strict_rationals": True}):
-        sets, inst = prover._witness_sets(cs, w["n"], adv, (), False, None, **kw)
+        sets, inst = witness._witness_sets(cs, w["n"], adv, (), False, None, **kw)
         assert len(sets) == 1 and inst == [[]]
         assert all(a is b for a, b in zip(sets[0], adv))
-    two, _ = prover._witness_sets(cs, w["n"], [adv, adv], [(), ()], False, None, device=object())
+    two, _ = witness._witness_sets(cs, w["n"], [adv, adv], [(), ()], False, None, device=object())
     assert all(a is b for s in two for a, b in zip(s, adv))
     assert all(np.array_equal(a, b) for a, b in zip(adv, before))
 

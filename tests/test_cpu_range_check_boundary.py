@@ -131,23 +131,23 @@ def test_device_completion_without_a_device_is_an_error_not_a_fallback():
 def test_host_path_is_untouched_without_a_device():
     """host columns of canonical integers keep the host path and its in-place semantics (a guard against a regression: this
     holds before the device path exists too, so it is no evidence of it)"""
-    from halo2_gpu_specific_amd import circuits, prover
+    from halo2_gpu_specific_amd import circuits, prover, witness
 
     cs = circuits.range_check(0, 61, 4)
     adv, _, _ = circuits.range_check_synthesize(8, vmax=61, count=100)
     n = 1 << 8
     want = [a.copy() for a in adv]
     prover.complete_range_check_witness(cs, n, want)
-    sets, _ = prover._witness_sets(cs, n, adv, (), False, None)
+    sets, _ = witness._witness_sets(cs, n, adv, (), False, None)
     assert sets[0][0] is adv[0] and all(np.array_equal(a, b) for a, b in zip(adv, want))
     with pytest.raises(ValueError, match="needs canonical advice columns"):
-        prover._witness_sets(cs, n, adv, (), True, None)          # no device given: nothing to complete Montgomery columns on
+        witness._witness_sets(cs, n, adv, (), True, None)          # no device given: nothing to complete Montgomery columns on
 
 
 def test_opt_in_leaves_a_wide_range_of_host_columns_to_the_host():
     """a range of 2^24 values or more is past the device's cap: under `range_checks_on_device` host columns are completed by
     the host path, on copies (the device handed in here has no attribute to touch)"""
-    from halo2_gpu_specific_amd import circuits, prover
+    from halo2_gpu_specific_amd import circuits, prover, witness
 
     import types
 
@@ -159,6 +159,6 @@ def test_opt_in_leaves_a_wide_range_of_host_columns_to_the_host():
     before = [a.copy() for a in adv]
     want = [a.copy() for a in adv]
     prover.complete_range_check_witness(cs, n, want)
-    sets, _ = prover._witness_sets(cs, n, adv, (), False, None, device=object(), range_checks_on_device=True)
+    sets, _ = witness._witness_sets(cs, n, adv, (), False, None, device=object(), range_checks_on_device=True)
     assert all(np.array_equal(a, b) for a, b in zip(adv, before)), "the caller's columns were written"
     assert all(np.array_equal(a, b) for a, b in zip(sets[0], want))

@@ -659,11 +659,12 @@ def test_intt_out_of_place(oracle, k):
     """h2_intt_to: the values are left alone, the coefficients land in another vector -- the same coefficients h2_intt leaves in place"""
     import halo2_gpu_specific_amd as h2
     from halo2_gpu_specific_amd import prover
+    from halo2_gpu_specific_amd.domain import _fr
 
     L = h2.lib()
     n = 1 << k
     dom = prover.Domain(k, 3)
-    wi, dv = prover._fr(dom.omega_inv), prover._fr(dom.ifft_divisor)
+    wi, dv = _fr(dom.omega_inv), _fr(dom.ifft_divisor)
     a = oracle.random_fr(9990 + k, n)
     keep, out = a.copy(), np.empty((n, 4), dtype=np.uint64)
     assert L.h2_intt_to(_ptr(a), _ptr(out), wi, dv, k) == 0

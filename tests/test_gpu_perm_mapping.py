@@ -130,7 +130,7 @@ def key_facts(pk):
 
 @pytest.mark.parametrize("which", ["mini-plonk", "lookup-shuffle"])
 def test_keygen_through_the_device_equals_keygen_through_the_host_function(device, params, which, monkeypatch):
-    from halo2_gpu_specific_amd import prover
+    from halo2_gpu_specific_amd import keygen, prover
     from halo2_gpu_specific_amd.rng import ProverRng
 
     cs, adv, fixed, copies, inst = circuit(which)
@@ -140,7 +140,7 @@ def test_keygen_through_the_device_equals_keygen_through_the_host_function(devic
     hpk = prover.keygen(device, params, cs, fixed, None, mapping=host_mapping)
     # the default route neither calls the host function nor can import scipy
     with monkeypatch.context() as m:
-        m.setattr(prover, "permutation_mapping", lambda *a: pytest.fail("keygen called the host function"))
+        m.setattr(keygen, "permutation_mapping", lambda *a: pytest.fail("keygen called the host function"))
         for name in [name for name in sys.modules if name == "scipy" or name.startswith("scipy.")]:
             m.setitem(sys.modules, name, None)
         m.setitem(sys.modules, "scipy", None)
@@ -164,13 +164,13 @@ _HOST_ROUTE = r"""
 import json, sys
 sys.path.insert(0, %r)
 sys.path.insert(0, %r)
-from halo2_gpu_specific_amd import prover
+from halo2_gpu_specific_amd import keygen, prover
 from test_gpu_perm_mapping import K, S_TRAPDOOR, circuit, key_facts
-calls, host = [], prover.permutation_mapping
+calls, host = [], keygen.permutation_mapping
 def counted(*a):
     calls.append(1)
     return host(*a)
-prover.permutation_mapping = counted
+keygen.permutation_mapping = counted       # the name keygen.keygen reads: its own module's, not prover's re-export
 D = prover.Device()
 cs, adv, fixed, copies, inst = circuit("mini-plonk")
 pk = prover.keygen(D, prover.Params.unsafe_setup(D, K, S_TRAPDOOR), cs, fixed, copies)

@@ -259,7 +259,7 @@ def test_status_records_name_the_pair_and_the_first_offending_row(device):
 def test_wide_range_cap(device):
     """vmax - vmin = 2^24 is past the counting sort's cap: the documented status from the C entry, a ValueError for resident
     columns; host columns keep the host path (which sorts)"""
-    from halo2_gpu_specific_amd import prover
+    from halo2_gpu_specific_amd import prover, witness
 
     k = 8
     n = 1 << k
@@ -270,7 +270,7 @@ def test_wide_range_cap(device):
     with pytest.raises(ValueError, match="2\\^24"):
         prover.complete_range_check_witness_device(device, cs, n, adv)
     assert np.array_equal(device.download(adv[0]), origin)
-    host = prover._witness_sets(cs, n, [origin.copy(), np.zeros((n, 4), np.uint64)], (), False, None, device=device)[0][0]
+    host = witness._witness_sets(cs, n, [origin.copy(), np.zeros((n, 4), np.uint64)], (), False, None, device=device)[0][0]
     assert isinstance(host[1], np.ndarray) and np.array_equal(host[1][:n - 6, 0], np.sort(host[0][:n - 6, 0]))
 
 

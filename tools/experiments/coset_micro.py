@@ -11,7 +11,8 @@ import torch  # noqa: E402
 
 from halo2_gpu_specific_amd import prover  # noqa: E402
 from halo2_gpu_specific_amd._lib import check  # noqa: E402
-from halo2_gpu_specific_amd.prover import _fr, R_MOD  # noqa: E402
+from halo2_gpu_specific_amd.domain import _fr  # noqa: E402
+from halo2_gpu_specific_amd.transcript import R_MOD  # noqa: E402
 
 k = int(sys.argv[1]) if len(sys.argv) > 1 else 22
 deg = int(sys.argv[2]) if len(sys.argv) > 2 else 3

@@ -10,7 +10,8 @@ import torch  # noqa: E402
 
 from halo2_gpu_specific_amd import lib  # noqa: E402
 from halo2_gpu_specific_amd._lib import check  # noqa: E402
-from halo2_gpu_specific_amd.prover import _fr, R_MOD  # noqa: E402
+from halo2_gpu_specific_amd.domain import _fr  # noqa: E402
+from halo2_gpu_specific_amd.transcript import R_MOD  # noqa: E402
 
 ROOT = 0x03DDB9F5166D18B798865EA93DD31F743215CF6DD39329C8D34F1ED960C37C9C
 L = lib()

@@ -16,12 +16,13 @@ import torch  # noqa: E402
 
 import halo2_gpu_specific_amd as h2  # noqa: E402
 from halo2_gpu_specific_amd import prover  # noqa: E402
+from halo2_gpu_specific_amd.domain import _fr  # noqa: E402
 
 L = h2.lib()
 k = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 n = 1 << k
 dom = prover.Domain(k, 5)
-wi, dv = prover._fr(dom.omega_inv), prover._fr(dom.ifft_divisor)
+wi, dv = _fr(dom.omega_inv), _fr(dom.ifft_divisor)
 rng = np.random.default_rng(1)
 src = rng.integers(0, 2**61, size=(n, 4), dtype=np.uint64)
 

@@ -91,7 +91,8 @@ def count_products(k, twiddles):
 
 def device_twiddles(D, k):
     """w^-e canonical, e < 2^(k-1), as (n/2, 4) u64 (w = the domain's omega)"""
-    from halo2_gpu_specific_amd.prover import _fr, check
+    from halo2_gpu_specific_amd._lib import check
+    from halo2_gpu_specific_amd.domain import _fr
 
     half = 1 << (k - 1)
     w_inv = pow(pow(ROOT_OF_UNITY, 1 << (28 - k), R_MOD), -1, R_MOD)

@@ -22,6 +22,7 @@ import prover_fuzz  # noqa: E402
 import test_evalh_host_exec as hx  # noqa: E402
 from h2util import Oracle, fr_mont  # noqa: E402
 from halo2_gpu_specific_amd import circuits, evaluation as ev, prover  # noqa: E402
+from halo2_gpu_specific_amd.keygen import _ANY  # noqa: E402
 
 ROOT_OF_UNITY = evalh_cases.ROOT
 
@@ -48,7 +49,7 @@ def circuit_case(cs, k, oracle, seed):
         calculations=graph.calculations, value_parts=value_parts, lookups=lookup_calcs, shuffles=shuffle_calcs,
         fixed=[rnd() for _ in range(cs.num_fixed)], advice=[rnd() for _ in range(cs.num_advice)],
         instance=[rnd() for _ in range(cs.num_instance)], l0=rnd(), l_last=rnd(), l_active_row=rnd(),
-        perm_z=[rnd() for _ in range(nsets)], perm_columns=[(prover._ANY[kd], i) for kd, i in cs.perm_columns],
+        perm_z=[rnd() for _ in range(nsets)], perm_columns=[(_ANY[kd], i) for kd, i in cs.perm_columns],
         perm_sigma=[rnd() for _ in range(ncols)], lookup_z=[rnd() for _ in range(sum(nz))], lookup_m=[rnd() for _ in range(len(nz))],
         shuffle_z=[rnd() for _ in range(len(shuffle_calcs))],
         y=fr_mont(ch.randrange(evalh_cases.R_MOD)), beta=fr_mont(ch.randrange(evalh_cases.R_MOD)),

@@ -105,7 +105,8 @@ def count_products(scalars):
 
 def device_powers(D, tau, n):
     """tau^i canonical, i < n, as (n, 4) u64"""
-    from halo2_gpu_specific_amd.prover import OP_CONSTANT, _fr, check
+    from halo2_gpu_specific_amd.domain import _fr
+    from halo2_gpu_specific_amd.prover import OP_CONSTANT, check
 
     f = D.eval_op(OP_CONSTANT, D.empty(n), c=tau)
     out = D.empty(n)
