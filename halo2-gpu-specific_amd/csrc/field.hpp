@@ -42,6 +42,15 @@ struct FrParams {
                                         0x7879462eu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u};  // R mod r
     static constexpr uint32_t RR[8] = {0xae216da7u, 0x1bb8e645u, 0xe35c59e3u, 0x53fe3ab1u,
                                        0x53bb8085u, 0x8c49833du, 0x7f4e44a5u, 0x0216d0b1u};  // R^2 mod r
+    static constexpr uint32_t CHUNK_POW[8][8] = {  // 2^(64 + 32 i) R mod p, i = 0..7 (fp_chunk_table)
+        {0x7c5fb586u, 0xb4c6edf9u, 0xbfeb93beu, 0x708c8d50u, 0x04f7e0efu, 0x9ffd1de4u, 0x9a392866u, 0x215b02acu},
+        {0xaf8b5a7au, 0x54c81065u, 0x97aa45f6u, 0x2b82a1efu, 0x330a5a6du, 0xbe492693u, 0x8229aff4u, 0x1847e486u},
+        {0xef8cfeb9u, 0xb075da81u, 0xa5b6cd8cu, 0xa7f12accu, 0x7957bf7bu, 0x32c47504u, 0x48ffa25eu, 0x03d581d7u},
+        {0xebb7ae00u, 0xee881bd8u, 0x483e9406u, 0x076add9cu, 0x184bf72du, 0xe590c2b8u, 0xff54fbf4u, 0x1df79fc3u},
+        {0xc177f51au, 0x5665c3b5u, 0xde75c713u, 0x00e7f02au, 0x2f747168u, 0xb09192e5u, 0xcccdc65du, 0x0621c0bbu},
+        {0x8f8fc595u, 0x41a9cbe4u, 0x0a58dc0fu, 0x9f36d601u, 0x440ad260u, 0xa6132126u, 0x093f81ddu, 0x2ab23b99u},
+        {0xae216da7u, 0x1bb8e645u, 0xe35c59e3u, 0x53fe3ab1u, 0x53bb8085u, 0x8c49833du, 0x7f4e44a5u, 0x0216d0b1u},
+        {0x04f2bf4fu, 0x6dae765eu, 0xa11298d6u, 0x347d7b17u, 0xf603929eu, 0x70f88a97u, 0x83e5893eu, 0x0ad4bd84u}};
 };
 
 struct FqParams {
@@ -58,6 +67,15 @@ struct FqParams {
                                         0x7879462cu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u};  // R mod q
     static constexpr uint32_t RR[8] = {0x538afa89u, 0xf32cfc5bu, 0xd44501fbu, 0xb5e71911u,
                                        0x0a417ff6u, 0x47ab1effu, 0xcab8351fu, 0x06d89f71u};  // R^2 mod q
+    static constexpr uint32_t CHUNK_POW[8][8] = {  // 2^(64 + 32 i) R mod p, i = 0..7 (fp_chunk_table)
+        {0xb1d8c62au, 0x2d9e3b3fu, 0xeb3c74f7u, 0x1be5d753u, 0x5d840e23u, 0x532e2dcfu, 0x9a392864u, 0x215b02acu},
+        {0x8b28a9d6u, 0x0f54b1e8u, 0x492b8e82u, 0xf21d65b8u, 0x91aba3c7u, 0x16d553c6u, 0x355abfe0u, 0x1847e484u},
+        {0x2fcc56eau, 0x70bb1707u, 0x583ff802u, 0xe0e407c3u, 0x9bab3e80u, 0xed7948a3u, 0x1110f1afu, 0x2c1e8d98u},
+        {0xcfc4da46u, 0xcd9e8446u, 0xd3cf3fbcu, 0x608145f0u, 0x74c97a69u, 0x7c85e319u, 0x599e034bu, 0x1798cd75u},
+        {0xcdd22cd6u, 0xd9e291c2u, 0xa40f0271u, 0xc722ccf2u, 0x11a2ac87u, 0xa49e35d6u, 0x8c993ec8u, 0x2e104397u},
+        {0xd86ece59u, 0xa021026fu, 0x6b59411bu, 0xb4c74c43u, 0x4bce7022u, 0xcd5b0ab0u, 0xaef5cf59u, 0x1d7bcfc4u},
+        {0x538afa89u, 0xf32cfc5bu, 0xd44501fbu, 0xb5e71911u, 0x0a417ff6u, 0x47ab1effu, 0xcab8351fu, 0x06d89f71u},
+        {0x83478424u, 0x52592227u, 0x602ec2ddu, 0xd71cacedu, 0xcede48f3u, 0x541fc3cfu, 0x96a02082u, 0x0fc6dd09u}};
 };
 
 template <class P>
@@ -393,6 +411,13 @@ H2_DEV Fp<P> fp_lazy_canon(const Fp<P>& a) {
     return fp_reduce_once(fp_lazy_red2p(a));
 }
 
+// A constant tabulated for fp_mul_chunk: the 8 / CL residues T_k = w 2^(32 CL k) 2^(32 (CL + 1)) mod p, limb-major --
+// w[l * (8 / CL) + k] = limb l of T_k -- so that a column of the product's sweep reads consecutive words.
+template <int CL>
+struct alignas(16) FpChunk {
+    uint32_t w[64 / CL];
+};
+
 // acc(96 bit = lo64 : hi32) += a * b.
 // v_mad_u64_u32 D, carry(SGPR pair), a, b, D ; v_addc_co_u32 hi, carry, hi, 0, carry
 H2_DEV void mad_acc(uint64_t& lo, uint32_t& hi, uint32_t a, uint32_t b) {
@@ -420,6 +445,8 @@ template <class P>
 __device__ __forceinline__ Fp<P> fp_mul_wide_dev(const Fp<P>& a, const Fp<P>& b);  // a < 2^256, b canonical -> < 2p, unreduced
 template <class P>
 __device__ __forceinline__ Fp<P> fp_mul_const_dev(const Fp<P>& a, const Fp<P>& w, const Fp<P>& wq);  // a < 2^256; see fp_mul_const
+template <class P, int CL>
+__device__ __forceinline__ Fp<P> fp_mul_chunk_dev(const Fp<P>& a, const FpChunk<CL>& t);  // a < 2^256; see fp_mul_chunk
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(H2_PORTABLE_MUL)
 #include "fp_mul_gen.hpp"
 #endif
@@ -609,6 +636,57 @@ H2_DEV void fp_const_pair(const Fp<P>& w_mont, Fp<P>& w_plain, Fp<P>& wq) {
         wq.l[i] = (uint32_t)lo;
         lo = (lo >> 32) | ((uint64_t)hi << 32);
         hi = 0;
+    }
+}
+
+// x * w for a CONSTANT w tabulated in chunks (the butterfly twiddles of the fixed NTT pass): the table does part of the
+// reduction.  With x = sum X_k 2^(32 CL k) (8 / CL chunks of CL limbs) and T_k = w 2^(32 CL k) 2^(32 nm) mod p (nm = CL + 1):
+// S = sum X_k T_k in one product-scanning sweep (64 multiply-adds, S < (8 / CL) 2^(32 CL) p), nm word-serial Montgomery
+// steps (m_i = lo * INV and m_i p: 8 multiply-adds each), r = (S + m p) / 2^(32 nm).  r = S 2^(-32 nm) = x w (mod p) -- for
+// Montgomery data x = X R that is (X w) R, fp_mul_const's contract -- and r < ((8 / CL) 2^(32 CL) p + 2^(32 nm) p) / 2^(32 nm)
+// = p (1 + 2^-29): below 2p with no fix-up.  88 (CL = 2) or 80 (CL = 1) multiply-adds and nm low products against 115
+// (tools/gen_fp_mul.py schedule_chunk has the column bounds).
+template <int CL, class P>
+H2_DEV Fp<P> fp_mul_chunk(const Fp<P>& x, const FpChunk<CL>& t) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(H2_PORTABLE_MUL)
+    return fp_mul_chunk_dev<P, CL>(x, t);
+#else
+    constexpr int NC = 8 / CL, NM = CL + 1;
+    Fp<P> r;
+    uint64_t lo = 0;
+    uint32_t hi = 0;
+    uint32_t m[NM];
+    for (int i = 0; i < NM + 7; i++) {
+        for (int j = 0; j < 8; j++) {
+            const int l = i - j % CL;
+            if (l >= 0 && l <= 7) mad_acc(lo, hi, x.l[j], t.w[l * NC + j / CL]);
+        }
+        for (int j = 0; j < NM && j < i; j++)
+            if (i - j <= 7) mad_acc(lo, hi, m[j], P::MOD[i - j]);
+        if (i < NM) {
+            m[i] = (uint32_t)lo * P::INV;
+            mad_acc(lo, hi, m[i], P::MOD[0]);
+        } else {
+            r.l[i - NM] = (uint32_t)lo;
+        }
+        lo = (lo >> 32) | ((uint64_t)hi << 32);
+        hi = 0;
+    }
+    r.l[7] = (uint32_t)lo;
+    return r;
+#endif
+}
+// w (Montgomery form) -> the table entry fp_mul_chunk reads: T_k = w_plain 2^(32 CL k + 32 (CL + 1)) mod p, one Montgomery
+// product of the plain value by the constant 2^e R mod p each (CHUNK_POW holds e = 64, 96 .. 288).
+template <int CL, class P>
+H2_DEV void fp_chunk_table(const Fp<P>& w_mont, FpChunk<CL>& out) {
+    constexpr int NC = 8 / CL;
+    const Fp<P> w_plain = fp_from_mont(w_mont);
+    for (int k = 0; k < NC; k++) {
+        Fp<P> c;
+        for (int l = 0; l < 8; l++) c.l[l] = P::CHUNK_POW[CL * k + CL - 1][l];
+        const Fp<P> t = fp_mul(w_plain, c);
+        for (int l = 0; l < 8; l++) out.w[l * NC + k] = t.l[l];
     }
 }
 

@@ -33,12 +33,25 @@ static constexpr int NTT_BATCH_MAX = 16;  // vectors per launch of a batched tra
 static constexpr int LO_BITS = 12;  // two-level twiddle tables: w^e = lo[e & 4095] * hi[e >> 12]
 
 // ---------------------------------------------------------------- table generation
-// A twiddle table in one of two forms.  pair = 0: out[i] = w, Montgomery form (the operand of fp_mul / fp_mul_wide).
+// A twiddle table in one of three forms.  pair = 0: out[i] = w, Montgomery form (the operand of fp_mul / fp_mul_wide).
 // pair = 1: out[2 i] = w as a PLAIN residue, out[2 i + 1] = floor(w 2^256 / r) -- the operands of fp_mul_const (field.hpp), the
 // constant-operand product the passes with CW use for every twiddle they read from a table.
+// pair = 2: entry i (sizeof(TwChunk) bytes) = w's chunk residues, limb-major -- the operand of fp_mul_chunk, which the fixed
+// pass (k_ntt_pass8) uses for its butterfly twiddles.
+using TwChunk = FpChunk<2>;   // four chunks of 64 bits (eight of 32 bits measured slower: DESIGN.md)
+static constexpr uint32_t TW_CHUNK_FR = sizeof(TwChunk) / sizeof(Fr);   // table elements per entry
+static constexpr uint32_t TW_CHUNK_Q = sizeof(TwChunk) / sizeof(uint4);  // 16-byte words per entry
 __device__ __forceinline__ void tw_store(Fr* out, uint32_t i, const Fr& w_mont, uint32_t pair) {
     if (!pair) {
         fp_store(out + i, w_mont);
+        return;
+    }
+    if (pair == 2) {
+        TwChunk t;
+        fp_chunk_table(w_mont, t);
+        uint4* const q = reinterpret_cast<uint4*>(out) + (size_t)i * TW_CHUNK_Q;
+#pragma unroll
+        for (uint32_t k = 0; k < TW_CHUNK_Q; k++) q[k] = make_uint4(t.w[4 * k], t.w[4 * k + 1], t.w[4 * k + 2], t.w[4 * k + 3]);
         return;
     }
     Fr w, q;
@@ -87,6 +100,7 @@ struct PassArgs {
     const Fr* in;
     Fr* out;
     const Fr* tw_bfly;  // R/2 entries: (w^(n/R))^e   (CW kernels: R/2 PAIRS -- plain value, quotient -- like tw_direct; see tw_store)
+    const Fr* tw_chunk;  // k_ntt_pass8: the same R/2 values as chunk tables (tw_store's third form)
     const Fr* tw_lo;    // min(n, 4096) entries: w^i
     const Fr* tw_hi;    // n >> 12 entries: w^(i << 12)   (unused when n <= 4096)
     const Fr* tw_direct;  // non-null: inter-pass twiddle = tw_direct[(rho << consumed) | K] (no generation multiply)
@@ -466,7 +480,8 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
 
 // ---------------------------------------------------------------- the common pass, tile ends fused
 // The radix-4 pass at one fixed geometry (8 bits, 4 columns, 256 lanes, four elements per lane, nothing skipped; one tile
-// per workgroup, blockIdx.y the vector; twiddle tables as pairs, k_ntt_pass's CW) with the two ends of a tile taken out of LDS.
+// per workgroup, blockIdx.y the vector; the tabulated inter-pass twiddles as pairs, k_ntt_pass's CW, the butterfly twiddles as
+// chunk tables, see below) with the two ends of a tile taken out of LDS.
 // The four rows a lane loads are the inputs of ONE unit of the first stage pair, and the four rows a unit of the last stage
 // pair produces are the four a lane stores.  So the first pair runs on the loaded registers (after pre3, the coset pre-scale
 // and the inter-pass twiddle, as before) and writes its outputs to LDS, and the last pair's outputs go through the
@@ -480,34 +495,46 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
 //     writes of the unfused load phase were).
 // The first pair needs ONE butterfly twiddle (index 1 of stage 1, entry 64 of the table) before the tile's first barrier, i.e.
 // before the LDS copy of the table is ordered against its readers: every lane reads that one from the table in memory.
+// The butterfly twiddles are chunk tables (fp_mul_chunk: 88 multiply-adds per product instead of fp_mul_const's 115).  The
+// stage pairs before the last one read only the entries whose index is a multiple of 4: those 32 are in LDS, as TW_CHUNK_Q
+// planes of 16-byte words -- plane l holds limb l of the four residues of every twiddle, what one column of the product's
+// sweep reads (lanes with different twiddles: 16-byte stride, conflict-free; the same twiddle: a broadcast).  The last stage
+// pair reads all R/2 entries, every lane its own three and once per tile: those come from the table in memory (16 KiB, cache
+// resident; 384 bytes per lane next to the 256 bytes of its elements).  Tile planes 32 KiB + 4 KiB: four workgroups per CU
+// as with the pair tables -- the whole table in LDS (48 KiB) leaves three, which costs more than the shorter product gains.
+static constexpr uint32_t PASS8_TW_LDS = 32;   // entries in LDS: indices 0, 4, 8 ..
+static constexpr uint32_t PASS8_LDS = ((256u << 2) * 2 + PASS8_TW_LDS * TW_CHUNK_Q) * sizeof(uint4);
+static_assert(4 * PASS8_LDS <= 160u * 1024, "four workgroups of k_ntt_pass8 per CU");
 template <bool DP>
 __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     constexpr uint32_t B = 8, R = 1u << B, log_c = 2, C = 1u << log_c;
     auto tmul = [](const Fr& x, const Fr& w) -> Fr { return fp_mul_wide(x, w); };
     uint4* t_lo = h2_smem;                  // the planes of k_ntt_pass, at the same offsets
     uint4* t_hi = t_lo + (R << log_c);
-    uint4* w_lo = t_hi + (R << log_c);
-    uint4* w_hi = w_lo + (R >> 1);
-    uint4* q_lo = w_hi + (R >> 1);
-    uint4* q_hi = q_lo + (R >> 1);
-    struct Tw {
-        Fr w, q;
+    uint4* w_pl = t_hi + (R << log_c);      // the chunk table's entries 0, 4, 8 ..: TW_CHUNK_Q planes of PASS8_TW_LDS words
+    const uint4* const tw_tab = reinterpret_cast<const uint4*>(a.tw_chunk);   // the whole table, entry-major
+    using Tw = TwChunk;
+    auto tw_unpack = [](Tw& t, const uint32_t k, const uint4 v) __attribute__((always_inline)) {
+        t.w[4 * k] = v.x; t.w[4 * k + 1] = v.y; t.w[4 * k + 2] = v.z; t.w[4 * k + 3] = v.w;
     };
-    auto tw_get = [&](uint32_t i) __attribute__((always_inline)) -> Tw {
+    static_assert((R >> 1) / PASS8_TW_LDS == 4, "the stage pairs before the last read the indices that are multiples of 4");
+    auto tw_get = [&](const uint32_t i, const bool mem) __attribute__((always_inline)) -> Tw {
         Tw t;
-        t.w = lds_get(w_lo, w_hi, i);
-        t.q = lds_get(q_lo, q_hi, i);
+#pragma unroll
+        for (uint32_t k = 0; k < TW_CHUNK_Q; k++)
+            tw_unpack(t, k, mem ? tw_tab[(size_t)i * TW_CHUNK_Q + k] : w_pl[k * PASS8_TW_LDS + (i >> 2)]);
         return t;
     };
-    auto bmul = [](const Fr& x, const Tw& t) __attribute__((always_inline)) -> Fr { return fp_mul_const(x, t.w, t.q); };
+    auto bmul = [](const Fr& x, const Tw& t) __attribute__((always_inline)) -> Fr { return fp_mul_chunk(x, t); };
     // stages s and s + 1 on the rows p, p + h, p + 2h, p + 3h (h = 2^s) of one column, in registers, twiddle index r = p mod h:
     // the arithmetic of k_ntt_pass's round4, operation for operation; x0 .. x3 come back in row order
     auto unit4 = [&](Fr& x0, Fr& x1, Fr& x2, Fr& x3, const uint32_t s, const uint32_t r, const bool unit, const Tw* w3 = nullptr) __attribute__((always_inline)) {
         const uint32_t h = 1u << s;
+        const bool mem = s == B - 2;   // the last stage pair: twiddles of every index
         x0 = fp_lazy_red2p(x0);
         x2 = fp_lazy_red2p(x2);
         if (!unit) {
-            const Tw wa = tw_get(r << (B - 1 - s));
+            const Tw wa = tw_get(r << (B - 1 - s), mem);
             x1 = bmul(x1, wa);
             x3 = bmul(x3, wa);
         } else {
@@ -516,8 +543,8 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
         }
         const Fr y0 = fp_lazy_add_red(x0, x1), y1 = fp_lazy_sub_red(x0, x1);
         Fr y2 = fp_lazy_add(x2, x3), y3 = fp_lazy_sub(x2, x3);
-        y2 = unit ? fp_lazy_red2p(y2) : bmul(y2, tw_get(r << (B - 2 - s)));
-        y3 = bmul(y3, w3 ? *w3 : tw_get((r + h) << (B - 2 - s)));   // (w3: that twiddle, already in registers)
+        y2 = unit ? fp_lazy_red2p(y2) : bmul(y2, tw_get(r << (B - 2 - s), mem));
+        y3 = bmul(y3, w3 ? *w3 : tw_get((r + h) << (B - 2 - s), mem));   // (w3: that twiddle, already in registers)
         x0 = fp_lazy_add(y0, y2);
         x1 = fp_lazy_add(y1, y3);
         x2 = fp_lazy_sub(y0, y2);
@@ -560,15 +587,14 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     const bool is_last = DP ? false : a.is_last != 0;   // (pairs in tw_direct: never the last pass)
     const uint32_t n_mask = (a.log_n >= 32) ? 0xffffffffu : ((1u << a.log_n) - 1);
 
-    if (tid < (R >> 1)) {
-        lds_put(w_lo, w_hi, tid, fp_load(a.tw_bfly + 2 * tid));
-        lds_put(q_lo, q_hi, tid, fp_load(a.tw_bfly + 2 * tid + 1));
-    }
+#pragma unroll
+    for (uint32_t g = tid; g < PASS8_TW_LDS * TW_CHUNK_Q; g += 256)
+        w_pl[(g % TW_CHUNK_Q) * PASS8_TW_LDS + g / TW_CHUNK_Q] = tw_tab[(size_t)(g / TW_CHUNK_Q) * 4 * TW_CHUNK_Q + g % TW_CHUNK_Q];
 
     // stage 1's twiddle of index 1 for the first stage pair, straight from the table (wave-uniform address)
     Tw tw64;
-    tw64.w = fp_load(a.tw_bfly + 2 * (R >> 2));
-    tw64.q = fp_load(a.tw_bfly + 2 * (R >> 2) + 1);
+#pragma unroll
+    for (uint32_t k = 0; k < TW_CHUNK_Q; k++) tw_unpack(tw64, k, tw_tab[(R >> 2) * TW_CHUNK_Q + k]);
 
     constexpr uint32_t NE = 4;
     {
@@ -1049,20 +1075,26 @@ PlanRef ntt_get_plan(DeviceCtx* ctx, uint32_t log_n, const uint64_t omega[4], hi
     uint32_t hi_count = log_n > LO_BITS ? (n >> LO_BITS) : 0;
     size_t total = lo_count + hi_count;
     std::vector<uint32_t> bf_off;
+    std::vector<uint8_t> fixed_geom;
     {
         // which passes read their tabulated twiddles as (plain, quotient) pairs: a property of the pass's geometry, fixed here
         uint32_t consumed = 0;
         for (size_t p = 0; p < pl->bits.size(); p++) {
             const uint32_t B = pl->bits[p];
             const bool last = p + 1 == pl->bits.size();
-            pl->cw.push_back(pass_shape(log_n, B, last ? consumed : log_n - consumed - B).radix4 ? 1 : 0);
+            const PassShape sh = pass_shape(log_n, B, last ? consumed : log_n - consumed - B);
+            pl->cw.push_back(sh.radix4 ? 1 : 0);
+            fixed_geom.push_back(sh.fixed ? 1 : 0);
             consumed += B;
         }
     }
+    std::vector<uint32_t> ch_off;  // the chunk tables of the passes of the fixed geometry (0: none)
     for (size_t p = 0; p < pl->bits.size(); p++) {
         const uint32_t b = pl->bits[p];
         bf_off.push_back((uint32_t)total);
         total += ((1u << b) >> 1 ? (1u << b) >> 1 : 1) * (pl->cw[p] ? 2u : 1u);
+        ch_off.push_back(fixed_geom[p] ? (uint32_t)total : 0u);
+        if (fixed_geom[p]) total += ((1u << b) >> 1) * TW_CHUNK_FR;
     }
     H2_HIP(hipMalloc(&pl->tables, total * sizeof(Fr)));
     pl->table_bytes = total * sizeof(Fr);
@@ -1078,6 +1110,12 @@ PlanRef ntt_get_plan(DeviceCtx* ctx, uint32_t log_n, const uint64_t omega[4], hi
         if (half)
             hipLaunchKernelGGL(k_pow_table, dim3((half + 255) / 256), dim3(256), 0, stream, pl->tables + bf_off[p], w,
                                n >> pl->bits[p], half, (uint32_t)pl->cw[p]);
+        // the fixed geometry reads the same values as chunk tables; the pair table stays for the general kernel (zero padding
+        // is a property of the call)
+        pl->tw_chunk.push_back(ch_off[p] ? pl->tables + ch_off[p] : nullptr);
+        if (ch_off[p])
+            hipLaunchKernelGGL(k_pow_table, dim3((half + 255) / 256), dim3(256), 0, stream, pl->tables + ch_off[p], w,
+                               n >> pl->bits[p], half, 2u);
     }
     // passes whose whole inter-pass twiddle set has <= 2^16 entries get it tabulated (2 MiB, L2-resident):
     // the pass then spends one multiplication per element on twiddles instead of two
@@ -1264,6 +1302,7 @@ static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr
             }
         }
         a.tw_bfly = pl->tw_bfly[p];
+        a.tw_chunk = pl->tw_chunk[p];
         a.tw_lo = pl->tw_lo;
         a.tw_hi = pl->tw_hi;
         a.tw_direct = pl->tw_direct[p];
@@ -1320,9 +1359,9 @@ static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr
             a.radix4 = sh.radix4 ? 1u : 0u;
             const uint32_t R = 1u << B, C = 1u << sh.log_c, threads = sh.threads;
             const uint32_t ntiles = (1u << L) / (R * C);
-            // tile planes + butterfly twiddles: R/2 values and a pad, or (CW) R/2 pairs exactly -- 40 KiB for the common pass
+            // tile planes + butterfly twiddles: R/2 values and a pad, or (CW) R/2 pairs exactly; k_ntt_pass8 has its own (36 KiB)
             const size_t lds = cw ? ((size_t)R * C + R) * sizeof(Fr) : ((size_t)R * C + (R >> 1) + 2) * sizeof(Fr);
-            if (lds > 64 * 1024) {  // beyond the default dynamic LDS limit: raise it once (k_ntt_pass8's tile is 40 KiB)
+            if (lds > 64 * 1024) {  // beyond the default dynamic LDS limit: raise it once (never the 8-bit passes)
                 static bool raised[64] = {};  // per device
                 const int dev = ctx->device;
                 if (dev < 0 || dev >= 64 || !raised[dev]) {
@@ -1331,7 +1370,9 @@ static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr
                     if (dev >= 0 && dev < 64) raised[dev] = true;
                 }
             }
-            hipLaunchKernelGGL(pass_fn[pass_kernel(sh, a.zskip, last)], dim3(ntiles, cnt), dim3(threads), lds, stream, a);
+            const NttKernel kernel = pass_kernel(sh, a.zskip, last);
+            const bool pass8 = kernel == NK_PASS8_DP || kernel == NK_PASS8;
+            hipLaunchKernelGGL(pass_fn[kernel], dim3(ntiles, cnt), dim3(threads), pass8 ? (size_t)PASS8_LDS : lds, stream, a);
         }
         // (`last_tab` unpins here: launched -- an eviction from here on synchronises the device before it frees)
         consumed += B;

@@ -15,6 +15,7 @@ struct NttPlan {
     const Fr* tw_lo = nullptr;         // w^i,        i < min(n, 4096)
     const Fr* tw_hi = nullptr;         // w^(i<<12),  i < n >> 12
     std::vector<const Fr*> tw_bfly;    // per pass: (w^(n/R))^e, e < R/2
+    std::vector<const Fr*> tw_chunk;   // per pass of the fixed geometry: tw_bfly's values as chunk tables (fp_mul_chunk), else nullptr
     std::vector<const Fr*> tw_direct;  // per pass: full inter-pass twiddle table or nullptr
     // per pass: 1 = its tw_bfly / tw_direct / last-pass tables hold (plain value, floor(value 2^256 / r)) PAIRS, the operands of
     // the constant-operand product fp_mul_const (the radix-4 passes: transforms >= 2^18)

@@ -28,6 +28,7 @@ FIELDS = {
 }
 W = (1 << 32) - 1
 TOP = (1 << 30) - 1  # limb 7 of an input < 2^254
+CHUNK_LIMBS = (2,)  # the chunk widths of schedule_chunk the header holds, in 32-bit limbs (1: measured slower in the NTT)
 
 
 def schedule(p, square=False, dual=False, wide=False):
@@ -161,6 +162,77 @@ def schedule_const(p):
         lines.append("    r.l[%d] = (uint32_t)lo;" % i)
         if i < 7:
             lines.append("    H2_SHIFT%d();" % (1 if carried else 0))
+    return lines, stats
+
+
+def schedule_chunk(p, chunk_limbs):
+    """The product by a constant tabulated in CHUNKS (the butterfly twiddles of the fixed NTT pass): the table holds, for the
+    8 / chunk_limbs chunks X_k of 32 chunk_limbs bits of the variable operand, the residues
+
+        T_k = w 2^(32 chunk_limbs k) 2^(32 nm) mod p     (nm = chunk_limbs + 1, each T_k < p)
+
+    and for ANY 256-bit x = sum X_k 2^(32 chunk_limbs k) one product-scanning sweep computes
+
+        S = sum X_k T_k                         64 multiply-adds, S < 2^(32 chunk_limbs + 2) p (2^66 p / 2^35 p)
+        nm word-serial Montgomery steps         m_i = lo * INV, m_i p: nm * 8 multiply-adds
+        r = (S + m p) / 2^(32 nm)               = x w (mod p), r < p (1 + 2^-29): below 2p, no fix-up
+
+    64 + 8 nm multiply-adds (88 / 80) and nm low products (3 / 2) against 115 for schedule_const.  Operands: a = x, t = the
+    table entry limb-major, t.w[l * nchunks + k] = limb l of T_k (column c reads the words of limbs c - chunk_limbs + 1 .. c).
+    stats["column_max"][i]: the exact upper bound of column i's accumulator, carry-over included."""
+    cl = chunk_limbs
+    assert cl in (1, 2)
+    nchunks, nm = 8 // cl, cl + 1
+    mod = [(p >> (32 * i)) & W for i in range(8)]
+    tmax = [W] * 7 + [(p - 1) >> 224]
+    lines, stats = [], {"free": 0, "set": 0, "acc": 0, "column_max": []}
+    carry_in = 0
+    for i in range(nm + 7):
+        terms = []
+        for j in range(8):
+            k, e = divmod(j, cl)
+            if 0 <= i - e <= 7:
+                terms.append((W * tmax[i - e], "a.l[%d]" % j, "t.w[%d]" % ((i - e) * nchunks + k), "V"))
+        for j in range(nm):
+            if 1 <= i - j <= 7:
+                terms.append((W * mod[i - j], "m%d" % j, "P::MOD[%d]" % (i - j), "S"))
+        terms.sort(key=lambda t: t[0])
+        total, nfree = carry_in, 0
+        for t in terms:
+            if total + t[0] < (1 << 64):
+                total += t[0]
+                nfree += 1
+            else:
+                break
+        lines.append("    // column %d: %d terms, %d cannot carry" % (i, len(terms) + (1 if i < nm else 0), nfree))
+        column_max = carry_in + sum(t[0] for t in terms)
+        carried = False
+        for k, (_, x, y, cls) in enumerate(terms):
+            kind = "FREE" if k < nfree else ("ACC" if carried else "SET")
+            if kind == "SET":
+                carried = True
+            stats[kind.lower()] += 1
+            lines.append("    H2_MAD_%s_%s(%s, %s);" % (kind, cls, x, y))
+        if i < nm:
+            lines.append("    const uint32_t m%d = (uint32_t)lo * P::INV;" % i)
+            kind = "ACC" if carried else ("SET" if column_max + W * mod[0] >= (1 << 64) else "FREE")
+            carried = carried or kind == "SET"
+            stats[kind.lower()] += 1
+            lines.append("    H2_MAD_%s_S(m%d, P::MOD[0]);  // low word becomes 0" % (kind, i))
+            column_max += W * mod[0]
+        else:
+            lines.append("    r.l[%d] = (uint32_t)lo;" % (i - nm))
+        lines.append("    H2_SHIFT%d();" % (1 if carried else 0))
+        assert column_max < (1 << 96)
+        stats["column_max"].append(column_max)
+        carry_in = column_max >> 32
+    lines.append("    r.l[7] = (uint32_t)lo;")
+    assert carry_in < (1 << 32)
+    stats["column_max"].append(carry_in)
+    # the sums as integers: S below nchunks 2^(32 cl) p = 2^66 p / 2^35 p, r below 2p (in fact p (1 + 2^-29))
+    s_max = nchunks * ((1 << (32 * cl)) - 1) * (p - 1)
+    assert s_max < ((nchunks * p) << (32 * cl))
+    assert (s_max + ((1 << (32 * nm)) - 1) * p) >> (32 * nm) < p + (p >> 29) < 2 * p
     return lines, stats
 
 
@@ -390,6 +462,25 @@ def main():
         out.append("}")
         out.append("")
         print(name, "const", stats)
+        # (any 256-bit value) * (a constant tabulated in chunks) -> below p (1 + 2^-29): the fixed NTT pass's butterfly twiddles
+        for cl in CHUNK_LIMBS:
+            lines, stats = schedule_chunk(p, cl)
+            out.append("// %s by a constant tabulated in %d chunks of %d bits: a < 2^256, t.w[l * %d + k] = limb l of w 2^(%d k + %d) mod p; result"
+                       % (name, 8 // cl, 32 * cl, 8 // cl, 32 * cl, 32 * (cl + 1)))
+            out.append("// < p (1 + 2^-29), NOT reduced: %d bare multiply-adds, %d carry-setting, %d carry-accumulating, %d low products"
+                       % (stats["free"], stats["set"], stats["acc"], cl + 1))
+            out.append("template <>")
+            out.append("__device__ __forceinline__ Fp<%s> fp_mul_chunk_dev<%s, %d>(const Fp<%s>& a, const FpChunk<%d>& t) {" % (name, name, cl, name, cl))
+            out.append("    using P = %s;" % name)
+            out.append("    Fp<P> r;")
+            out.append("    uint64_t lo = 0, cy0, cy1, cy2;")
+            out.append("    uint32_t hi = 0;")
+            out += emit(lower(lines))
+            out.append("    (void)cy0; (void)cy1; (void)cy2; (void)hi;")
+            out.append("    return r;")
+            out.append("}")
+            out.append("")
+            print(name, "chunk", cl, {k: v for k, v in stats.items() if k != "column_max"})
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "halo2-gpu-specific_amd", "csrc", "fp_mul_gen.hpp")
     with open(path, "w") as f:
         f.write("\n".join(out))
