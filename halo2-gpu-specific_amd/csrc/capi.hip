@@ -40,34 +40,26 @@ int bad(const char* msg) {
     return H2_ERR_INVALID;
 }
 
-// plan lookup is the only shared mutable state touched by the h2_dev_* paths
-PlanRef plan_locked(DeviceCtx* ctx, uint32_t log_n, const uint64_t omega[4], hipStream_t s, bool have_lock) {
-    if (have_lock) return ntt_get_plan(ctx, log_n, omega, s);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    return ntt_get_plan(ctx, log_n, omega, s);
-}
-
 int dev_ntt_impl(DeviceCtx* ctx, const Fr* src, Fr* dst, Fr* tmp, uint32_t in_len, const uint64_t omega[4],
-                 uint32_t log_n, const Fr* pre3, const Fr* post3, hipStream_t s, bool have_lock) {
+                 uint32_t log_n, const Fr* pre3, const Fr* post3, hipStream_t s) {
     if (log_n > 28) return bad("log_n exceeds the 2-adicity of Fr (S = 28)");
     std::vector<uint32_t> bits;
     ntt_split(log_n, bits);
     if (bits.size() >= 2 && tmp == nullptr) return bad("NTT of this size needs a scratch buffer (d_tmp)");
-    PlanRef pl = plan_locked(ctx, log_n, omega, s, have_lock);  // pinned until the passes are launched
+    PlanRef pl = ntt_get_plan(ctx, log_n, omega, s);  // pinned until the passes are launched
     ntt_run(ctx, pl.get(), src, dst, tmp, in_len, pre3, post3, s);
     return H2_OK;
 }
 
 int dev_extended_to_coeff_impl(DeviceCtx* ctx, Fr* d_a, Fr* d_tmp, uint32_t extended_k, const uint64_t g_coset[4],
                                const uint64_t g_coset_inv[4], const uint64_t extended_omega_inv[4],
-                               const uint64_t extended_ifft_divisor[4], hipStream_t s, bool have_lock) {
+                               const uint64_t extended_ifft_divisor[4], hipStream_t s) {
     // into_coset = false: coset_powers = [g_coset_inv, g_coset] (domain.rs:385-387), fused with the
     // iFFT divisor: y[i] *= divisor * {1, g_coset_inv, g_coset}[i % 3].
     Fr d = fr_from_u64x4(extended_ifft_divisor);
     Fr gi = fr_from_u64x4(g_coset_inv), g = fr_from_u64x4(g_coset);
     Fr post3[3] = {d, fp_mul(d, gi), fp_mul(d, g)};  // host-side Montgomery products
-    return dev_ntt_impl(ctx, d_a, d_a, d_tmp, 1u << extended_k, extended_omega_inv, extended_k, nullptr, post3, s,
-                        have_lock);
+    return dev_ntt_impl(ctx, d_a, d_a, d_tmp, 1u << extended_k, extended_omega_inv, extended_k, nullptr, post3, s);
 }
 
 // Elementwise host-slice operations over long vectors run as a pipeline of chunks on three streams of the slot: chunk c + 1
@@ -304,7 +296,7 @@ int host_ntt(HostCall& call, HostResult& res, const Fr* src, Fr* d_a, const uint
     Fr* d_t = (Fr*)call.ctx->buf_b.get(sizeof(Fr) << log_n);
     Fr post3[3];
     if (divisor) post3[0] = post3[1] = post3[2] = fr_from_u64x4(divisor);
-    H2_TRY(dev_ntt_impl(call.ctx, src, d_a, d_t, 1u << log_n, omega, log_n, nullptr, divisor ? post3 : nullptr, call.stream, true));
+    H2_TRY(dev_ntt_impl(call.ctx, src, d_a, d_t, 1u << log_n, omega, log_n, nullptr, divisor ? post3 : nullptr, call.stream));
     return res.write(d_a, call.stream);
 }
 const char* const BAD_LOG_N = "log_n exceeds the 2-adicity of Fr (S = 28)";
@@ -428,14 +420,12 @@ int h2_release_plans(void) {
             ~RestoreDevice() { (void)hipSetDevice(prev); }
         } restore;
         for (DeviceCtx* ctx : existing_contexts()) {
-            std::vector<NttPlan*> gone;
             H2_HIP(hipSetDevice(ctx->device));
             {
-                std::lock_guard<std::mutex> g(ctx->mu);      // no transform of this context is between lookup and launch
-                ntt_detach_idle_plans(ctx, gone);
-                ctx->coeff_arena.release();                   // (no call of the slot is running: its block of column vectors goes too)
+                std::lock_guard<std::mutex> g(ctx->mu);      // coeff_arena is the slot's: no host-slice call of it is running
+                ctx->coeff_arena.release();
             }
-            ntt_free_plans(gone);                             // synchronises and frees with no lock held
+            ntt_release_idle_plans(ctx);                      // synchronises and frees with no lock held
         }
         return (int)H2_OK;
     });
@@ -515,7 +505,7 @@ int h2_coeff_to_extended(const uint64_t* coeffs, uint64_t* out, uint32_t k, uint
         // into_coset = true: coset_powers = [g_coset, g_coset_inv] (domain.rs:383-385)
         Fr pre3[3] = {fr_from_u64x4(g_coset), fr_from_u64x4(g_coset), fr_from_u64x4(g_coset_inv)};
         const Fr* src = call.in(ctx->buf_a, coeffs, (size_t)1 << k);
-        H2_TRY(dev_ntt_impl(ctx, src, d_in, d_t, 1u << k, extended_omega, extended_k, pre3, nullptr, call.stream, true));
+        H2_TRY(dev_ntt_impl(ctx, src, d_in, d_t, 1u << k, extended_omega, extended_k, pre3, nullptr, call.stream));
         return res.write(d_in, call.stream);
     });
 }
@@ -535,7 +525,7 @@ int h2_extended_to_coeff(const uint64_t* a, uint64_t* out, size_t out_len, uint3
         Fr* d_a = (Fr*)call.upload(ctx->buf_a, a, ext_bytes);
         Fr* d_t = (Fr*)ctx->buf_b.get(ext_bytes);
         H2_TRY(dev_extended_to_coeff_impl(ctx, d_a, d_t, extended_k, g_coset, g_coset_inv, extended_omega_inv,
-                                          extended_ifft_divisor, call.stream, true));
+                                          extended_ifft_divisor, call.stream));
         return res.write(d_a, call.stream);
     });
 }
@@ -690,7 +680,7 @@ int h2_dev_ntt(void* d_a, void* d_tmp, const uint64_t omega[4], uint32_t log_n, 
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         return dev_ntt_impl(ctx, (Fr*)d_a, (Fr*)d_a, (Fr*)d_tmp, 1u << log_n, omega, log_n, nullptr, nullptr,
-                            pick_stream(ctx, stream), false);
+                            pick_stream(ctx, stream));
     });
 }
 
@@ -702,7 +692,7 @@ int h2_dev_intt(void* d_a, void* d_tmp, const uint64_t omega_inv[4], const uint6
         Fr d = fr_from_u64x4(divisor);
         Fr post3[3] = {d, d, d};
         return dev_ntt_impl(ctx, (Fr*)d_a, (Fr*)d_a, (Fr*)d_tmp, 1u << log_n, omega_inv, log_n, nullptr, post3,
-                            pick_stream(ctx, stream), false);
+                            pick_stream(ctx, stream));
     });
 }
 
@@ -717,7 +707,7 @@ int h2_dev_coeff_to_extended(const void* d_coeffs, void* d_out, void* d_tmp, uin
         Fr pre3[3] = {fr_from_u64x4(g_coset), fr_from_u64x4(g_coset), fr_from_u64x4(g_coset_inv)};
         if (d_coeffs == d_out && extended_k > 8 && d_tmp == nullptr) return bad("in-place extension needs d_tmp");
         return dev_ntt_impl(ctx, (const Fr*)d_coeffs, (Fr*)d_out, (Fr*)d_tmp, 1u << k, extended_omega, extended_k,
-                            pre3, nullptr, pick_stream(ctx, stream), false);
+                            pre3, nullptr, pick_stream(ctx, stream));
     });
 }
 
@@ -731,8 +721,8 @@ int h2_dev_coset_ntt(const void* d_coeffs, void* d_out, void* d_tmp, uint32_t lo
         std::vector<uint32_t> bits;
         ntt_split(log_n, bits);
         if (bits.size() >= 2 && d_tmp == nullptr) return bad("NTT of this size needs a scratch buffer (d_tmp)");
-        PlanRef pl = plan_locked(ctx, log_n, omega, s, false);
-        ScaleTabRef tab = ntt_scale_table(pl.get(), fr_from_u64x4(g), nullptr, s);
+        PlanRef pl = ntt_get_plan(ctx, log_n, omega, s);
+        NttTablePin tab = ntt_scale_table(pl.get(), fr_from_u64x4(g), nullptr, s);
         ntt_run(ctx, pl.get(), (const Fr*)d_coeffs, (Fr*)d_out, (Fr*)d_tmp, 1u << log_n, nullptr, nullptr, s, tab.get(), 1u);
         return (int)H2_OK;
     });
@@ -753,8 +743,8 @@ static int dev_ntt_batch_impl(const void* const* srcs, void* const* dsts, size_t
         std::vector<uint32_t> bits;
         ntt_split(log_n, bits);
         if (bits.size() >= 2 && d_tmp == nullptr) return bad("NTT of this size needs a scratch buffer (d_tmp)");
-        PlanRef pl = plan_locked(ctx, log_n, omega, s, false);
-        ScaleTabRef tab_ref;
+        PlanRef pl = ntt_get_plan(ctx, log_n, omega, s);
+        NttTablePin tab_ref;
         Fr d{};
         Fr post3[3];
         const Fr* post = nullptr;
@@ -820,9 +810,9 @@ int h2_dev_coset_intt(void* d_a, void* d_tmp, uint32_t log_n, const uint64_t g_i
         std::vector<uint32_t> bits;
         ntt_split(log_n, bits);
         if (bits.size() >= 2 && d_tmp == nullptr) return bad("NTT of this size needs a scratch buffer (d_tmp)");
-        PlanRef pl = plan_locked(ctx, log_n, omega_inv, s, false);
+        PlanRef pl = ntt_get_plan(ctx, log_n, omega_inv, s);
         const Fr d = fr_from_u64x4(divisor);
-        ScaleTabRef tab = ntt_scale_table(pl.get(), fr_from_u64x4(g_inv), &d, s);
+        NttTablePin tab = ntt_scale_table(pl.get(), fr_from_u64x4(g_inv), &d, s);
         ntt_run(ctx, pl.get(), (const Fr*)d_a, (Fr*)d_a, (Fr*)d_tmp, 1u << log_n, nullptr, nullptr, s, tab.get(), 2u);
         return (int)H2_OK;
     });
@@ -836,7 +826,7 @@ int h2_dev_extended_to_coeff(void* d_a, void* d_tmp, uint32_t extended_k, const 
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         return dev_extended_to_coeff_impl(ctx, (Fr*)d_a, (Fr*)d_tmp, extended_k, g_coset, g_coset_inv,
-                                          extended_omega_inv, extended_ifft_divisor, pick_stream(ctx, stream), false);
+                                          extended_omega_inv, extended_ifft_divisor, pick_stream(ctx, stream));
     });
 }
 
@@ -1806,7 +1796,7 @@ int h2_quotient_poly_coeff(const h2_evalh_desc* desc, const uint64_t* t_evaluati
                 host_upload(d_t, t_evaluations, t_len * sizeof(Fr), s);
                 H2_TRY(divide_by_vanishing_launch(d_values, size, d_t, t_len, s));
                 Fr* d_tmp = (Fr*)ctx->buf_b.get(size * sizeof(Fr));
-                H2_TRY(dev_extended_to_coeff_impl(ctx, d_values, d_tmp, ek, g_coset, g_coset_inv, extended_omega_inv, extended_ifft_divisor, s, true));
+                H2_TRY(dev_extended_to_coeff_impl(ctx, d_values, d_tmp, ek, g_coset, g_coset_inv, extended_omega_inv, extended_ifft_divisor, s));
                 return res.write(d_values, s);
             };
             bool finished = false;
@@ -1827,7 +1817,7 @@ int h2_dev_evaluate_h(const h2_evalh_desc* desc, void* d_values, void* stream) {
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         std::lock_guard<std::mutex> g(ctx->mu);  // the interpreter work space is per device
-        return evalh_device(ctx, desc, (Fr*)d_values, pick_stream(ctx, stream), true);
+        return evalh_device(ctx, desc, (Fr*)d_values, pick_stream(ctx, stream));
     });
 }
 

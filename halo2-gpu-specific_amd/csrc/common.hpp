@@ -60,7 +60,7 @@ bool host_pinned(const void* p);
 void host_upload(void* d_dst, const void* src, size_t bytes, hipStream_t s);
 void host_download(void* dst, const void* d_src, size_t bytes, hipStream_t s);
 
-struct NttPlan;  // ntt.hip
+struct NttCache;  // ntt.hpp
 
 // device copy of a registered host range of SRS points (resident.hip): `gen` is the registration it was uploaded for
 struct ResidentCopy {
@@ -72,11 +72,10 @@ struct ResidentCopy {
 // What the host-API slots of ONE physical device share: the transform plans (twiddle tables), the device copies of
 // registered SRS ranges (1 GiB + a 12 GiB table at k = 24: never per slot) and their accounting.
 struct DeviceShared {
-    std::mutex mu;                     // guards `resident` (a lookup may upload an SRS) and plan creation across the slots
+    std::mutex mu;                     // guards `resident` and `retired` (a lookup may upload an SRS)
     std::map<const void*, ResidentCopy> resident;  // registered host base ranges -> device copies (resident.hip)
     std::vector<ResidentCopy> retired;  // copies whose registration was replaced: freed by the next h2_bases_unregister, under every slot's lock
-    std::map<std::string, NttPlan*> plans;
-    size_t ntt_last_table_bytes = 0;   // of the optional last-pass tables (ntt.hip; guarded by ntt.hip's table mutex)
+    NttCache* ntt = nullptr;           // the NTT plans and their tables, under a lock of their own (ntt.hpp); created with this
 };
 
 // One host-API SLOT of a device: its own streams, staging buffers and scratch, so that two host-slice calls on one device
@@ -98,11 +97,8 @@ struct DeviceCtx {
     PinnedBuf pinned;
     DeviceShared* shared;
     std::map<const void*, ResidentCopy>& resident;
-    std::map<std::string, NttPlan*>& plans;
-    size_t& ntt_last_table_bytes;
     hipDeviceProp_t prop;
-    explicit DeviceCtx(DeviceShared* s)
-        : shared(s), resident(s->resident), plans(s->plans), ntt_last_table_bytes(s->ntt_last_table_bytes) {}
+    explicit DeviceCtx(DeviceShared* s) : shared(s), resident(s->resident) {}
 };
 
 // Device pool (HALO2_PROOFS_N_GPU honoured, prover.rs:57-70).

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "ntt.hpp"
 
 // HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue
 // serialise: the library alone runs a second MSM stream and a stream per host-API slot next to its caller's compute and
@@ -135,7 +136,10 @@ static DeviceCtx* ctx_at(int dev, int sub) {
     std::lock_guard<std::mutex> g(p.mu);
     const size_t at = (size_t)dev * p.slots + sub;
     if (!p.ctxs[at]) {
-        if (!p.shared[dev]) p.shared[dev] = new DeviceShared();
+        if (!p.shared[dev]) {
+            p.shared[dev] = new DeviceShared();
+            p.shared[dev]->ntt = new NttCache();
+        }
         DeviceCtx* c = new DeviceCtx(p.shared[dev]);
         c->device = dev;
         c->slot = sub;

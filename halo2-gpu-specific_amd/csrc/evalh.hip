@@ -535,7 +535,7 @@ static void evalh_plan_launch(const EvalhPlan* plan, const h2_evalh_desc* d, Fr*
 
 // ---------------------------------------------------------------- host driver
 
-int evalh_device(DeviceCtx* ctx, const h2_evalh_desc* d, Fr* d_values, hipStream_t stream, bool have_lock) {
+int evalh_device(DeviceCtx* ctx, const h2_evalh_desc* d, Fr* d_values, hipStream_t stream) {
     if (!d || !d_values) {
         set_last_error("h2_evaluate_h: null argument");
         return H2_ERR_INVALID;
@@ -567,14 +567,7 @@ int evalh_device(DeviceCtx* ctx, const h2_evalh_desc* d, Fr* d_values, hipStream
         if (EvalhPlanRef held = evalh_plan_get(d, nullptr)) {
             const EvalhPlan* plan = held.get();
             PlanRef pl;  // the power tables of extended_omega: pinned until the kernels that read them are launched
-            if (plan->uses_omega) {
-                if (have_lock) {
-                    pl = ntt_get_plan(ctx, d->extended_k, d->extended_omega, stream);
-                } else {
-                    std::lock_guard<std::mutex> g(ctx->mu);
-                    pl = ntt_get_plan(ctx, d->extended_k, d->extended_omega, stream);
-                }
-            }
+            if (plan->uses_omega) pl = ntt_get_plan(ctx, d->extended_k, d->extended_omega, stream);
             evalh_plan_launch(plan, d, d_values, plan->uses_omega ? pl->tw_lo : nullptr, plan->uses_omega ? pl->tw_hi : nullptr,
                               row_begin, row_end, stream);
             return H2_OK;
@@ -654,14 +647,7 @@ int evalh_device(DeviceCtx* ctx, const h2_evalh_desc* d, Fr* d_values, hipStream
 
     const int32_t last_rotation = -((int32_t)d->blinding_factors + 1);
     PlanRef pl;  // the power tables of extended_omega: pinned until the kernels that read them are launched
-    if (d->n_perm_sets) {
-        if (have_lock) {
-            pl = ntt_get_plan(ctx, d->extended_k, d->extended_omega, stream);
-        } else {
-            std::lock_guard<std::mutex> g(ctx->mu);
-            pl = ntt_get_plan(ctx, d->extended_k, d->extended_omega, stream);
-        }
-    }
+    if (d->n_perm_sets) pl = ntt_get_plan(ctx, d->extended_k, d->extended_omega, stream);
     {
         hipLaunchKernelGGL(k_evalh_expr, dim3(blocks), dim3(threads), 0, stream, p, d_inter, d_values, d_lk, d_sh);
     }
@@ -786,7 +772,7 @@ int evalh_host(DeviceCtx* ctx, const h2_evalh_desc* d, uint64_t* values) {
         void* d_values = nullptr;
         H2_HIP(hipMalloc(&d_values, bytes));
         owned.push_back(d_values);
-        int rc = evalh_device(ctx, &dd, (Fr*)d_values, ctx->stream, true);
+        int rc = evalh_device(ctx, &dd, (Fr*)d_values, ctx->stream);
         if (rc == H2_OK) {
             host_download(values, d_values, bytes, ctx->stream);
             H2_HIP(hipStreamSynchronize(ctx->stream));
@@ -934,7 +920,7 @@ static int evalh_coeffs_worker(DeviceCtx* ctx, const h2_evalh_desc* d, uint64_t*
         for (uint32_t t = 0; t < log_c; t++) omega = fp_sqr(omega);
         uint64_t omega_u[4], g_u[4];
         for (int i = 0; i < 4; i++) omega_u[i] = (uint64_t)omega.l[2 * i] | ((uint64_t)omega.l[2 * i + 1] << 32);
-        PlanRef pl = ntt_get_plan(ctx, d->k, omega_u, stream);  // the caller holds ctx->mu (DeviceLease)
+        PlanRef pl = ntt_get_plan(ctx, d->k, omega_u, stream);
         const unsigned nblocks = (unsigned)((n + 255) / 256);
         const Fr w_step = fp_pow_u32(w_ext, step);
         Fr g = fp_mul(zeta, fp_pow_u32(w_ext, first));  // g_first
@@ -951,7 +937,7 @@ static int evalh_coeffs_worker(DeviceCtx* ctx, const h2_evalh_desc* d, uint64_t*
                     dsts.push_back(kv.second.second);
                     tmps.push_back(d_tmp + (tmps.size() % batch_width) * n);
                 }
-                ScaleTabRef tab = ntt_scale_table(pl.get(), g, nullptr, stream);
+                NttTablePin tab = ntt_scale_table(pl.get(), g, nullptr, stream);
                 for (size_t at = 0; at < srcs.size(); at += batch_width)   // (a chunk's scratch slots are distinct)
                     ntt_run_many(ctx, pl.get(), srcs.data() + at, dsts.data() + at, tmps.data() + at,
                                  std::min(batch_width, srcs.size() - at), (uint32_t)n, nullptr, nullptr, stream, tab.get(), 1u);
@@ -986,7 +972,7 @@ static int evalh_coeffs_worker(DeviceCtx* ctx, const h2_evalh_desc* d, uint64_t*
             dd.l0 = on_coset(d->l0);
             dd.l_last = on_coset(d->l_last);
             dd.l_active_row = (const uint64_t*)d_active_j;
-            int rc = evalh_device(ctx, &dd, d_values_j, stream, true);
+            int rc = evalh_device(ctx, &dd, d_values_j, stream);
             if (rc != H2_OK) {
                 cleanup();
                 return rc;

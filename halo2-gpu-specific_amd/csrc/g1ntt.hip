@@ -180,7 +180,6 @@ int g1_ntt_launch(DeviceCtx* ctx, const uint64_t* d_in, uint64_t* d_out, uint32_
         if (log_n >= 2) {
             uint64_t om[4];
             fr_to_u64x4(w, om);
-            std::lock_guard<std::mutex> g(ctx->mu);
             pl = ntt_get_plan(ctx, log_n, om, stream);
             tw_lo = pl->tw_lo;
             tw_hi = pl->tw_hi;

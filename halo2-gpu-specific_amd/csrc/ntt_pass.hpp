@@ -1,0 +1,72 @@
+// ntt_pass.hpp -- what ntt.hip (schedule, plans, table cache) needs of ntt_pass.hip (the device code): the argument block of a
+// pass, the kernel ids, the launcher and the table fillers.  Internal to the two files.
+#pragma once
+#include "common.hpp"
+
+namespace h2 {
+
+static constexpr int NTT_BATCH_MAX = 16;  // vectors per launch of a batched transform (pointers travel in the kernel arguments)
+static constexpr int LO_BITS = 12;  // two-level twiddle tables: w^e = lo[e & 4095] * hi[e >> 12]
+
+using TwChunk = FpChunk<2>;   // four chunks of 64 bits (eight of 32 bits measured slower: DESIGN.md)
+static constexpr uint32_t TW_CHUNK_FR = sizeof(TwChunk) / sizeof(Fr);   // table elements per entry
+static constexpr uint32_t TW_CHUNK_Q = sizeof(TwChunk) / sizeof(uint4);  // 16-byte words per entry
+
+struct PassArgs {
+    const Fr* in;
+    Fr* out;
+    const Fr* tw_bfly;  // R/2 entries: (w^(n/R))^e   (CW kernels: R/2 PAIRS -- plain value, quotient -- like tw_direct; see tw_store)
+    const Fr* tw_chunk;  // k_ntt_pass8: the same R/2 values as chunk tables (tw_store's third form)
+    const Fr* tw_lo;    // min(n, 4096) entries: w^i
+    const Fr* tw_hi;    // n >> 12 entries: w^(i << 12)   (unused when n <= 4096)
+    const Fr* tw_direct;  // non-null: inter-pass twiddle = tw_direct[(rho << consumed) | K] (no generation multiply)
+    uint32_t direct_kmajor;  // ... = tw_direct[(K << B) | rho] instead (the last pass's table: read in load order)
+    uint32_t hi_scaled;  // tw_hi already carries the uniform post-scale (1/n): never skip, no post multiply
+    Fr pre3[3];         // has_pre3: x *= pre3[idx % 3] on the first-pass load (idx % 3 == 0 skipped)
+    Fr post3[3];        // has_post3: y *= post3[idx % 3] on the final store
+    uint32_t has_pre3, has_post3, post3_uniform;
+    uint32_t log_n, B, s_log, t_log;
+    uint32_t nprev;       // number of earlier passes
+    uint32_t prevB[4];    // their bit widths
+    uint32_t prevT[4];    // their T_q logs
+    uint32_t is_last, in_len, log_c;
+    // generic coset scale (coeff -> one coset of the extended domain and back): sc[i] = g^i = sc_lo[i & 4095] * sc_hi[i >> 12]
+    // (sc_hi also carries the iNTT divisor).  scale_mode 1: x[i] *= sc[i] on the first pass's load (the inter-pass twiddle
+    // path, which a first pass never uses, does it); 2: y[i] *= sc[i] on the final store
+    const Fr* sc_lo;
+    const Fr* sc_hi;
+    uint32_t scale_mode;
+    // several transforms of one plan in ONE launch (blockIdx.y picks the vector): a 2^20-point pass is 1024 tiles, one
+    // resident round of the chip in which every workgroup waits out its own load -> stages -> store chain; with the
+    // tiles of 8-16 vectors in the grid the rounds overlap (the columns of a wide witness on one coset)
+    uint32_t batch;
+    const Fr* in_b[NTT_BATCH_MAX];
+    Fr* out_b[NTT_BATCH_MAX];
+    uint32_t zskip;  // first pass of a zero-padded transform: rows rho >= R >> zskip are zero (see the load loop)
+    uint32_t radix4;  // stage loop: two stages per LDS round trip (four elements per lane), launched with R / 4 * C threads
+};
+
+// Which kernel a pass runs (the values are h2_ntt_shape's kernel ids, H2_NTT_KERNEL_* in halo2_hip.h): chosen by pass_kernel
+// (ntt.hip) only; the launcher indexes pass_fn with it and h2_ntt_shape reports it.
+enum NttKernel : uint32_t {
+    NK_PASS8_DP = H2_NTT_KERNEL_PASS8_DP,
+    NK_PASS8 = H2_NTT_KERNEL_PASS8,
+    NK_R4_DP = H2_NTT_KERNEL_R4_DP,
+    NK_R4 = H2_NTT_KERNEL_R4,
+    NK_R2 = H2_NTT_KERNEL_R2,
+};
+
+// One pass over `cnt` vectors on `threads` lanes per tile; the grid and the dynamic LDS follow from the kernel and a.log_n /
+// a.B / a.log_c.  `device`: the current one (the LDS limit of the general kernels is raised once per device: 9-bit passes).
+void ntt_pass_launch(int device, NttKernel kernel, const PassArgs& a, uint32_t cnt, uint32_t threads, hipStream_t stream);
+
+// Table fillers: one kernel each on `stream` (none for an empty table).  `form`: tw_store's `pair` (ntt_pass.hip).
+void ntt_fill_pow(Fr* out, const Fr& base, uint32_t mul, uint32_t count, uint32_t form, hipStream_t stream);  // out[i] = base^(i mul)
+// out[(rho << kbits) | K] = base^((rho K << s_log) mod n): the complete inter-pass twiddle set of a middle pass
+void ntt_fill_direct(Fr* out, const Fr& base, uint32_t kbits, uint32_t s_log, uint32_t log_n, uint32_t count, uint32_t form,
+                     hipStream_t stream);
+// out[(K << bits) | rho] = base^((rho K) mod n) (* d when given), 2^log_n Montgomery values (log_n >= 8): the last pass's, in load order
+void ntt_fill_last(Fr* out, const Fr& base, uint32_t bits, uint32_t log_n, const Fr* d, hipStream_t stream);
+void ntt_fill_scaled(Fr* out, const Fr* in, const Fr& d, uint32_t count, hipStream_t stream);  // out[i] = in[i] * d
+
+}  // namespace h2

@@ -222,6 +222,29 @@ def test_ntt_shape_reports_the_documented_plan():
                     assert mc.KERNELS[p["kernel"]] == "k_ntt_pass<true, %s>" % ("false" if last else "true")
 
 
+def test_ntt_shape_equals_the_recorded_table():
+    """h2_ntt_shape for every log_n in 0 .. 28 and every in_log in 0 .. log_n, with default knobs, under H2_NTT_NINE=0 and
+    under H2_NTT_NO_ZSKIP=1 (a child process each), equals tests/golden/ntt_shape_table.json row for row: the table was
+    recorded from the library before the pass schedule moved into one function (ntt_schedule) that the plan builder, the
+    launcher and h2_ntt_shape share"""
+    import json
+
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    try:
+        import gen_ntt_shape_table as gen
+    finally:
+        sys.path.pop(0)
+    with open(os.path.join(ROOT, "tests", "golden", "ntt_shape_table.json")) as f:
+        want = json.load(f)["settings"]
+    assert [s["knobs"] for s in want] == list(gen.SETTINGS) == [{}, {"H2_NTT_NINE": "0"}, {"H2_NTT_NO_ZSKIP": "1"}]
+    for setting in want:
+        got = gen.rows_under(setting["knobs"])
+        assert len(got) == len(setting["rows"]) == 29 * 30 // 2
+        assert [r[:2] for r in got] == [[log_n, in_log] for log_n in range(29) for in_log in range(log_n + 1)]
+        for g, w in zip(got, setting["rows"]):
+            assert g == w, (setting["knobs"], g, w)
+
+
 def test_ntt_shape_bad_arguments():
     L = h2.lib()
     out = np.zeros((8, 7), dtype=np.uint32)
