@@ -129,6 +129,8 @@ SYMBOLS = {
     "h2_permutation_mapping_scratch_bytes": (_sz, [_sz, _sz, _sz]),
     "h2_dev_permutation_mapping": (ctypes.c_int, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
     "h2_dev_permutation_mapping_phases": (ctypes.c_int, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _fp, _vp]),
+    "h2_cells_place_scratch_bytes": (_sz, [_sz]),
+    "h2_dev_cells_place": (ctypes.c_int, [_vp, _sz, _sz, _u32, _vp, _sz, _vp]),
     "h2_check_scratch_bytes": (_sz, [_sz]),
     "h2_dev_check_nonzero_rows": (ctypes.c_int, [_vp, _sz, _vp, _vp, _vp]),
     "h2_dev_check_gates": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _sz, _vp]),

@@ -135,6 +135,7 @@ class ConstraintSystem:
         self.lookup_tracer = {}      # table identifier -> (name, [table Expression], [(name, [input Expression])])
         self.shuffle_tracer = []     # (name, [input Expression], [shuffle Expression])
         self.range_checks = []       # (origin advice index, sort advice index, min, max, step): range_check::Argument
+        self.constants = []          # fixed columns that take the constants of a floor planner (enable_constant)
 
     # -- columns ------------------------------------------------------------------------------------------
     def advice_column(self):
@@ -170,6 +171,17 @@ class ConstraintSystem:
     def instance_column(self):
         self.num_instance += 1
         return ("instance", self.num_instance - 1)
+
+    def lookup_table_column(self):
+        """circuit.rs:1755-1759: a fixed column that `Layouter.assign_table` fills"""
+        return self.fixed_column()
+
+    def enable_constant(self, column):
+        """circuit.rs:1301-1306: the floor planner may put constants into this fixed column; it joins the permutation"""
+        assert column[0] == "fixed"
+        if column not in self.constants:
+            self.constants.append(column)
+            self.enable_equality(column)
 
     # -- queries (circuit.rs:1478-1560) -----------------------------------------------------------------------
     def _query(self, column, rotation):

@@ -110,7 +110,9 @@ def cs_store(cs):
     """write_cs (helpers.rs:406-456) -> bytes"""
     out = [_u32(cs.num_advice), _u32(cs.num_instance), _u32(0), _u32(cs.num_fixed), _u32(len(cs.num_advice_queries))]
     out += [_u32(v) for v in cs.num_advice_queries]
-    out += [_u32(0), _u32(0)]                                   # selector_map, constants: no selectors / constant columns
+    out.append(_u32(0))                                         # selector_map: no selectors
+    out.append(_u32(len(cs.constants)))                         # constants: write_fixed_columns (helpers.rs:386-395)
+    out += [_u32(index) for _, index in cs.constants]
     for queries in (cs.advice_queries, cs.instance_queries, cs.fixed_queries):
         out.append(_u32(len(queries)))
         for column, rotation in queries:
@@ -150,7 +152,7 @@ def cs_store(cs):
 
 def cs_fetch(r, name="circuit"):
     """read_cs (helpers.rs:458-561) -> ConstraintSystem; refuses what this prover does not implement (selectors that
-    were not compiled away, constant columns)"""
+    were not compiled away)"""
     cs = circuit.ConstraintSystem(name)
     cs.num_advice, cs.num_instance = r.u32(), r.u32()
     if r.u32():
@@ -158,8 +160,8 @@ def cs_fetch(r, name="circuit"):
     cs.num_fixed = r.u32()
     cs.num_advice_queries = [r.u32() for _ in range(r.u32())]
     selector_map = [r.u32() for _ in range(r.u32())]
-    constants = [r.u32() for _ in range(r.u32())]
-    del selector_map, constants                                 # keygen-time information only
+    cs.constants = [("fixed", r.u32()) for _ in range(r.u32())]
+    del selector_map                                            # keygen-time information only
     lists = []
     for _ in range(3):
         lists.append([(r.u32(), r.i32()) for _ in range(r.u32())])
@@ -199,6 +201,15 @@ def vk_digest(cs, dom, fixed_commitments, perm_commitments):
     shuffles, instance columns: cs_store) and the fixed / permutation commitments.  Two circuits that differ in
     any gate, lookup or query therefore get different transcripts.  `keygen(..., transcript_repr=...)` overrides the
     value with one dumped from the Rust side (tools/ref_dump) once that can be pinned."""
+    h = hashlib.blake2b(digest_size=64, person=b"Halo2-Verify-Key")
+    h.update(vk_digest_preimage(cs, dom, fixed_commitments, perm_commitments))
+    return int.from_bytes(h.digest(), "little") % R_MOD
+
+
+def vk_digest_preimage(cs, dom, fixed_commitments, perm_commitments):
+    """what vk_digest hashes: a u64 length, then the pinned verifying key in this build's binary form.  The constants
+    columns of the constraint system (PinnedConstraintSystem's `constants`, circuit.rs:1137-1152) are part of it through
+    cs_store, as a count and the columns' indices; a circuit without any contributes the zero count it always has."""
     cs_bytes = cs_store(cs)
     body = [b"halo2-hip-vk-v2", dom.k.to_bytes(4, "little"), dom.extended_k.to_bytes(4, "little"),
             dom.omega.to_bytes(32, "little"), R_MOD.to_bytes(32, "little"), Q_MOD.to_bytes(32, "little"),
@@ -207,7 +218,4 @@ def vk_digest(cs, dom, fixed_commitments, perm_commitments):
         body.append(len(group).to_bytes(4, "little"))
         body += [point_to_bytes(p) for p in group]
     body = b"".join(body)
-    h = hashlib.blake2b(digest_size=64, person=b"Halo2-Verify-Key")
-    h.update(len(body).to_bytes(8, "little"))
-    h.update(body)
-    return int.from_bytes(h.digest(), "little") % R_MOD
+    return len(body).to_bytes(8, "little") + body

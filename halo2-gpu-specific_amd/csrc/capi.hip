@@ -18,6 +18,7 @@
 #include "poly.hpp"
 #include "logup.hpp"
 #include "permmap.hpp"
+#include "place.hpp"
 #include "rangecheck.hpp"
 #include "resident.hpp"
 #include "scan.hpp"
@@ -1584,6 +1585,19 @@ int h2_dev_range_check_complete(void* const* d_origins, void* const* d_companion
         return range_check_complete_launch(d_origins, d_companions, origin_forms, companion_forms, vmin, vmax, step,
                                            first_unassigned, pairs, usable_rows, n, (uint32_t*)d_status, d_scratch,
                                            pick_stream(ctx, stream));
+    });
+}
+
+// ------------------------------------------------------------------ the circuit front end's device assembly
+size_t h2_cells_place_scratch_bytes(size_t count) { return cells_place_scratch_bytes(count); }
+
+int h2_dev_cells_place(const h2_place_segment* segments, size_t count, size_t n, uint32_t out_form, void* d_scratch,
+                       size_t scratch_bytes, void* stream) {
+    if (const char* what = cells_place_validate(segments, count, n, out_form, d_scratch, scratch_bytes))
+        return bad((std::string("h2_dev_cells_place: ") + what).c_str());
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return cells_place_launch(segments, count, n, out_form, d_scratch, pick_stream(ctx, stream));
     });
 }
 

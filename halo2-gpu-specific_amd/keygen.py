@@ -132,7 +132,8 @@ def program_descriptor(cs, k, extended_k, graph=None, value_parts=None, lookup_c
 
 
 def keygen(device, params, cs, fixed, copies, mapping=None, fixed_montgomery=False, transcript_repr=None, strict_rationals=False):
-    """keygen_vk + keygen_pk.  fixed: list of canonical (n, 4) u64 columns; copies: see permutation_mapping.
+    """keygen_vk + keygen_pk.  fixed: list of canonical (n, 4) u64 columns, host arrays or device tensors; copies: see
+    permutation_mapping.
     `mapping` = (map_col, map_row) replaces `copies` and `fixed_montgomery` marks columns already in the in-memory
     representation: the two things a CircuitData file holds (keygen_pk_from_info, plonk/keygen.rs:458-553).
     A fixed column may be a `Rational` (batch_invert_assigned, keygen.rs:276): resolved on the device straight to the
@@ -159,7 +160,9 @@ def keygen(device, params, cs, fixed, copies, mapping=None, fixed_montgomery=Fal
         if resolved:                                                 # Montgomery already
             pk.fixed_values.append(col)
             continue
-        t = D.upload(col)
+        # a resident column (synthesis.synthesize_keygen on the device): Montgomery residues stay with the key as they
+        # are, canonical values are converted in a copy -- the caller's tensor is not written
+        t = D.upload(col) if not D.torch.is_tensor(col) else col if fixed_montgomery else D.clone(col)
         if not fixed_montgomery:
             check(L.h2_dev_batch_mont(t.data_ptr(), n, D.stream), "h2_dev_batch_mont")
         pk.fixed_values.append(t)

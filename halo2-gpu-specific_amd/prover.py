@@ -1,5 +1,6 @@
 """create_proof on the device-resident C ABI: the caller of the hot path -- and the package's public
-surface: the names of device.py, params.py, keygen.py, witness.py, check.py and assigned.py are re-exported below.
+surface: the names of device.py, params.py, keygen.py, witness.py, check.py, assigned.py and synthesis.py are re-exported
+below.
 
 Every polynomial lives in HBM from upload to the last opening; the host sees only what the protocol hashes
 (commitments, evaluations) plus the handful of low coefficients SHPLONK adjusts.  Orchestration follows
@@ -29,7 +30,7 @@ from .assigned import (ASSIGNED_BAD_ROWS, ASSIGNED_FORM_CANONICAL, ASSIGNED_FORM
 from .check import (CHECK_COPY, CHECK_GATE, CHECK_LOOKUP, CHECK_SHUFFLE, ConstraintNotSatisfied, Lookup, Permutation,  # noqa: F401
                     Shuffle, assert_satisfied, check_failures, check_result, check_witness)
 from .circuit import compile_evaluator  # noqa: F401
-from .cs_format import vk_digest  # noqa: F401
+from .cs_format import vk_digest, vk_digest_preimage  # noqa: F401
 from .device import CosetTables, Device, footprint, g1_ntt, max_scalar_bits, parse_bytes, sharding_description  # noqa: F401
 from .domain import DELTA, ROOT_OF_UNITY, ZETA, Domain, _fr, _vp  # noqa: F401
 from .keygen import (PERM_MAPPING_SORT_TILE, PM_INTERNAL, PM_OK, PM_OUT_OF_BOUNDS, PM_STATUS_WORDS, ProvingKey, _ANY,  # noqa: F401
@@ -37,6 +38,9 @@ from .keygen import (PERM_MAPPING_SORT_TILE, PM_INTERNAL, PM_OK, PM_OUT_OF_BOUND
 from .multiopen import _gwc, _shplonk
 from .parallel import allgather_rows, allreduce_counts, allreduce_max, coset_unmix_matrix, exchange_cosets, msm_split_range, scatter_cosets
 from .params import Params  # noqa: F401
+from .synthesis import (AssignedCells, BoundsFailure, Circuit, ColumnNotInPermutation, DeviceColumns, FlatFloorPlanner,  # noqa: F401
+                        HostColumns, Layouter, NotEnoughColumnsForConstants, NotEnoughRowsAvailable, Region, SynthesisError, Table, V1,
+                        region_starts, synthesize_keygen, synthesize_witness)
 from .transcript import Blake2bWrite, R_MOD, fr_to_mont_limbs, g1_add_affine
 from .witness import (RC_FORM_CANONICAL, RC_FORM_COMPACT, RC_FORM_MONTGOMERY, RC_IN_USE, RC_NO_FIT, RC_OK, RC_OUT_OF_RANGE,  # noqa: F401
                       RC_STATUS_WORDS, RC_UNSUPPORTED, _compress, _instance_columns, _witness_sets, complete_range_check_witness,

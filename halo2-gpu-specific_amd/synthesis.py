@@ -1,0 +1,680 @@
+"""A circuit front end: `Circuit`, `Layouter`, `Region`, `Table`, the floor planners `FlatFloorPlanner` and `V1`, and the two
+assemblies the assignments end up in.
+
+  Circuit / Layouter / Region / Table   circuit.rs (Layouter :393-474, Region :172-360, Table :362-391)
+  SimpleTableLayouter                   circuit/floor_planner/single_pass.rs:56-110, flat.rs:177-233
+  FlatFloorPlanner                      circuit/floor_planner/flat.rs:33-95
+  V1                                    circuit/floor_planner/v1.rs:65-161, v1/strategy.rs:107-225
+  errors                                plonk/error.rs
+
+The front end is a BULK one: an assignment covers a range of cells (`count` cells `stride` rows apart), never one Python call
+per cell of a 2^22-row column.  Values are a Python integer (one cell, or the same value for `count` cells), a 1-D u64 array
+(compact cells: 8 bytes each), an (m, 4) u64 array (canonical cells), a device tensor of either shape (values torch code
+computed on the device: they never visit the host), or None (keygen, `without_witnesses`).
+
+Two assemblies sit behind one interface: `HostColumns` writes numpy columns; `DeviceColumns` gathers the ranges into a segment
+list that ONE launch of h2_dev_cells_place (csrc/place.hip) places into resident columns.  The reference lets a later
+assignment of a cell win; the device assembly keeps that by flushing its queue before it queues a segment that may overlap a
+queued one of the same column.
+"""
+import math
+import time
+
+import numpy as np
+
+from ._lib import check
+from .circuit import R_MOD, ConstraintSystem
+
+PLACE_FORM_CANONICAL, PLACE_FORM_COMPACT, PLACE_FORM_BROADCAST = 0, 1, 2               # H2_PLACE_FORM_*
+PLACE_OUT_CANONICAL, PLACE_OUT_MONTGOMERY = 0, 1                                       # H2_PLACE_OUT_*
+# h2_place_segment: dst, src, first_row, stride, count (u64 each), form, reserved (u32 each)
+PLACE_SEGMENT = np.dtype([("dst", "<u8"), ("src", "<u8"), ("first_row", "<u8"), ("stride", "<u8"), ("count", "<u8"),
+                          ("form", "<u4"), ("reserved", "<u4")])
+_MASK64 = (1 << 64) - 1
+_COLUMN_ORDER = {"instance": 0, "advice": 1, "fixed": 2}                               # Column's Ord (plonk/circuit.rs:47-105)
+
+
+# -- errors (plonk/error.rs) ---------------------------------------------------------------------------------------------
+class SynthesisError(Exception):
+    """Error::Synthesis: a table used wrongly, a value missing where one is needed"""
+
+
+class NotEnoughRowsAvailable(SynthesisError):
+    """a cell at or beyond the usable rows of a 2^k-row circuit"""
+
+    def __init__(self, k):
+        SynthesisError.__init__(self, "k = %d is too small for the given circuit" % k)
+        self.current_k = k
+
+
+class NotEnoughColumnsForConstants(SynthesisError):
+    """more constants than free cells in the columns of `enable_constant`"""
+
+
+class ColumnNotInPermutation(SynthesisError):
+    """a copy constraint on a column without `enable_equality`"""
+
+    def __init__(self, column):
+        SynthesisError.__init__(self, "column %s[%d] is not in the permutation (enable_equality)" % column)
+        self.column = column
+
+
+class BoundsFailure(SynthesisError):
+    """a column the constraint system does not have"""
+
+
+# -- values --------------------------------------------------------------------------------------------------------------
+def _limbs(v):
+    v %= R_MOD
+    return [(v >> (64 * j)) & _MASK64 for j in range(4)]
+
+
+class _Values:
+    """one assignment's values: kind = "none" | "int" | "host" | "device"; compact = one u64 per cell"""
+
+    def __init__(self, values, count):
+        self.data, self.compact = values, False
+        if values is None:
+            self.kind, self.count = "none", 1 if count is None else count
+        elif isinstance(values, (int, np.integer)):
+            self.kind, self.data, self.count = "int", int(values) % R_MOD, 1 if count is None else count
+        elif isinstance(values, np.ndarray):
+            if values.dtype != np.uint64 or not (values.ndim == 1 or (values.ndim == 2 and values.shape[1] == 4)):
+                raise TypeError("cell values are u64 arrays of shape (m,) or (m, 4)")
+            self.kind, self.compact, self.count = "host", values.ndim == 1, len(values)
+        elif hasattr(values, "data_ptr"):
+            if not values.is_cuda or values.element_size() != 8 or not (values.dim() == 1 or (values.dim() == 2 and values.shape[1] == 4)):
+                raise TypeError("resident cell values are 64-bit device tensors of shape (m,) or (m, 4)")
+            if not values.is_contiguous():
+                values = self.data = values.contiguous()
+            self.kind, self.compact, self.count = "device", values.dim() == 1, values.shape[0]
+        else:
+            raise TypeError("cell values: an integer, a u64 array, a device tensor or None")
+        if count is not None and self.kind in ("host", "device") and count != self.count:
+            raise ValueError("%d values for %d cells" % (self.count, count))
+
+    def first(self):
+        """the first value as an integer (a table column's default)"""
+        if self.kind == "int":
+            return self.data
+        if self.kind == "none" or self.count == 0:
+            return None
+        head = self.data[:1]
+        if self.kind == "device":
+            head = head.cpu().numpy().view(np.uint64)
+        return int(head[0]) if self.compact else sum(int(x) << (64 * j) for j, x in enumerate(head[0]))
+
+
+class AssignedCells:
+    """`count` assigned cells of one column, `stride` rows apart from `row` on: what an assignment returns and what the
+    constraints of a region take.  Slicing gives the sub-range."""
+
+    def __init__(self, column, row, count=1, stride=1):
+        self.column, self.row, self.count, self.stride = column, row, count, stride
+
+    def __len__(self):
+        return self.count
+
+    def __getitem__(self, key):
+        if isinstance(key, slice):
+            start, stop, step = key.indices(self.count)
+            if step < 1:
+                raise ValueError("cells are sliced forwards")
+            return AssignedCells(self.column, self.row + start * self.stride, len(range(start, stop, step)), self.stride * step)
+        if not -self.count <= key < self.count:
+            raise IndexError(key)
+        return AssignedCells(self.column, self.row + (key % self.count) * self.stride, 1, 1)
+
+    def rows(self):
+        return self.row + self.stride * np.arange(self.count, dtype=np.int64)
+
+    def __repr__(self):
+        return "AssignedCells(%s[%d], row %d, %d x %d)" % (self.column + (self.row, self.count, self.stride))
+
+
+# -- the two assemblies --------------------------------------------------------------------------------------------------
+class HostColumns:
+    """`count` canonical (n, 4) u64 numpy columns, zero until assigned; `alloc(count, n)` supplies them (Device.pinned_columns)"""
+
+    def __init__(self, count, n, alloc=None):
+        self.n = n
+        self.columns = list(alloc(count, n)) if alloc and count else [np.zeros((n, 4), dtype=np.uint64) for _ in range(count)]
+
+    def place(self, index, row, stride, vals):
+        if vals.count == 0:
+            return
+        target = self.columns[index][row:row + (vals.count - 1) * stride + 1:stride]
+        if vals.kind == "int":
+            target[:] = np.array(_limbs(vals.data), dtype=np.uint64)
+            return
+        data = vals.data if vals.kind == "host" else vals.data.cpu().numpy().view(np.uint64)
+        if vals.compact:
+            target[:, 0], target[:, 1:] = data, 0
+        else:
+            target[:] = data
+
+    def finish(self):
+        return self.columns
+
+
+class _Arena:
+    """page-locked staging of one form's host values: appended to as the regions assign, uploaded once per flush"""
+
+    def __init__(self, torch, width):
+        self.torch, self.width, self.used, self.buf, self.busy = torch, width, 0, None, None
+        self.pack_seconds = 0.0
+
+    def append(self, data):
+        begin = time.perf_counter()
+        at = self._append(data)
+        self.pack_seconds += time.perf_counter() - begin
+        return at
+
+    def _append(self, data):
+        if self.busy is not None:                 # the previous flush's upload still reads the buffer
+            self.busy.synchronize()
+            self.busy = None
+        need = self.used + len(data)
+        if self.buf is None or need > len(self.buf):
+            grown = self.torch.empty((max(need, 2 * (len(self.buf) if self.buf is not None else 0), 1 << 12), self.width),
+                                     dtype=self.torch.int64).pin_memory()
+            if self.used:
+                grown[:self.used] = self.buf[:self.used]
+            self.buf = grown
+        self.buf.numpy().view(np.uint64)[self.used:need] = data.reshape(len(data), self.width)
+        self.used = need
+        return need - len(data)
+
+
+class DeviceColumns:
+    """`count` resident (n, 4) columns, zero until assigned, written by h2_dev_cells_place: canonical, or Montgomery residues
+    (`montgomery`: keygen's fixed columns).  Host values are staged in one page-locked arena per form and cross PCIe once per
+    flush, compact cells at 8 bytes; device tensors are read where they are.  A segment that may overlap a queued one of its
+    column flushes the queue first, so that the later assignment wins as it does in the reference."""
+
+    def __init__(self, device, count, n, montgomery=False, timed=False):
+        self.D, self.n, self.out_form = device, n, PLACE_OUT_MONTGOMERY if montgomery else PLACE_OUT_CANONICAL
+        self.columns = [device.zeros(n) for _ in range(count)]
+        # the staging arenas stay with the Device between syntheses (page-locking memory costs more than filling it); an
+        # assembly takes a pair for its lifetime and hands it back in finish()
+        pool = device.__dict__.setdefault("_place_arenas", [])
+        self.arenas = pool.pop() if pool else {False: _Arena(device.torch, 4), True: _Arena(device.torch, 1)}
+        for arena in self.arenas.values():
+            arena.pack_seconds = 0.0
+        self.queue, self.boxes, self.keep = [], {}, []
+        self.cells_placed = self.flushes = 0
+        self.timed, self.kernel_ms, self.flush_seconds = timed, 0.0, 0.0
+
+    @staticmethod
+    def _may_overlap(a, b):
+        (r0, s0, c0), (r1, s1, c1) = a, b
+        if r0 + (c0 - 1) * s0 < r1 or r1 + (c1 - 1) * s1 < r0:
+            return False
+        return (r1 - r0) % math.gcd(s0, s1) == 0
+
+    def _overlaps_queued(self, index, row, stride, count):
+        """may this range write a cell that a queued segment of the column writes?  Exact for single cells, conservative for
+        two strided ranges (same residue modulo the gcd of the strides, inside each other's bounds)"""
+        box = self.boxes.get(index)
+        last = row + (count - 1) * stride
+        if box is None or last < box[0] or row > box[1]:
+            return False
+        spans, singles = box[2], box[3]
+        if count == 1:
+            if row in singles:
+                return True
+        elif singles and any(row <= r <= last and (r - row) % stride == 0 for r in singles):
+            return True
+        return any(self._may_overlap((row, stride, count), other) for other in spans)
+
+    def place(self, index, row, stride, vals):
+        if vals.count == 0:
+            return
+        if self._overlaps_queued(index, row, stride, vals.count):
+            self.flush()
+        last = row + (vals.count - 1) * stride
+        box = self.boxes.setdefault(index, [row, last, [], set()])
+        box[0], box[1] = min(box[0], row), max(box[1], last)
+        if vals.count == 1:
+            box[3].add(row)
+        else:
+            box[2].append((row, stride, vals.count))
+        if vals.kind == "int":
+            form, source = PLACE_FORM_BROADCAST, (False, self.arenas[False].append(np.array([_limbs(vals.data)], dtype=np.uint64)))
+        elif vals.kind == "host":
+            form = PLACE_FORM_COMPACT if vals.compact else PLACE_FORM_CANONICAL
+            source = (vals.compact, self.arenas[vals.compact].append(vals.data))
+        else:
+            form, source = PLACE_FORM_COMPACT if vals.compact else PLACE_FORM_CANONICAL, vals.data
+            self.keep.append(vals.data)
+        self.queue.append((index, row, stride, vals.count, form, source))
+
+    def flush(self):
+        if not self.queue:
+            return
+        started = time.perf_counter()
+        self._flush()
+        self.flush_seconds += time.perf_counter() - started
+
+    def _flush(self):
+        D, torch = self.D, self.D.torch
+        caller = torch.cuda.current_stream(D.dev)
+        with torch.cuda.stream(D.tstream):
+            if self.keep:                          # tensors of the caller's stream: ordered before the launch, alive until after
+                ready = torch.cuda.Event()
+                ready.record(caller)
+                D.tstream.wait_event(ready)
+                for t in self.keep:
+                    t.record_stream(D.tstream)
+            base = {}
+            for compact, arena in self.arenas.items():
+                if arena.used:
+                    staged = arena.buf[:arena.used].to(D.dev, non_blocking=True)
+                    arena.busy = torch.cuda.Event()
+                    arena.busy.record(D.tstream)
+                    base[compact] = (staged, staged.data_ptr(), 8 if compact else 32)
+                    arena.used = 0
+        segs = np.zeros(len(self.queue), dtype=PLACE_SEGMENT)
+        for i, (index, row, stride, count, form, source) in enumerate(self.queue):
+            if isinstance(source, tuple):
+                _, ptr, width = base[source[0]]
+                src = ptr + source[1] * width
+            else:
+                src = source.data_ptr()
+            segs[i] = (self.columns[index].data_ptr(), src, row, stride, count, form, 0)
+        nbytes = D.L.h2_cells_place_scratch_bytes(len(segs))
+        scratch = D.scratch(nbytes)
+        if self.timed:                             # tools/synthesis_bench.py: the launch (with its segment table's copy) by events
+            begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            begin.record(D.tstream)
+        check(D.L.h2_dev_cells_place(segs.ctypes.data, len(segs), self.n, self.out_form, scratch.data_ptr(), nbytes,
+                                     D.stream), "h2_dev_cells_place")
+        if self.timed:
+            end.record(D.tstream)
+            end.synchronize()
+            self.kernel_ms += begin.elapsed_time(end)
+        self.cells_placed += int(segs["count"].sum())
+        self.flushes += 1
+        for staged, _, _ in base.values():
+            staged.record_stream(D.tstream)
+        self.queue, self.boxes, self.keep = [], {}, []
+
+    def finish(self):
+        self.flush()
+        if self.arenas is not None:
+            self.pack_seconds = sum(arena.pack_seconds for arena in self.arenas.values())
+            self.D.__dict__.setdefault("_place_arenas", []).append(self.arenas)
+            self.arenas = None
+        return self.columns
+
+
+# -- the constraint-system side of an assignment pass -------------------------------------------------------------------------
+class _Assembly:
+    """What the layouters assign into (the reference's `Assignment`): keygen keeps fixed cells, copies and constants and drops
+    advice values (keygen.rs:100-215); the witness pass keeps advice and drops the rest (prover.rs:85-162)."""
+
+    def __init__(self, cs, k, keygen, columns, instances=None):
+        self.cs, self.k, self.n, self.keygen, self.columns, self.instances = cs, k, 1 << k, keygen, columns, instances
+        self.usable = self.n - (cs.blinding_factors() + 1)
+        self.copies, self.first_unassigned = [], {}
+        self.positions = {column: i for i, column in enumerate(cs.perm_columns)}
+
+    def _check(self, column, row, last):
+        kind, index = column
+        if index >= {"advice": self.cs.num_advice, "fixed": self.cs.num_fixed, "instance": self.cs.num_instance}[kind]:
+            raise BoundsFailure("no column %s[%d]" % column)
+        if row < 0 or last >= self.usable:
+            raise NotEnoughRowsAvailable(self.k)
+
+    def assign(self, column, row, stride, vals):
+        if vals.count == 0:
+            return
+        last = row + (vals.count - 1) * stride
+        self._check(column, row, last)
+        if column[0] == "advice":
+            self.first_unassigned[column[1]] = max(self.first_unassigned.get(column[1], 0), last + 1)
+        if self.keygen != (column[0] == "fixed"):
+            return
+        if vals.kind == "none":
+            raise SynthesisError("no value for %s[%d]" % column)
+        self.columns.place(column[1], row, stride, vals)
+
+    def fill_from_row(self, column, row, value):
+        if row >= self.usable:                       # keygen.rs:206
+            raise NotEnoughRowsAvailable(self.k)
+        if self.keygen:
+            self.columns.place(column[1], row, 1, _Values(value, self.usable - row))
+
+    def copy(self, left, lrows, right, rrows):
+        if not self.keygen:
+            return
+        for column, rows in ((left, lrows), (right, rrows)):
+            if len(rows):
+                self._check(column, int(rows.min()), int(rows.max()))
+        if not len(lrows):
+            return
+        pos = []
+        for column in (left, right):
+            if column not in self.positions:
+                raise ColumnNotInPermutation(column)
+            pos.append(np.full(len(lrows), self.positions[column], dtype=np.int64))
+        self.copies.append(np.stack([pos[0], lrows, pos[1], rrows], axis=1))
+
+    def query_instance(self, column, row):
+        if row >= self.usable:
+            raise NotEnoughRowsAvailable(self.k)
+        if self.keygen or self.instances is None:
+            return None
+        vals = self.instances[column[1]]
+        return int(vals[row]) % R_MOD if row < len(vals) else 0
+
+    def copies_array(self):
+        return np.concatenate(self.copies) if self.copies else np.zeros((0, 4), dtype=np.int64)
+
+
+# -- what a circuit's `synthesize` sees ---------------------------------------------------------------------------------------
+class Circuit:
+    """plonk/circuit.rs:476-500.  `planner` is the reference's associated type FloorPlanner."""
+    planner = None
+
+    def configure(self, cs):
+        raise NotImplementedError
+
+    def synthesize(self, config, layouter):
+        raise NotImplementedError
+
+    def without_witnesses(self):
+        raise NotImplementedError
+
+
+class Region:
+    """One region of an assignment pass.  Offsets are relative to the region's start (absolute rows under FlatFloorPlanner)."""
+
+    def __init__(self, assembly, start, constants, shape=None):
+        self._asm, self._start, self._constants, self._shape = assembly, start, constants, shape
+
+    def _assign(self, kind, column, offset, values, stride, count):
+        if column[0] != kind:
+            raise TypeError("%s is not a %s column" % (column, kind))
+        if stride < 1 or offset < 0:
+            raise ValueError("offset >= 0 and stride >= 1")
+        vals = _Values(values, count)
+        if self._shape is not None:                  # V1's measurement pass (v1.rs:240-300): columns and height only
+            self._shape.columns.add(column)
+            if vals.count:
+                self._shape.row_count = max(self._shape.row_count, offset + (vals.count - 1) * stride + 1)
+        else:
+            self._asm.assign(column, self._start + offset, stride, vals)
+        return AssignedCells(column, self._start + offset, vals.count, stride)
+
+    def assign_advice(self, column, offset, values, stride=1, count=None):
+        """`values` to the cells offset, offset + stride, ... of an advice column; an integer with `count`: that value in
+        `count` cells; None (keygen): `count` cells without a value"""
+        return self._assign("advice", column, offset, values, stride, count)
+
+    def assign_fixed(self, column, offset, values, stride=1, count=None):
+        return self._assign("fixed", column, offset, values, stride, count)
+
+    def assign_advice_from_constant(self, column, offset, constant):
+        cells = self.assign_advice(column, offset, int(constant))
+        self.constrain_constant(cells, constant)
+        return cells
+
+    def assign_advice_from_instance(self, instance_column, row, advice_column, offset):
+        """-> (cell, value): the advice cell takes the instance's value and is tied to it (flat.rs:398-416)"""
+        if self._shape is not None:
+            return self.assign_advice(advice_column, offset, None), None
+        value = self._asm.query_instance(instance_column, row)
+        if value is None and not self._asm.keygen:
+            raise SynthesisError("no instance values were given")
+        cell = self.assign_advice(advice_column, offset, value)
+        self._asm.copy(cell.column, cell.rows(), instance_column, np.array([row], dtype=np.int64))
+        return cell, value
+
+    def constrain_constant(self, cells, constant):
+        if self._shape is None and self._asm.keygen:
+            self._constants.extend((int(constant) % R_MOD, cells.column, int(r)) for r in cells.rows())
+
+    def constrain_equal(self, left, right):
+        """`count` copy constraints between two ranges of equal length"""
+        if len(left) != len(right):
+            raise ValueError("constrain_equal: %d cells against %d" % (len(left), len(right)))
+        if self._shape is None:
+            self._asm.copy(left.column, left.rows(), right.column, right.rows())
+
+
+class Table:
+    """SimpleTableLayouter (single_pass.rs:56-110): the cells of a lookup table's columns, assigned from row 0"""
+
+    def __init__(self, assembly, used):
+        self._asm, self._used, self.columns = assembly, used, {}            # column -> [default, [(offset, count)]]
+
+    def assign_cell(self, column, offset, values, count=None):
+        if column[0] != "fixed":
+            raise TypeError("%s is not a table column" % (column,))
+        if column in self._used:
+            raise SynthesisError("fixed[%d] already belongs to another table" % column[1])
+        vals = _Values(values, count)
+        if vals.count == 0:
+            return
+        entry = self.columns.setdefault(column, [None, []])
+        if offset == 0:
+            if entry[0] is not None:
+                raise SynthesisError("row 0 of table column fixed[%d] assigned twice" % column[1])
+            entry[0] = vals.first() if self._asm.keygen else 0
+        entry[1].append((offset, vals.count))
+        self._asm.assign(column, offset, 1, vals)
+
+    def finish(self):
+        """flat.rs:198-231: every column assigned from row 0 without holes and to one length; the rest takes the default"""
+        lengths = set()
+        for column, (default, spans) in self.columns.items():
+            end = 0
+            for offset, count in sorted(spans):
+                if offset > end:
+                    raise SynthesisError("table column fixed[%d] has unassigned rows below %d" % (column[1], offset))
+                end = max(end, offset + count)
+            if default is None:
+                raise SynthesisError("table column fixed[%d] has no row 0" % column[1])
+            lengths.add(end)
+        if len(lengths) != 1:
+            raise SynthesisError("the columns of a table differ in length" if lengths else "an empty table")
+        first_unused = lengths.pop()
+        self._used.update(self.columns)
+        for column, (default, _) in self.columns.items():
+            self._asm.fill_from_row(column, first_unused, default)
+
+
+class _Shape:
+    def __init__(self, index):
+        self.index, self.columns, self.row_count = index, set(), 0
+
+
+class Layouter:
+    """One pass over a circuit's `synthesize`.  `starts`: the rows V1 gave the regions (None: every region starts at row 0,
+    FlatFloorPlanner); `shapes`: a list that makes this V1's measurement pass."""
+
+    def __init__(self, assembly, starts=None, shapes=None):
+        self._asm, self._starts, self._shapes = assembly, starts, shapes
+        self._regions, self._tables, self.constants = 0, set(), []
+
+    def assign_region(self, name, fn):
+        index = self._regions
+        self._regions += 1
+        if self._shapes is not None:
+            self._shapes.append(_Shape(index))
+            return fn(Region(self._asm, 0, self.constants, self._shapes[-1]))
+        return fn(Region(self._asm, 0 if self._starts is None else self._starts[index], self.constants))
+
+    def assign_table(self, name, fn):
+        if self._shapes is not None:                  # v1.rs:209: tables take no part in the measurement
+            return
+        table = Table(self._asm, self._tables)
+        fn(table)
+        table.finish()
+
+    def constrain_instance(self, cells, instance_column, row):
+        if self._shapes is None:
+            self._asm.copy(cells.column, cells.rows(), instance_column, row + np.arange(len(cells), dtype=np.int64))
+
+    def namespace(self, name):
+        return self
+
+
+# -- floor planners ------------------------------------------------------------------------------------------------------------
+def _column_key(column):
+    return (_COLUMN_ORDER[column[0]], column[1])
+
+
+def _sorted_constants(constants):
+    """by the (column, row) of the advice cell (flat.rs:52-58, v1.rs:134-140); stable, as the reference's sort_by"""
+    return sorted(constants, key=lambda c: (_column_key(c[1]), c[2]))
+
+
+def _assign_constants(assembly, constants, positions):
+    for (column, row), (value, cell_column, cell_row) in zip(positions, constants):
+        assembly.assign(column, row, 1, _Values(value, None))
+        assembly.copy(column, np.array([row], dtype=np.int64), cell_column, np.array([cell_row], dtype=np.int64))
+
+
+class FlatFloorPlanner:
+    """flat.rs: offsets are absolute rows.  Keygen: the constants go to rows 0, 1, ... of the FIRST constants column, in the
+    order of their advice cells, one copy each.  Proving: fixed cells and copies are dropped by the assembly."""
+
+    @staticmethod
+    def synthesize(assembly, circuit, config):
+        layouter = Layouter(assembly)
+        circuit.synthesize(config, layouter)
+        if assembly.keygen:
+            constants = _sorted_constants(layouter.constants)
+            columns = assembly.cs.constants
+            if constants and not columns:
+                raise NotEnoughColumnsForConstants("the circuit constrains constants and has no constants column")
+            _assign_constants(assembly, constants, [(columns[0], row) for row in range(len(constants))] if constants else [])
+        return layouter
+
+
+def free_intervals(allocations, start, end):
+    """Allocations::free_intervals (v1/strategy.rs:64-98): the unallocated intervals [a, b) that meet [start, end); b = None
+    is the unbounded one.  `allocations`: {start row: length}."""
+    row = start
+    for s in sorted(allocations):
+        if end is not None and s >= end:
+            continue
+        if row < s:
+            yield row, s
+        row = max(row, s + allocations[s])
+    if end is None or row < end:
+        yield row, end
+
+
+def first_fit_region(column_allocations, columns, length, start, slack):
+    """v1/strategy.rs:107-161"""
+    if not columns:
+        return start
+    c, rest = columns[0], columns[1:]
+    end = None if slack is None else start + length + slack
+    for lo, hi in list(free_intervals(column_allocations.setdefault(c, {}), start, end)):
+        s_slack = None if hi is None else (hi - lo) - length
+        if s_slack is None or s_slack >= 0:
+            row = first_fit_region(column_allocations, rest, length, lo, s_slack)
+            if row is not None:
+                column_allocations[c].setdefault(row, length)        # a BTreeSet ordered by start: an equal start is kept
+                return row
+    return None
+
+
+def slot_in_biggest_advice_first(shapes):
+    """v1/strategy.rs:198-225 -> (start row per region, {column: allocations}).  The reference sorts with
+    sort_unstable_by_key and reverses, which leaves the order of equal areas open; here: a STABLE ascending sort, then the
+    reverse -- among equal areas the region declared LAST is placed first."""
+    area = lambda sh: sum(1 for c in sh.columns if c[0] == "advice") * sh.row_count   # noqa: E731
+    order = sorted(shapes, key=area)[::-1]
+    allocations, starts = {}, {}
+    for sh in order:
+        starts[sh.index] = first_fit_region(allocations, sorted(sh.columns, key=_column_key), sh.row_count, 0, None)
+    return [starts[i] for i in range(len(shapes))], allocations
+
+
+class V1:
+    """v1.rs:65-161: a measurement pass over `without_witnesses()`, slot_in_biggest_advice_first, the assignment pass, then
+    the constants into the free cells of the constants columns below the first unassigned row."""
+
+    @staticmethod
+    def plan(circuit, config):
+        shapes = []
+        circuit.without_witnesses().synthesize(config, Layouter(None, shapes=shapes))
+        return slot_in_biggest_advice_first(shapes)
+
+    @staticmethod
+    def synthesize(assembly, circuit, config):
+        starts, allocations = V1.plan(circuit, config)
+        first_unassigned_row = max([max(s + l for s, l in a.items()) for a in allocations.values() if a] + [0])
+        layouter = Layouter(assembly, starts=starts)
+        circuit.synthesize(config, layouter)
+        if assembly.keygen:
+            positions = [(c, row) for c in assembly.cs.constants
+                         for lo, hi in free_intervals(allocations.get(c, {}), 0, first_unassigned_row) for row in range(lo, hi)]
+            if len(positions) < len(layouter.constants):
+                raise NotEnoughColumnsForConstants("%d constants, %d free cells in the constants columns"
+                                                   % (len(layouter.constants), len(positions)))
+            _assign_constants(assembly, _sorted_constants(layouter.constants), positions)
+        return layouter
+
+
+# -- entry points ----------------------------------------------------------------------------------------------------------------
+def _planner(circuit, planner):
+    return planner or circuit.planner or V1
+
+
+def synthesize_keygen(device, circuit, k, planner=None, resident=False, montgomery=False):
+    """configure + the keygen pass of `circuit` (keygen.rs:236-300) -> (cs, fixed, copies), as `keygen` takes them.
+    `planner`: the circuit's own (`Circuit.planner`), V1 when it names none.  `resident`: the fixed columns are built on
+    `device` (DeviceColumns) and returned as device tensors -- canonical, or with `montgomery` as the residues
+    `keygen(..., fixed_montgomery=True)` takes as they are; otherwise numpy columns (`device` may be None)."""
+    cs = ConstraintSystem(type(circuit).__name__)
+    config = circuit.configure(cs)
+    cs.chunk_lookups()
+    cs.chunk_shuffles()
+    n = 1 << k
+    if n < cs.minimum_rows():
+        raise NotEnoughRowsAvailable(k)
+    columns = DeviceColumns(device, cs.num_fixed, n, montgomery) if resident else HostColumns(cs.num_fixed, n)
+    assembly = _Assembly(cs, k, True, columns)
+    _planner(circuit, planner).synthesize(assembly, circuit.without_witnesses(), config)
+    return cs, columns.finish(), assembly.copies_array()
+
+
+def synthesize_witness(device, circuit, cs_or_pk, k, planner=None, resident=True, instances=None, alloc=None, stats=None):
+    """the witness pass of `circuit` (prover.rs:85-204) -> (advice, first_unassigned), as create_proof_ext / check_witness
+    take them: `advice` resident canonical columns (`resident`, DeviceColumns) or numpy ones (`alloc(count, n)` supplies
+    them, e.g. Device.pinned_columns); first_unassigned = {advice column: 1 + its last assigned row}, the record the
+    range-check completion asks for.  `cs_or_pk`: the constraint system of synthesize_keygen, or the proving key made of it.
+    `instances`: the instance columns' values, for assign_advice_from_instance.  `stats`: a dict that receives the device
+    assembly's counters and times (cells placed, launches, seconds spent staging values and flushing, the launches' milliseconds by
+    events -- which makes every flush wait for its launch)."""
+    cs = getattr(cs_or_pk, "cs", cs_or_pk)
+    probe = ConstraintSystem(cs.name)
+    config = circuit.configure(probe)               # configure is deterministic: the same columns as at keygen
+    if (probe.num_advice, probe.num_fixed, probe.num_instance) != (cs.num_advice, cs.num_fixed, cs.num_instance):
+        raise ValueError("the circuit does not configure the constraint system it is proved under")
+    n = 1 << k
+    columns = DeviceColumns(device, cs.num_advice, n, timed=stats is not None) if resident else HostColumns(cs.num_advice, n, alloc)
+    assembly = _Assembly(cs, k, False, columns, instances)
+    _planner(circuit, planner).synthesize(assembly, circuit, config)
+    advice = columns.finish()
+    if stats is not None and resident:
+        stats.update(cells_placed=columns.cells_placed, flushes=columns.flushes, pack_seconds=columns.pack_seconds,
+                     flush_seconds=columns.flush_seconds, kernel_ms=columns.kernel_ms)
+    return advice, dict(assembly.first_unassigned)
+
+
+def region_starts(circuit, planner=None):
+    """the first row of every region of `circuit`, in the order `synthesize` declares them"""
+    cs = ConstraintSystem("plan")
+    config = circuit.configure(cs)
+    if _planner(circuit, planner) is FlatFloorPlanner:
+        shapes = []
+        circuit.without_witnesses().synthesize(config, Layouter(None, shapes=shapes))
+        return [0] * len(shapes)
+    return V1.plan(circuit, config)[0]

@@ -339,6 +339,34 @@ int h2_dev_range_check_complete(void *const *d_origins, void *const *d_companion
                                 const uint64_t *step, const uint64_t *first_unassigned, size_t pairs, size_t usable_rows,
                                 size_t n, void *d_status, void *d_scratch, size_t scratch_bytes, void *stream);
 
+/* The circuit front end's device assembly (synthesis.py): `count` segments of assigned cells placed into resident columns of
+ * n rows (n x 4 u64 each) by ONE launch whose work is split by cells, not by segments.  Segment i writes cell j < count of
+ * its source to row first_row + j * stride of the column dst.  A source is read in the segment's form:
+ *   CANONICAL  count cells of 4 u64, the integers (below the modulus)      COMPACT  count u64 values
+ *   BROADCAST  ONE canonical cell, written to every row of the segment
+ * and the whole batch is written in out_form: CANONICAL (a witness, as the prover takes it) or MONTGOMERY (as
+ * h2_dev_batch_mont leaves a canonical column: keygen's fixed columns).  `segments` is a HOST array, read before the call
+ * returns; dst and src are device pointers (sources may be anywhere on the device: staged values or tensors computed there).
+ * No two segments of a call may write the same cell (which one wins is undefined: a caller that wants "the later
+ * assignment wins" places the earlier one by an earlier call).  Segments with count 0 are skipped.
+ * d_scratch: h2_cells_place_scratch_bytes(count) bytes, 16-byte aligned.  Asynchronous on `stream`.  Returns H2_ERR_INVALID
+ * without touching a device, h2_last_error naming the reason, for a null or misaligned pointer, an unknown form, stride 0, a
+ * segment whose last row is not below n, or too small a scratch. */
+enum { H2_PLACE_FORM_CANONICAL = 0, H2_PLACE_FORM_COMPACT = 1, H2_PLACE_FORM_BROADCAST = 2 };
+enum { H2_PLACE_OUT_CANONICAL = 0, H2_PLACE_OUT_MONTGOMERY = 1 };
+typedef struct {
+    void *dst;
+    const void *src;
+    uint64_t first_row;
+    uint64_t stride;
+    uint64_t count;
+    uint32_t form;
+    uint32_t reserved;
+} h2_place_segment;
+size_t h2_cells_place_scratch_bytes(size_t count);
+int h2_dev_cells_place(const h2_place_segment *segments, size_t count, size_t n, uint32_t out_form, void *d_scratch,
+                       size_t scratch_bytes, void *stream);
+
 /* Rational cells (`Assigned<F>`, plonk/assigned.rs) resolved to field elements, as poly::batch_invert_assigned
  * (poly.rs:148-173) does for keygen's fixed columns and the fork's assign_advice cell by cell (plonk/prover.rs:1607-1612):
  * for each of `cols` columns of n rows, out[r] = num[r] / den[r], and 0 where den[r] = 0 (`Assigned::evaluate`).  All
