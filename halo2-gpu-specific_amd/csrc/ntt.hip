@@ -81,9 +81,8 @@ static uint32_t pass_zskip(uint32_t L, const NttPass& ps, uint32_t in_len) {
 
 static NttKernel pass_kernel(const NttPass& ps, uint32_t zskip) {
     if (!ps.shape.radix4) return NK_R2;
-    const bool dp = !ps.last;  // pairs in tw_direct: the middle passes' tables (a first pass has none)
-    if (ps.shape.fixed && zskip == 0) return dp ? NK_PASS8_DP : NK_PASS8;
-    return dp ? NK_R4_DP : NK_R4;
+    if (ps.shape.fixed && zskip == 0) return ps.last ? NK_PASS8 : NK_PASS8_DP;
+    return ps.last ? NK_R4 : NK_R4_DP;
 }
 
 // The plan of a transform as the launcher will run it (h2_ntt_shape): per pass 7 words -- bits, log_c, threads, radix4,
@@ -333,7 +332,7 @@ NttTablePin ntt_scale_table(NttPlan* pl, const Fr& g, const Fr* d, hipStream_t s
 // ---------------------------------------------------------------- plans
 static void free_plan(NttPlan* pl) {
     if (pl->tables) (void)hipFree(pl->tables);
-    for (const Fr* t : pl->tw_direct)
+    for (const Fr* t : pl->tw_inter)
         if (t) (void)hipFree(const_cast<Fr*>(t));
     for (NttTableMap* map : {&pl->scaled_hi, &pl->scale_tabs, &pl->last_direct})
         for (auto& kv : *map) (void)hipFree(kv.second.ptr);
@@ -429,17 +428,19 @@ PlanRef ntt_get_plan(DeviceCtx* ctx, uint32_t log_n, const uint64_t omega[4], hi
         if (ps.shape.fixed) ntt_fill_pow(next, w, n >> ps.B, half, 2u, stream);
         pl->tw_chunk.push_back(ps.shape.fixed ? next : nullptr);
         next += chunk_entries(ps);
-        // passes whose whole inter-pass twiddle set has <= 2^16 entries get it tabulated (2 MiB, L2-resident):
-        // the pass then spends one multiplication per element on twiddles instead of two
-        Fr* direct = nullptr;
+        // A middle pass whose whole inter-pass twiddle set has <= 2^16 entries (pass 1 of every plan of three passes or more:
+        // t_log is the first pass's width) gets it tabulated, as chunk entries in the order (rho << t_log) | K.  The pass
+        // BEFORE it multiplies by them where it stores (pass_args: nx_tab / tw_applied): there a tile reads consecutive
+        // entries -- 32 KiB per tile of the fixed geometry, about 0.5 MiB hot per L2 of the 8 MiB a 2^16-entry table takes.
+        Fr* tab = nullptr;
         if (ps.t_log != 0 && !ps.last && ps.B + ps.t_log <= 16) {
             const uint32_t cnt = 1u << (ps.B + ps.t_log);
-            const size_t bytes = (size_t)cnt * sizeof(Fr) * (form ? 2 : 1);
-            H2_HIP(hipMalloc(&direct, bytes));
+            const size_t bytes = (size_t)cnt * sizeof(TwChunk);
+            H2_HIP(hipMalloc(&tab, bytes));
             pl->table_bytes += bytes;
         }
-        pl->tw_direct.push_back(direct);
-        if (direct) ntt_fill_direct(direct, w, ps.t_log, ps.s_log, log_n, 1u << (ps.B + ps.t_log), form, stream);
+        pl->tw_inter.push_back(tab);
+        if (tab) ntt_fill_direct(tab, w, ps.t_log, ps.s_log, log_n, 1u << (ps.B + ps.t_log), 2u, stream);
     }
     H2_HIP(hipGetLastError());
     // the tables are complete before the plan is published: a second caller on another stream (h2_dev_* on a different
@@ -492,7 +493,14 @@ static PassArgs pass_args(const NttPlan* pl, size_t p, const Fr* const* srcs, Fr
     a.tw_chunk = pl->tw_chunk[p];
     a.tw_lo = pl->tw_lo;
     a.tw_hi = pl->tw_hi;
-    a.tw_direct = pl->tw_direct[p];
+    a.tw_applied = pl->tw_inter[p] != nullptr;
+    if (!ps.last && pl->tw_inter[p + 1]) {
+        const NttPass& nx = pl->sched[p + 1];
+        a.nx_tab = pl->tw_inter[p + 1];
+        a.nx_s_log = nx.s_log;
+        a.nx_B = nx.B;
+        a.nx_t_log = nx.t_log;
+    }
     set_scale3(a, first ? pre3 : nullptr, ps.last ? post3 : nullptr);
     a.log_n = pl->log_n;
     a.B = ps.B;
@@ -531,10 +539,7 @@ static void ntt_run_chunk(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr
                 a.hi_scaled = 1;
             }
             last_tab = last_table(ctx, pl, ps.B, a.hi_scaled ? &post3[0] : nullptr, stream);
-            if (last_tab.get()) {
-                a.tw_direct = last_tab.get();
-                a.direct_kmajor = 1;
-            }
+            a.tw_direct = last_tab.get();
         }
         ntt_pass_launch(ctx->device, pass_kernel(ps, a.zskip), a, cnt, ps.shape.threads, stream);
     }

@@ -58,11 +58,13 @@ struct NttPlan {
     const Fr* tw_lo = nullptr;         // w^i,        i < min(n, 4096)
     const Fr* tw_hi = nullptr;         // w^(i<<12),  i < n >> 12
     // per pass: (w^(n/R))^e, e < R/2 -- as (plain value, floor(value 2^256 / r)) PAIRS, the operands of the constant-operand
-    // product fp_mul_const, for the passes with shape.radix4 (transforms >= 2^18), which read tw_direct as pairs too
+    // product fp_mul_const, for the passes with shape.radix4 (transforms >= 2^18)
     std::vector<const Fr*> tw_bfly;
     std::vector<const Fr*> tw_chunk;   // per pass of the fixed geometry: tw_bfly's values as chunk tables (fp_mul_chunk), else nullptr
-    std::vector<const Fr*> tw_direct;  // per pass: full inter-pass twiddle table or nullptr
-    size_t table_bytes = 0;            // of `tables` and the per-pass direct tables
+    // per pass: its full inter-pass twiddle set as chunk tables, w^(rho K S) at [(rho << t_log) | K] (the middle pass of a plan
+    // of three passes or more), else nullptr.  The pass BEFORE it multiplies by them at its store (PassArgs::nx_tab).
+    std::vector<const Fr*> tw_inter;
+    size_t table_bytes = 0;            // of `tables` and the per-pass tw_inter tables
     NttTableMap scaled_hi;   // divisor -> tw_hi * divisor (iNTT: 1/n folded into the last pass); kept for the plan's life
     // (generator, divisor) -> two-level table of g^i (coset transforms): 4096 + n/4096 entries.  At most SCALE_TABS_MAX per
     // plan: the public coset entry points take any generator, so the least recently used table nobody holds is dropped

@@ -22,6 +22,8 @@
 //   * zero padding  (eval_fft_prepare, evaluation_gpu.rs:890-900; domain.rs:280)
 //   * zeta-power coset pre-scale (distribute_powers_zeta, domain.rs:382-398)
 //   * 1/n and zeta^-1 post-scale (domain.rs:404-409, :341)
+#include <stdexcept>
+
 #include "ntt_pass.hpp"
 
 namespace h2 {
@@ -135,17 +137,35 @@ __device__ __forceinline__ void lds_put(uint4* lo, uint4* hi, uint32_t i, const 
 
 // Every pass works in the lazy domain of field.hpp -- values below 4p in LDS and between the passes, products by fp_mul_wide
 // (no final subtraction), bare additions; canonical residues come back at the last pass's store.
-// CW (the radix-4 passes): the twiddles this pass reads from tables -- the butterfly twiddles in LDS and the tabulated
-// inter-pass twiddles (tw_direct) -- are (plain value, quotient) pairs and multiply by fp_mul_const: 115 multiply-adds per
-// product instead of 136 (field.hpp).  Twiddles COMPOSED at run time (lo x hi of the two-level tables, the coset scales,
-// pre3 / post3) stay Montgomery products.
-// DP: tw_direct holds pairs too (the 2^16-entry table of a middle pass: 4 MiB, read out of L2).  The LAST pass's complete table
-// stays in Montgomery form whatever CW says: as pairs it is 64 B per element streamed from HBM next to the 64 B of data, and the
-// pass -- 2.1 GB per launch at 2^24 -- stopped following its instruction count (590 us either way, profiles/r6_ntt_constw.txt).
-template <bool RADIX4, bool DP = false>
+// CW (the radix-4 passes): the butterfly twiddles in LDS are (plain value, quotient) pairs and multiply by fp_mul_const: 115
+// multiply-adds per product instead of 136 (field.hpp).  Twiddles COMPOSED at run time (lo x hi of the two-level tables, the
+// coset scales, pre3 / post3) stay Montgomery products, and so does the LAST pass's complete table (tw_direct): as pairs it is
+// 64 B per element streamed from HBM next to the 64 B of data, and the pass -- 2.1 GB per launch at 2^24 -- stopped following
+// its instruction count (590 us either way, profiles/r6_ntt_constw.txt).
+// NLAST: a pass before the last, known when the kernel is compiled (the last pass's table, scales and scatter are not in it).
+// ST: the pass after this one has its inter-pass twiddles tabulated (PassArgs::nx_tab) and this pass multiplies by them where
+// it stores, so that pass loads finished operands (tw_applied).  The product is the same wherever it runs; a first pass waits
+// for rows 2 MiB apart and has issue slots to spare, the middle pass is bound by issue (measured).  At the store
+// the entries a tile needs are consecutive in the table's own order, which is what makes the chunk form (128 B per entry)
+// affordable: store_twiddle below.
+__device__ __forceinline__ Fr store_twiddle(const PassArgs& a, const Fr& y, const uint32_t entry) {
+    const uint4* const q = reinterpret_cast<const uint4*>(a.nx_tab) + (size_t)entry * TW_CHUNK_Q;
+    TwChunk t;
+#pragma unroll
+    for (uint32_t k = 0; k < TW_CHUNK_Q; k++) {
+        const uint4 v = q[k];
+        t.w[4 * k] = v.x; t.w[4 * k + 1] = v.y; t.w[4 * k + 2] = v.z; t.w[4 * k + 3] = v.w;
+    }
+    // any 256-bit y (a pass hands on values below 4p) -> below p (1 + 2^-29) < 2p: what the next pass's first butterflies
+    // take as they are (fp_lazy_red2p of a value below 4p)
+    return fp_mul_chunk(y, t);
+}
+
+template <bool RADIX4, bool NLAST = false, bool ST = false>
 __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
     constexpr bool CW = RADIX4;
-    static_assert(!DP || CW, "pairs in tw_direct only next to pairs in tw_bfly");
+    static_assert(!ST || NLAST || !RADIX4, "a last pass stores the transform's output");
+    const bool is_last = NLAST ? false : a.is_last != 0;
     // x * w for a canonical twiddle w: any x < 2^256 -> a value below 2p
     auto tmul = [](const Fr& x, const Fr& w) -> Fr { return fp_mul_wide(x, w); };
     const uint32_t B = a.B, R = 1u << B, log_c = a.log_c, C = 1u << log_c;
@@ -192,7 +212,7 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
     // ---- tile geometry
     uint32_t base = 0, K_uniform = 0;
     const uint32_t S = 1u << a.s_log;
-    if (!a.is_last) {
+    if (!is_last) {
         // tiles: for each hi, for each chunk of C consecutive low positions
         uint32_t chunks_per_hi = S >> log_c;
         uint32_t hi = tile_id / chunks_per_hi, lo0 = (tile_id % chunks_per_hi) << log_c;
@@ -212,7 +232,7 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
 #pragma unroll
         for (uint32_t q = 0; q < NE; q++) {
             const uint32_t e = e0 + q * nthreads;
-            if (!a.is_last) {
+            if (!is_last) {
                 col[q] = e & (C - 1);
                 rho[q] = (e >> log_c) & (R - 1);
                 idx[q] = base + (rho[q] << a.s_log) + col[q];
@@ -244,27 +264,17 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
             }
         }
         const bool pre_scale = a.scale_mode == 1u && a.nprev == 0;
-        if (a.nprev != 0 || pre_scale) {
+        if ((a.nprev != 0 && !a.tw_applied) || pre_scale) {
             // omega^(rho * S * K); a unit twiddle (rho = 0 or K = 0) multiplies like any other: the tables hold it
-            if (a.tw_direct != nullptr && !pre_scale) {
+            // (tw_applied: the pass before this one multiplied by it at its store)
+            if (!NLAST && a.tw_direct != nullptr && !pre_scale) {   // (the last pass's table)
 #pragma unroll
                 for (uint32_t q0 = 0; q0 < NE; q0 += 2) {
-                    if constexpr (DP) {
-                        // (plain value, quotient) pairs, one at a time: two pairs in flight next to the four elements spilled
+                    Fr w[2];
 #pragma unroll
-                        for (uint32_t q = q0; q < q0 + 2; q++) {
-                            const size_t at = a.direct_kmajor ? ((Kk[q] << B) | rho[q]) : ((rho[q] << a.t_log) | Kk[q]);
-                            const Fr w = fp_load(a.tw_direct + 2 * at), wq = fp_load(a.tw_direct + 2 * at + 1);
-                            x[q] = fp_mul_const(x[q], w, wq);
-                        }
-                    } else {
-                        Fr w[2];
+                    for (uint32_t q = 0; q < 2; q++) w[q] = fp_load(a.tw_direct + ((Kk[q0 + q] << B) | rho[q0 + q]));
 #pragma unroll
-                        for (uint32_t q = 0; q < 2; q++)
-                            w[q] = fp_load(a.tw_direct + (a.direct_kmajor ? ((Kk[q0 + q] << B) | rho[q0 + q]) : ((rho[q0 + q] << a.t_log) | Kk[q0 + q])));
-#pragma unroll
-                        for (uint32_t q = 0; q < 2; q++) x[q0 + q] = tmul(x[q0 + q], w[q]);
-                    }
+                    for (uint32_t q = 0; q < 2; q++) x[q0 + q] = tmul(x[q0 + q], w[q]);
                 }
             } else if (a.log_n <= LO_BITS && !pre_scale) {
 #pragma unroll
@@ -296,8 +306,8 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
         for (uint32_t q = 0; q < NE; q++) {
             // (row and column again from e: cheaper than keeping them in registers across the products)
             const uint32_t e = e0 + q * nthreads;
-            const uint32_t r_q = a.is_last ? (e & (R - 1)) : ((e >> log_c) & (R - 1));
-            const uint32_t c_q = a.is_last ? ((e >> B) & (C - 1)) : (e & (C - 1));
+            const uint32_t r_q = is_last ? (e & (R - 1)) : ((e >> log_c) & (R - 1));
+            const uint32_t c_q = is_last ? ((e >> B) & (C - 1)) : (e & (C - 1));
             if (e >= total || (zskip && r_q >= (R >> zskip))) continue;
             if (zskip) {
                 for (uint32_t m = 0; m < (1u << zskip); m++) lds_put(t_lo, t_hi, ((bitrev(r_q, B) | m) << log_c) + c_q, x[q]);
@@ -400,13 +410,13 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
         for (uint32_t q = 0; q < NE; q++) {
             const uint32_t e = e0 + q * nthreads;
             const uint32_t c = e & (C - 1), k = (e >> log_c) & (R - 1);
-            if (!a.is_last)
+            if (!is_last)
                 idx[q] = base + (k << a.s_log) + c;
             else
                 idx[q] = ((tile_id << log_c) + c) + (k << a.t_log);
             y[q] = lds_get(t_lo, t_hi, (k << log_c) + c);
         }
-        if (a.is_last && a.scale_mode == 2u) {
+        if (is_last && a.scale_mode == 2u) {
             // one at a time: four results are live next to the two table halves and the product
 #pragma unroll
             for (uint32_t q = 0; q < NE; q++) {
@@ -414,7 +424,7 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
                 const Fr w = fp_mul(fp_load(a.sc_lo + (i & ((1u << LO_BITS) - 1))), fp_load(a.sc_hi + (i >> LO_BITS)));
                 y[q] = fp_reduce_once(fp_mul_wide(y[q], w));
             }
-        } else if (a.is_last && a.has_post3 && !a.hi_scaled) {
+        } else if (is_last && a.has_post3 && !a.hi_scaled) {
 #pragma unroll
             for (uint32_t q = 0; q < NE; q++) {
                 const uint32_t m = idx[q] % 3;
@@ -423,11 +433,22 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
                 for (int l = 0; l < 8; l++) w.l[l] = m == 0 ? a.post3[0].l[l] : (m == 1 ? a.post3[1].l[l] : a.post3[2].l[l]);
                 y[q] = fp_reduce_once(fp_mul_wide(y[q], w));
             }
-        } else if (a.is_last) {
+        } else if (is_last) {
             // the transform's output is canonical (an intermediate pass hands its values on below 4p: the next pass's
             // inter-pass twiddle product takes them as they are)
 #pragma unroll
             for (uint32_t q = 0; q < NE; q++) y[q] = fp_lazy_canon(y[q]);
+        }
+        if constexpr (ST) {
+            // the next pass's inter-pass twiddle, one at a time (an entry is 32 registers next to the four results): C may
+            // exceed that pass's stride, so its row rho' is taken per element
+#pragma unroll
+            for (uint32_t q = 0; q < NE; q++) {
+                const uint32_t e = e0 + q * nthreads;
+                const uint32_t rho_n = (idx[q] >> a.nx_s_log) & ((1u << a.nx_B) - 1);
+                const uint32_t K_n = K_uniform | (((e >> log_c) & (R - 1)) << a.t_log);
+                if (e < total) y[q] = store_twiddle(a, y[q], (rho_n << a.nx_t_log) | K_n);
+            }
         }
 #pragma unroll
         for (uint32_t q = 0; q < NE; q++)
@@ -437,8 +458,7 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
 
 // ---------------------------------------------------------------- the common pass, tile ends fused
 // The radix-4 pass at one fixed geometry (8 bits, 4 columns, 256 lanes, four elements per lane, nothing skipped; one tile
-// per workgroup, blockIdx.y the vector; the tabulated inter-pass twiddles as pairs, k_ntt_pass's CW, the butterfly twiddles as
-// chunk tables, see below) with the two ends of a tile taken out of LDS.
+// per workgroup, blockIdx.y the vector; the butterfly twiddles as chunk tables, see below) with the two ends of a tile taken out of LDS.
 // The four rows a lane loads are the inputs of ONE unit of the first stage pair, and the four rows a unit of the last stage
 // pair produces are the four a lane stores.  So the first pair runs on the loaded registers (after pre3, the coset pre-scale
 // and the inter-pass twiddle, as before) and writes its outputs to LDS, and the last pair's outputs go through the
@@ -462,8 +482,12 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
 static constexpr uint32_t PASS8_TW_LDS = 32;   // entries in LDS: indices 0, 4, 8 ..
 static constexpr uint32_t PASS8_LDS = ((256u << 2) * 2 + PASS8_TW_LDS * TW_CHUNK_Q) * sizeof(uint4);
 static_assert(4 * PASS8_LDS <= 160u * 1024, "four workgroups of k_ntt_pass8 per CU");
-template <bool DP>
+// NLAST, ST: k_ntt_pass's.  With ST the product runs on the four results a lane holds after the last stage pair, rows
+// (tid >> 2) + 64 q of a tile whose next-pass row rho' is uniform: entries (rho' << 8) | k of that table, 16 consecutive ones
+// (2 KiB) per wave and load, the same 256 (32 KiB) for the 64 consecutive tiles of one rho'.
+template <bool NLAST, bool ST = false>
 __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
+    static_assert(!ST || NLAST, "a last pass stores the transform's output");
     constexpr uint32_t B = 8, R = 1u << B, log_c = 2, C = 1u << log_c;
     auto tmul = [](const Fr& x, const Fr& w) -> Fr { return fp_mul_wide(x, w); };
     uint4* t_lo = h2_smem;                  // the planes of k_ntt_pass, at the same offsets
@@ -541,7 +565,7 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
         lds_put(t_lo, t_hi, i0 + 3 * step, x3);
         __syncthreads();
     };
-    const bool is_last = DP ? false : a.is_last != 0;   // (pairs in tw_direct: never the last pass)
+    const bool is_last = NLAST ? false : a.is_last != 0;
     const uint32_t n_mask = (a.log_n >= 32) ? 0xffffffffu : ((1u << a.log_n) - 1);
 
 #pragma unroll
@@ -600,25 +624,15 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
                 }
             }
             const bool pre_scale = a.scale_mode == 1u && a.nprev == 0;
-            if (a.nprev != 0 || pre_scale) {
-                if (a.tw_direct != nullptr && !pre_scale) {
+            if ((a.nprev != 0 && !a.tw_applied) || pre_scale) {
+                if (!NLAST && a.tw_direct != nullptr && !pre_scale) {   // (the last pass's table)
 #pragma unroll
                     for (uint32_t q0 = 0; q0 < NE; q0 += 2) {
-                        if constexpr (DP) {
+                        Fr w[2];
 #pragma unroll
-                            for (uint32_t q = q0; q < q0 + 2; q++) {
-                                const size_t at = a.direct_kmajor ? ((Kk[q] << B) | rho[q]) : ((rho[q] << a.t_log) | Kk[q]);
-                                const Fr w = fp_load(a.tw_direct + 2 * at), wq = fp_load(a.tw_direct + 2 * at + 1);
-                                x[q] = fp_mul_const(x[q], w, wq);
-                            }
-                        } else {
-                            Fr w[2];
+                        for (uint32_t q = 0; q < 2; q++) w[q] = fp_load(a.tw_direct + ((Kk[q0 + q] << B) | rho[q0 + q]));
 #pragma unroll
-                            for (uint32_t q = 0; q < 2; q++)
-                                w[q] = fp_load(a.tw_direct + (a.direct_kmajor ? ((Kk[q0 + q] << B) | rho[q0 + q]) : ((rho[q0 + q] << a.t_log) | Kk[q0 + q])));
-#pragma unroll
-                            for (uint32_t q = 0; q < 2; q++) x[q0 + q] = tmul(x[q0 + q], w[q]);
-                        }
+                        for (uint32_t q = 0; q < 2; q++) x[q0 + q] = tmul(x[q0 + q], w[q]);
                     }
                 } else if (a.log_n <= LO_BITS && !pre_scale) {
 #pragma unroll
@@ -696,6 +710,15 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
 #pragma unroll
             for (uint32_t q = 0; q < NE; q++) y[q] = fp_lazy_canon(y[q]);
         }
+        if constexpr (ST) {
+            // the next pass's inter-pass twiddle, one at a time; rho' from the tile's base: its 4 columns share it (nx_s_log >= 2)
+            const uint32_t rho_n = (base >> a.nx_s_log) & ((1u << a.nx_B) - 1);
+#pragma unroll
+            for (uint32_t q = 0; q < NE; q++) {
+                const uint32_t K_n = K_uniform | (((tid >> log_c) + q * (R / NE)) << a.t_log);
+                y[q] = store_twiddle(a, y[q], (rho_n << a.nx_t_log) | K_n);
+            }
+        }
 #pragma unroll
         for (uint32_t q = 0; q < NE; q++) fp_store(out_p + idx[q], y[q]);
     }
@@ -710,6 +733,10 @@ static const PassFn pass_fn[H2_NTT_KERNEL_COUNT] = {
     k_ntt_pass<true, false>,  // NK_R4
     k_ntt_pass<false>,        // NK_R2
 };
+// the same kernels with the next pass's twiddles at the store (ST: a.nx_tab), for the ids a pass before the last can have
+static const PassFn pass_fn_st[H2_NTT_KERNEL_COUNT] = {
+    k_ntt_pass8<true, true>, nullptr, k_ntt_pass<true, true, true>, nullptr, k_ntt_pass<false, false, true>,
+};
 
 void ntt_pass_launch(int device, NttKernel kernel, const PassArgs& a, uint32_t cnt, uint32_t threads, hipStream_t stream) {
     const uint32_t R = 1u << a.B, C = 1u << a.log_c;
@@ -719,13 +746,15 @@ void ntt_pass_launch(int device, NttKernel kernel, const PassArgs& a, uint32_t c
     if (lds > 64 * 1024) {  // beyond the default dynamic LDS limit: raise it once (never the 8-bit passes)
         static bool raised[64] = {};  // per device
         if (device < 0 || device >= 64 || !raised[device]) {
-            for (NttKernel k : {NK_R4_DP, NK_R4, NK_R2})
-                H2_HIP(hipFuncSetAttribute((const void*)pass_fn[k], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            for (const PassFn f : {pass_fn[NK_R4_DP], pass_fn[NK_R4], pass_fn[NK_R2], pass_fn_st[NK_R4_DP], pass_fn_st[NK_R2]})
+                H2_HIP(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             if (device >= 0 && device < 64) raised[device] = true;
         }
     }
     const bool pass8 = kernel == NK_PASS8_DP || kernel == NK_PASS8;
-    hipLaunchKernelGGL(pass_fn[kernel], dim3(ntiles, cnt), dim3(threads), pass8 ? (size_t)PASS8_LDS : lds, stream, a);
+    const PassFn fn = a.nx_tab ? pass_fn_st[kernel] : pass_fn[kernel];
+    if (!fn) throw std::runtime_error("ntt_pass_launch: a last pass has no next pass to multiply for");
+    hipLaunchKernelGGL(fn, dim3(ntiles, cnt), dim3(threads), pass8 ? (size_t)PASS8_LDS : lds, stream, a);
 }
 
 static dim3 fill_grid(uint32_t count) { return dim3((count + 255) / 256); }

@@ -15,12 +15,19 @@ static constexpr uint32_t TW_CHUNK_Q = sizeof(TwChunk) / sizeof(uint4);  // 16-b
 struct PassArgs {
     const Fr* in;
     Fr* out;
-    const Fr* tw_bfly;  // R/2 entries: (w^(n/R))^e   (CW kernels: R/2 PAIRS -- plain value, quotient -- like tw_direct; see tw_store)
+    const Fr* tw_bfly;  // R/2 entries: (w^(n/R))^e   (CW kernels: R/2 PAIRS -- plain value, quotient; see tw_store)
     const Fr* tw_chunk;  // k_ntt_pass8: the same R/2 values as chunk tables (tw_store's third form)
     const Fr* tw_lo;    // min(n, 4096) entries: w^i
     const Fr* tw_hi;    // n >> 12 entries: w^(i << 12)   (unused when n <= 4096)
-    const Fr* tw_direct;  // non-null: inter-pass twiddle = tw_direct[(rho << consumed) | K] (no generation multiply)
-    uint32_t direct_kmajor;  // ... = tw_direct[(K << B) | rho] instead (the last pass's table: read in load order)
+    const Fr* tw_direct;  // non-null (a last pass): inter-pass twiddle = tw_direct[(K << B) | rho], its load order (no generation multiply)
+    // The inter-pass twiddles of a tabulated middle pass (the plan's tw_inter) are applied where the pass BEFORE it stores:
+    // tw_applied (that middle pass): the elements it loads carry their twiddle already, its load multiplies by nothing;
+    // nx_tab (the pass before it): the next pass's table, chunk entries (tw_store's third form) at [(rho' << nx_t_log) | K'], and
+    // that pass's s_log / B / t_log -- the element stored at idx is the next pass's row rho' = (idx >> nx_s_log) & (2^nx_B - 1)
+    // and its K' is this pass's K | k << t_log
+    uint32_t tw_applied;
+    const Fr* nx_tab;
+    uint32_t nx_s_log, nx_B, nx_t_log;
     uint32_t hi_scaled;  // tw_hi already carries the uniform post-scale (1/n): never skip, no post multiply
     Fr pre3[3];         // has_pre3: x *= pre3[idx % 3] on the first-pass load (idx % 3 == 0 skipped)
     Fr post3[3];        // has_post3: y *= post3[idx % 3] on the final store
@@ -62,7 +69,8 @@ void ntt_pass_launch(int device, NttKernel kernel, const PassArgs& a, uint32_t c
 
 // Table fillers: one kernel each on `stream` (none for an empty table).  `form`: tw_store's `pair` (ntt_pass.hip).
 void ntt_fill_pow(Fr* out, const Fr& base, uint32_t mul, uint32_t count, uint32_t form, hipStream_t stream);  // out[i] = base^(i mul)
-// out[(rho << kbits) | K] = base^((rho K << s_log) mod n): the complete inter-pass twiddle set of a middle pass
+// out[(rho << kbits) | K] = base^((rho K << s_log) mod n): the complete inter-pass twiddle set of a middle pass (form 2:
+// sizeof(TwChunk) bytes per entry)
 void ntt_fill_direct(Fr* out, const Fr& base, uint32_t kbits, uint32_t s_log, uint32_t log_n, uint32_t count, uint32_t form,
                      hipStream_t stream);
 // out[(K << bits) | rho] = base^((rho K) mod n) (* d when given), 2^log_n Montgomery values (log_n >= 8): the last pass's, in load order
