@@ -77,6 +77,7 @@ SYMBOLS = {
     "h2_msm_scratch_bytes": (_sz, [_sz, _u32]),
     "h2_msm_batch_scratch_bytes": (_sz, [_sz, _u32, _sz]),
     "h2_msm_shape": (ctypes.c_int, [_sz, _u32, _vp, _vp, _vp]),
+    "h2_msm_last_launches": (_sz, [_vp, _sz]),
     "h2_ntt_shape": (ctypes.c_int, [_u32, _u32, _vp, _sz, _vp]),
     "h2_dev_msm": (ctypes.c_int, [_vp, _vp, _sz, _u32, _vp, _sz, _vp, _vp]),
     "h2_dev_msm_batch": (ctypes.c_int, [_vp, _sz, _vp, _sz, _u32, _vp, _sz, _vp, _vp]),

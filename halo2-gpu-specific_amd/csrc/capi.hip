@@ -838,6 +838,8 @@ int h2_msm_shape(size_t n, uint32_t max_bits, uint32_t* c, uint32_t* windows, ui
     return H2_OK;
 }
 
+size_t h2_msm_last_launches(h2_msm_launch_info* out, size_t cap) { return msm_last_launches(cap ? out : nullptr, out ? cap : 0); }
+
 int h2_ntt_shape(uint32_t log_n, uint32_t in_log, h2_ntt_pass_shape* out, size_t cap, size_t* count) {
     static_assert(sizeof(h2_ntt_pass_shape) == 7 * sizeof(uint32_t), "h2_ntt_pass_shape is seven words");
     if (!count || (cap && !out)) return bad("h2_ntt_shape: null argument");

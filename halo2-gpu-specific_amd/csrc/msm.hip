@@ -1559,6 +1559,25 @@ struct LdsLimit {
         if (dev >= 0 && dev < 64) raised[dev] = true;
     }
 };
+// The launch record (h2_msm_last_launches): msm_launch appends what it hands its kernels to a list of the calling thread;
+// the outermost driver on the thread empties the list when it is entered.  Host only; the vector keeps its capacity.
+namespace {
+thread_local std::vector<h2_msm_launch_info> t_launches;
+thread_local int t_launch_depth = 0;
+struct LaunchScope {  // one per driver: the outer one clears
+    LaunchScope() {
+        if (t_launch_depth++ == 0) t_launches.clear();
+    }
+    ~LaunchScope() { t_launch_depth--; }
+};
+}  // namespace
+size_t msm_last_launches(h2_msm_launch_info* out, size_t cap) {
+    const size_t count = t_launches.size();
+    if (out)
+        for (size_t i = 0; i < count && i < cap; i++) out[i] = t_launches[i];
+    return count;
+}
+
 // name the k_partition<TILE> / k_acc_slice<WAVES> that msm_launch starts
 template <uint32_t TILE>
 using tile = std::integral_constant<uint32_t, TILE>;
@@ -1603,7 +1622,10 @@ static void msm_launch(const MsmShape& s, const Hot& hot, const Fr* d_scalars, c
                            ((size_t)4 << s.hi_bits) + 4 * (TILE / 256), stream, keys, s.n, s.lo_bits, s.hi_bits, pcursor, tmp,
                            s.range_shift, s.W, s.R, (uint32_t)s.tab_stride, (const uint8_t*)bflags, w_first);
     };
+    h2_msm_launch_info rec{};
     if (s.tab && s.two_level) {
+        rec.partition = H2_MSM_PART_TWO_LEVEL;
+        rec.hot_partitioned = s.Wk > s.W ? 1u : 0u;
         uint2* tmpa = (uint2*)(scratch + s.off_tmpa);
         uint32_t* cursor_a = (uint32_t*)(scratch + s.off_tmpa + s.entries * 8);
         uint32_t* tile_start = cursor_a + PARTA_GROUPS_MAX;
@@ -1619,10 +1641,13 @@ static void msm_launch(const MsmShape& s, const Hot& hot, const Fr* d_scalars, c
         if (s.Wk > s.W) partition(tile<PART_T_TABLE>(), s.W, s.Wk - s.W);
         hipLaunchKernelGGL(k_part_b, dim3((unsigned)(s.entries / PART_AB_T + (1u << a_bits) + 1)), dim3(256), (size_t)PART_AB_T * 8,
                            stream, (const uint2*)tmpa, pbase, s.lo_bits, b_bits, a_bits, tile_start, pcursor, tmp);
-    } else if (s.tab && s.hi_bits > 10)
+    } else if (s.tab && s.hi_bits > 10) {
+        rec.partition = H2_MSM_PART_16384;
         partition(tile<PART_T_TABLE>(), 0u, s.Wk);
-    else
+    } else {
+        rec.partition = H2_MSM_PART_2048;
         partition(tile<PART_T>(), 0u, s.Wk);
+    }
     // a partition holding more than 4x its fair share (and at least a few thousand entries) takes the skew path
     uint32_t skew_threshold = (uint32_t)std::max<size_t>(4 * (s.entries / s.np), 4096);
     const uint32_t hot_partition = (!fused && hot.on) ? ((s.tab ? 1u : s.R * s.W) << s.hi_bits) : 0xffffffffu;
@@ -1658,6 +1683,7 @@ static void msm_launch(const MsmShape& s, const Hot& hot, const Fr* d_scalars, c
     // one lane per bucket from 2^19 buckets on (round 3, same box: 2^22 windowed 6.75 -> 6.61 ms, over a table 5.91 -> 5.76-5.90,
     // 2^24 windowed 23.9 -> 23.7; at 2^17 the forms tie, at 2^16 buckets the quads win by 4-7 %)
     static const uint32_t lane_from = getenv("H2_MSM_FINISH_LANE_LOG") ? 1u << atoi(getenv("H2_MSM_FINISH_LANE_LOG")) : 1u << 19;
+    rec.finish = s.nbt >= lane_from ? H2_MSM_FINISH_LANES : H2_MSM_FINISH_QUADS;
     if (s.nbt >= lane_from)
         hipLaunchKernelGGL(k_finish_lane, dim3((s.nbt + 255) / 256), dim3(256), 0, stream, partials, starts, s.nbt, s.log_s,
                            buckets, heavy + 1, heavy);
@@ -1688,6 +1714,22 @@ static void msm_launch(const MsmShape& s, const Hot& hot, const Fr* d_scalars, c
         hipLaunchKernelGGL(k_reduce, dim3(1, 1), dim3(REDUCE_T), 0, stream, buckets + s.nb, 1u, 1u, s.qm, winpart + s.Wt,
                            winpart + 1, (uint32_t*)(scratch + s.off_rcount));
     H2_HIP(hipGetLastError());
+    rec.form = fused ? H2_MSM_FORM_FUSED : s.tab ? H2_MSM_FORM_TABLE : H2_MSM_FORM_WINDOWED;
+    rec.max_bits = max_bits > 254 ? 254u : max_bits;
+    rec.c = s.c, rec.wfull = s.wfull, rec.W = s.W, rec.Wt = s.Wt, rec.Wk = s.Wk, rec.R = s.R, rec.range_shift = s.range_shift;
+    rec.cols = s.cols, rec.Wc = s.Wc, rec.nb = s.nb, rec.nbt = s.nbt, rec.lo_bits = s.lo_bits, rec.hi_bits = s.hi_bits;
+    rec.np = s.np, rec.log_s = s.log_s, rec.qm = s.qm, rec.RG = s.RG, rec.planes = s.planes, rec.chunks = s.chunks;
+    rec.plane_seg = s.plane_seg, rec.plane_l = s.plane_l, rec.two_level = s.two_level, rec.a_bits = s.a_bits;
+    rec.hot_on = (fused ? fused->hot_mask != 0 : hot.on) ? 1u : 0u;
+    rec.block_sums = bflags ? 1u : 0u;
+    rec.stage_cap = stage_cap, rec.skew_threshold = skew_threshold, rec.hot_partition = hot_partition;
+    rec.acc_waves = acc_waves == 5 ? 5u : 4u;
+    rec.reduce = (s.tab && s.planes) ? H2_MSM_REDUCE_PLANES : H2_MSM_REDUCE_GROUPS;
+    rec.hot_mask = fused ? fused->hot_mask : 0ull;
+    rec.n = s.n, rec.entries = s.entries, rec.scratch = (uint64_t)(uintptr_t)scratch;
+    rec.off_keys = s.off_keys, rec.off_sorted = s.off_sorted, rec.off_pbase = s.off_pbase, rec.off_starts = s.off_starts;
+    rec.off_heavy = s.off_heavy, rec.off_buckets = s.off_buckets, rec.total = s.total;
+    t_launches.push_back(rec);
 }
 
 // host tail: add the G partials of each window, then Horner over the windows
@@ -1792,6 +1834,7 @@ static void plan_decide(ColumnPlan& p, size_t n, const Fr* h_samples, const uint
 
 int msm_device(DeviceCtx* ctx, const Fr* d_scalars, const uint64_t* d_bases, size_t n, uint32_t max_bits,
                void* d_scratch, size_t scratch_bytes, uint64_t* out_xyz, hipStream_t stream) {
+    LaunchScope records;
     if (n == 0 || max_bits == 0) {
         msm_identity(out_xyz);
         return H2_OK;
@@ -1834,6 +1877,7 @@ int msm_device(DeviceCtx* ctx, const Fr* d_scalars, const uint64_t* d_bases, siz
 // narrow columns needs: at 2^18 a single MSM is ~1 ms of mostly fixed latency.
 static int msm_device_fused(DeviceCtx* ctx, const Fr* const* d_scalars, uint32_t cols, const uint64_t* d_bases, size_t n,
                             uint32_t bits, char* scratch, uint64_t* const* outs, hipStream_t stream) {
+    LaunchScope records;
     const MsmShape s = msm_shape(n, bits, false, cols);
     const size_t wp = exported_points(s);
     // the column table (cols pointers, padded to 16 bytes, then cols dominant values) is staged in pinned memory too
@@ -1916,6 +1960,7 @@ int msm_device_batch(DeviceCtx* ctx, const Fr* const* d_scalars, size_t count, c
 int msm_device_batch_ex(DeviceCtx* ctx, const Fr* const* d_scalars, const uint64_t* const* bases_each,
                         const uint32_t* bits_each, size_t count, const uint64_t* d_bases, size_t n, uint32_t max_bits,
                         void* d_scratch, size_t scratch_bytes, uint64_t* out_xyz, hipStream_t stream) {
+    LaunchScope records;
     if (count == 0) return H2_OK;
     std::vector<ColumnPlan> plans(count);
     uint32_t top_bits = 0;

@@ -6,6 +6,8 @@ namespace h2 {
 size_t msm_scratch_bytes(size_t n, uint32_t max_bits);
 void msm_shape_query(size_t n, uint32_t max_bits, uint32_t* c, uint32_t* windows, uint32_t* buckets_per_window);
 void msm_identity(uint64_t out_xyz[12]);
+// the launches of the calling thread's most recent msm_device* call (h2_msm_last_launches): returns their count
+size_t msm_last_launches(h2_msm_launch_info* out, size_t cap);
 // device-resident scalars + bases; result to host memory (synchronises `stream` for the final
 // W*G-point read-back and the host-side window combine)
 int msm_device(DeviceCtx* ctx, const Fr* d_scalars, const uint64_t* d_bases, size_t n, uint32_t max_bits,

@@ -684,6 +684,48 @@ int h2_dev_extended_to_coeff(void *d_a, void *d_tmp, uint32_t extended_k, const 
 size_t h2_msm_scratch_bytes(size_t n, uint32_t max_bits);
 /* the Pippenger shape the library will use: window bits c, number of windows, buckets per window */
 int h2_msm_shape(size_t n, uint32_t max_bits, uint32_t *c, uint32_t *windows, uint32_t *buckets_per_window);
+/* What the MSM launcher did, for reporting and for tests.  Part of what one launch runs depends on the sampled scalars (a
+ * dominant value, whether a table pays), so it cannot be told from n and the bound: every launch of the pipeline appends
+ * one record -- the very values it hands its kernels -- to a list of the calling thread.  The list is emptied when
+ * h2_dev_msm / _batch / _batch_ex (or a host-slice MSM that ends in them) is entered, so afterwards it holds that call's
+ * launches in launch order: one for h2_dev_msm, one per fused group and then one per remaining column for a batch.  Host
+ * only: no device work, no synchronisation, no allocation in the steady state. */
+enum { H2_MSM_FORM_WINDOWED = 0, H2_MSM_FORM_TABLE = 1, H2_MSM_FORM_FUSED = 2, H2_MSM_FORM_COUNT = 3 };
+enum {
+    H2_MSM_PART_2048 = 0,      /* k_partition<2048> over every key array */
+    H2_MSM_PART_16384 = 1,     /* k_partition<16384> over every key array (a table with more than 2^10 partitions) */
+    H2_MSM_PART_TWO_LEVEL = 2, /* k_part_a + k_part_b over the digit arrays of a table */
+    H2_MSM_PART_COUNT = 3
+};
+enum { H2_MSM_FINISH_QUADS = 0, H2_MSM_FINISH_LANES = 1, H2_MSM_FINISH_COUNT = 2 }; /* k_finish / k_finish_lane */
+enum { H2_MSM_REDUCE_GROUPS = 0, H2_MSM_REDUCE_PLANES = 1, H2_MSM_REDUCE_COUNT = 2 }; /* k_reduce / k_reduce_chunks + _planes */
+typedef struct {
+    uint32_t form;      /* H2_MSM_FORM_* */
+    uint32_t max_bits;  /* the bound k_digits was given */
+    /* the shape: window bits, windows c bits wide (the rest c - 1), digit windows, windows run, key arrays, row ranges and
+     * their shift, fused columns and windows per column, buckets per window and in all, the sort's split of a bucket id,
+     * partitions, slice length, k_reduce's chunk length and workgroups per window, the bit-plane reduce, the two-level
+     * partition */
+    uint32_t c, wfull, W, Wt, Wk, R, range_shift, cols, Wc, nb, nbt, lo_bits, hi_bits, np, log_s, qm, RG;
+    uint32_t planes, chunks, plane_seg, plane_l, two_level, a_bits;
+    uint32_t hot_on;          /* a dominant value has its own window (fused: any column has) */
+    uint32_t block_sums;      /* ... and whole 256-row blocks of it enter as one tabulated point */
+    uint32_t partition;       /* H2_MSM_PART_* */
+    uint32_t hot_partitioned; /* two-level: the dominant-value array went through k_partition<16384> on its own */
+    uint32_t stage_cap;       /* k_bucket_sort stages partitions of up to this many entries in LDS; 0: none */
+    uint32_t skew_threshold;  /* ... and counts larger ones with wave-aggregated atomics */
+    uint32_t hot_partition;   /* the partition k_copy_hot moves; 0xffffffff: none (fused: see hot_mask) */
+    uint32_t finish;          /* H2_MSM_FINISH_* */
+    uint32_t acc_waves;       /* k_acc_slice<4> or <5> */
+    uint32_t reduce;          /* H2_MSM_REDUCE_* */
+    uint64_t hot_mask;        /* fused: the columns with a dominant value */
+    uint64_t n, entries;
+    uint64_t scratch;         /* device address of the scratch slice, then byte offsets into it */
+    uint64_t off_keys, off_sorted, off_pbase, off_starts, off_heavy, off_buckets, total;
+} h2_msm_launch_info;
+/* Copies the calling thread's records to out[0 .. min(count, cap)) and returns their count, which may exceed cap
+ * (out may be null when cap is 0). */
+size_t h2_msm_last_launches(h2_msm_launch_info *out, size_t cap);
 /* The passes the library will run for a transform of 2^log_n points (best_fft, arithmetic.rs:546) whose first 2^in_log
  * inputs are live and the rest zero padding (in_log == log_n: none), for reporting and for tests: computed by the
  * launcher's own split, geometry and kernel selector under the same once-per-process H2_NTT_* knobs.  Host only.  Writes

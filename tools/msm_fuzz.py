@@ -36,6 +36,16 @@ def aff(j):
     return tuple(oracle.to_affine(j).tolist())
 
 
+def print_launches():
+    """what the launcher did in the call that just failed (h2_msm_last_launches: this thread's last MSM entry-point call)"""
+    import halo2_gpu_specific_amd as h2
+    from msm_plan_cases import last_launches
+
+    for k, rec in enumerate(last_launches(h2.lib())):
+        print("  launch %d: %s" % (k, " ".join("%s=%s" % (key, hex(v) if key in ("scratch", "hot_mask", "hot_partition") else v)
+                                              for key, v in rec.items())))
+
+
 def rand_ints(count, bits):
     """`count` uniform integers below min(2^bits, r) as Python ints"""
     words = rng.integers(0, 1 << 62, size=(count, 5), dtype=np.uint64)
@@ -121,6 +131,7 @@ def fused_cases():
                 bad = [j for j in range(count) if got[j] != want[j]]
                 print("MISMATCH fused group: n=%d bits=%d columns=%d (wrong: %s) scratch=%d seed=%d case=%d" % (
                     n, bits, count, bad, nbytes, seed, cases))
+                print_launches()
                 sys.exit(1)
         cases += 1
     print("msm_fuzz: %d groups of 2..7 columns in %.0f s, every column equal to the oracle (seed %d), fused and pipelined" % (
@@ -169,10 +180,12 @@ while time.time() < t_end:
     cases += 1
     if got != want:
         print("MISMATCH n=%d bits=%d use_bits=%d kind=%d seed=%d case=%d" % (n, bits, use_bits, kind, seed, cases))
+        print_launches()
         sys.exit(1)
     if tables:
         digits = int(rng.choice([0, 11, 12, 13, 15, 16, 20, 27, 32]))
         if aff(over_table(scalars, pts, use_bits, digits)) != want:
             print("MISMATCH over a table: n=%d bits=%d use_bits=%d kind=%d digits=%d seed=%d case=%d" % (n, bits, use_bits, kind, digits, seed, cases))
+            print_launches()
             sys.exit(1)
 print("msm_fuzz: %d cases in %.0f s, all equal to the oracle (seed %d)%s" % (cases, budget, seed, ", windowed and over tables" if tables else ""))
