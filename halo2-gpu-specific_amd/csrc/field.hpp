@@ -676,6 +676,28 @@ H2_DEV Fp<P> fp_mul_chunk(const Fp<P>& x, const FpChunk<CL>& t) {
     return r;
 #endif
 }
+// Stages 0 and 1 of a radix-2 DIT pass on the rows 4b .. 4b + 3 of one column, in the lazy domain: every twiddle is 1 but the
+// one of stage 1's second butterfly (w3).  x0 .. x3 in row order, in and out.  `red`: the four operands may be anywhere
+// below 4p and are brought below 2p first.  Without it they have to BE below 2p already, literally -- what a product
+// leaves: fp_mul_wide's result (below 2p) or fp_mul_chunk's (below p (1 + 2^-29)) -- and fp_lazy_red2p would hand each of
+// them back unchanged; so both forms compute the same 256-bit values, not merely the same residues.  Out: below 4p, like
+// every row in LDS.  Intermediates: y0, y1, y2 below 2p, y3 below p (1 + 2^-29).
+template <int CL, class P>
+H2_DEV void fp_lazy_first_pair(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3, const FpChunk<CL>& w3, const bool red) {
+    if (red) {
+        x0 = fp_lazy_red2p(x0);
+        x1 = fp_lazy_red2p(x1);
+        x2 = fp_lazy_red2p(x2);
+        x3 = fp_lazy_red2p(x3);
+    }
+    const Fp<P> y0 = fp_lazy_add_red(x0, x1), y1 = fp_lazy_sub_red(x0, x1);
+    const Fp<P> y2 = fp_lazy_red2p(fp_lazy_add(x2, x3));
+    const Fp<P> y3 = fp_mul_chunk(fp_lazy_sub(x2, x3), w3);
+    x0 = fp_lazy_add(y0, y2);
+    x1 = fp_lazy_add(y1, y3);
+    x2 = fp_lazy_sub(y0, y2);
+    x3 = fp_lazy_sub(y1, y3);
+}
 // w (Montgomery form) -> the table entry fp_mul_chunk reads: T_k = w_plain 2^(32 CL k + 32 (CL + 1)) mod p, one Montgomery
 // product of the plain value by the constant 2^e R mod p each (CHUNK_POW holds e = 64, 96 .. 288).
 template <int CL, class P>

@@ -157,7 +157,7 @@ __device__ __forceinline__ Fr store_twiddle(const PassArgs& a, const Fr& y, cons
         t.w[4 * k] = v.x; t.w[4 * k + 1] = v.y; t.w[4 * k + 2] = v.z; t.w[4 * k + 3] = v.w;
     }
     // any 256-bit y (a pass hands on values below 4p) -> below p (1 + 2^-29) < 2p: what the next pass's first butterflies
-    // take as they are (fp_lazy_red2p of a value below 4p)
+    // take as they are (k_ntt_pass8: with no reduction, fp_lazy_first_pair; k_ntt_pass: fp_lazy_red2p hands them back)
     return fp_mul_chunk(y, t);
 }
 
@@ -485,6 +485,9 @@ static_assert(4 * PASS8_LDS <= 160u * 1024, "four workgroups of k_ntt_pass8 per 
 // NLAST, ST: k_ntt_pass's.  With ST the product runs on the four results a lane holds after the last stage pair, rows
 // (tid >> 2) + 64 q of a tile whose next-pass row rho' is uniform: entries (rho' << 8) | k of that table, 16 consecutive ones
 // (2 KiB) per wave and load, the same 256 (32 KiB) for the 64 consecutive tiles of one rho'.
+// Loads that depend on nothing are issued before the waits they used to follow (profiles/ntt_tile_ends_isa.txt): at the head
+// the word of the LDS table copy, the four elements and the last pass's first two table entries are one batch, waited for
+// once; at the tail the store products keep the next entry's first half in flight.
 template <bool NLAST, bool ST = false>
 __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     static_assert(!ST || NLAST, "a last pass stores the transform's output");
@@ -509,7 +512,10 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     auto bmul = [](const Fr& x, const Tw& t) __attribute__((always_inline)) -> Fr { return fp_mul_chunk(x, t); };
     // stages s and s + 1 on the rows p, p + h, p + 2h, p + 3h (h = 2^s) of one column, in registers, twiddle index r = p mod h:
     // the arithmetic of k_ntt_pass's round4, operation for operation; x0 .. x3 come back in row order
-    auto unit4 = [&](Fr& x0, Fr& x1, Fr& x2, Fr& x3, const uint32_t s, const uint32_t r, const bool unit, const Tw* w3 = nullptr) __attribute__((always_inline)) {
+    // In two halves, so that the last stage pair can start the loads of what follows it between them.  unit4_mul: everything
+    // up to the last product; x0 .. x3 leave as y0, y1 (below 2p) and y2, y3 (products: below p (1 + 2^-29); y2 of a unit:
+    // below 2p).  unit4_add: the four sums and differences, below 4p.
+    auto unit4_mul = [&](Fr& x0, Fr& x1, Fr& x2, Fr& x3, const uint32_t s, const uint32_t r, const bool unit) __attribute__((always_inline)) {
         const uint32_t h = 1u << s;
         const bool mem = s == B - 2;   // the last stage pair: twiddles of every index
         x0 = fp_lazy_red2p(x0);
@@ -525,7 +531,14 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
         const Fr y0 = fp_lazy_add_red(x0, x1), y1 = fp_lazy_sub_red(x0, x1);
         Fr y2 = fp_lazy_add(x2, x3), y3 = fp_lazy_sub(x2, x3);
         y2 = unit ? fp_lazy_red2p(y2) : bmul(y2, tw_get(r << (B - 2 - s), mem));
-        y3 = bmul(y3, w3 ? *w3 : tw_get((r + h) << (B - 2 - s), mem));   // (w3: that twiddle, already in registers)
+        y3 = bmul(y3, tw_get((r + h) << (B - 2 - s), mem));
+        x0 = y0;
+        x1 = y1;
+        x2 = y2;
+        x3 = y3;
+    };
+    auto unit4_add = [](Fr& x0, Fr& x1, Fr& x2, Fr& x3) __attribute__((always_inline)) {
+        const Fr y0 = x0, y1 = x1, y2 = x2, y3 = x3;
         x0 = fp_lazy_add(y0, y2);
         x1 = fp_lazy_add(y1, y3);
         x2 = fp_lazy_sub(y0, y2);
@@ -558,7 +571,8 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
         const uint32_t step = (1u << s) << log_c;
         Fr x0 = lds_get(t_lo, t_hi, i0), x1 = lds_get(t_lo, t_hi, i0 + step);
         Fr x2 = lds_get(t_lo, t_hi, i0 + 2 * step), x3 = lds_get(t_lo, t_hi, i0 + 3 * step);
-        unit4(x0, x1, x2, x3, s, r, unit);
+        unit4_mul(x0, x1, x2, x3, s, r, unit);
+        unit4_add(x0, x1, x2, x3);
         lds_put(t_lo, t_hi, i0, x0);
         lds_put(t_lo, t_hi, i0 + 2 * step, x2);
         lds_put(t_lo, t_hi, i0 + step, x1);
@@ -568,9 +582,13 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     const bool is_last = NLAST ? false : a.is_last != 0;
     const uint32_t n_mask = (a.log_n >= 32) ? 0xffffffffu : ((1u << a.log_n) - 1);
 
-#pragma unroll
-    for (uint32_t g = tid; g < PASS8_TW_LDS * TW_CHUNK_Q; g += 256)
-        w_pl[(g % TW_CHUNK_Q) * PASS8_TW_LDS + g / TW_CHUNK_Q] = tw_tab[(size_t)(g / TW_CHUNK_Q) * 4 * TW_CHUNK_Q + g % TW_CHUNK_Q];
+    // The LDS copy of the table's entries 0, 4, 8 ..: one 16-byte word per lane.  Nothing reads it before the tile's first
+    // barrier, so only its load is issued here; the word goes to LDS once the tile's element loads are in flight behind it:
+    // one memory round trip at the head of a tile, not a table round trip and then an element round trip.  (The wait in
+    // front of that ds_write compiles to vmcnt(0): the element loads are under exec masks, idx < in_len, so how many of them
+    // are behind this load is not known statically.  The elements are what the lane needs next in any case.)
+    static_assert(PASS8_TW_LDS * TW_CHUNK_Q == 256, "one word of the LDS copy per lane");
+    const uint4 w_fill = tw_tab[(size_t)(tid / TW_CHUNK_Q) * 4 * TW_CHUNK_Q + tid % TW_CHUNK_Q];
 
     // stage 1's twiddle of index 1 for the first stage pair, straight from the table (wave-uniform address)
     Tw tw64;
@@ -613,6 +631,16 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
                 x[q] = fp_zero<FrParams>();
                 if (idx[q] < a.in_len) x[q] = fp_load(in_p + idx[q]);
             }
+            const bool pre_scale = a.scale_mode == 1u && a.nprev == 0;
+            // the last pass's table: its first two entries are requested with the elements, not after pre3
+            const bool direct = !NLAST && a.nprev != 0 && !a.tw_applied && a.tw_direct != nullptr && !pre_scale;
+            Fr wd[2];
+            if (direct) {
+#pragma unroll
+                for (uint32_t q = 0; q < 2; q++) wd[q] = fp_load(a.tw_direct + ((Kk[q] << B) | rho[q]));
+            }
+            __builtin_amdgcn_sched_barrier(0);   // (every load above is issued before the wait below)
+            w_pl[(tid % TW_CHUNK_Q) * PASS8_TW_LDS + tid / TW_CHUNK_Q] = w_fill;
             if (a.has_pre3) {
 #pragma unroll
                 for (uint32_t q = 0; q < NE; q++) {
@@ -623,17 +651,15 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
                     if (m != 0) x[q] = tmul(x[q], w);
                 }
             }
-            const bool pre_scale = a.scale_mode == 1u && a.nprev == 0;
             if ((a.nprev != 0 && !a.tw_applied) || pre_scale) {
-                if (!NLAST && a.tw_direct != nullptr && !pre_scale) {   // (the last pass's table)
+                if (direct) {
+                    Fr w[2];
 #pragma unroll
-                    for (uint32_t q0 = 0; q0 < NE; q0 += 2) {
-                        Fr w[2];
+                    for (uint32_t q = 0; q < 2; q++) w[q] = fp_load(a.tw_direct + ((Kk[2 + q] << B) | rho[2 + q]));
 #pragma unroll
-                        for (uint32_t q = 0; q < 2; q++) w[q] = fp_load(a.tw_direct + ((Kk[q0 + q] << B) | rho[q0 + q]));
+                    for (uint32_t q = 0; q < 2; q++) x[q] = tmul(x[q], wd[q]);
 #pragma unroll
-                        for (uint32_t q = 0; q < 2; q++) x[q0 + q] = tmul(x[q0 + q], w[q]);
-                    }
+                    for (uint32_t q = 0; q < 2; q++) x[2 + q] = tmul(x[2 + q], w[q]);
                 } else if (a.log_n <= LO_BITS && !pre_scale) {
 #pragma unroll
                     for (uint32_t q = 0; q < NE; q++) {
@@ -661,7 +687,11 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
             // x[q] is row 4b + bitrev2(q) of unit b: stages 0 and 1 (every twiddle of stage 0 and index 0 of stage 1 is 1)
             const uint32_t b = is_last ? bitrev(tid & 63, B - 2) : (tid >> log_c);
             const uint32_t i0 = (b << (2 + log_c)) + (is_last ? (tid >> 6) : (tid & (C - 1)));
-            unit4(x[0], x[2], x[1], x[3], 0, 0, true, &tw64);
+            // Operands that left a product are below 2p as they are: a later pass's come from the store product of the pass
+            // before it (tw_applied: below p (1 + 2^-29)) or from the twiddle product above (below 2p), a coset first pass's
+            // from its pre-scale.  Only a first pass that loads the caller's data (with or without pre3, which leaves every
+            // third element unmultiplied) has to reduce them.  Wave-uniform.
+            fp_lazy_first_pair(x[0], x[2], x[1], x[3], tw64, !(a.nprev != 0 || pre_scale));
             lds_put(t_lo, t_hi, i0, x[0]);
             lds_put(t_lo, t_hi, i0 + 2 * C, x[1]);
             lds_put(t_lo, t_hi, i0 + C, x[2]);
@@ -673,13 +703,31 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
 
         // ---- last stage pair and store (+ post-scale on the final pass): lane t holds rows (t >> 2) + 64 q of column t & 3
         Fr y[NE];
+        // the next pass's inter-pass twiddles (ST): entry q of this lane, 64 << t_log entries apart; rho' from the tile's base:
+        // its 4 columns share it (nx_s_log >= 2)
+        const uint4* nx_q = nullptr;
+        size_t nx_step = 0;
+        if constexpr (ST) {
+            const uint32_t rho_n = (base >> a.nx_s_log) & ((1u << a.nx_B) - 1);
+            const uint32_t K_n = K_uniform | ((tid >> log_c) << a.t_log);
+            nx_q = reinterpret_cast<const uint4*>(a.nx_tab) + (size_t)((rho_n << a.nx_t_log) | K_n) * TW_CHUNK_Q;
+            nx_step = (size_t)((R / NE) << a.t_log) * TW_CHUNK_Q;
+        }
+        Tw nx_t;   // ST: the entry of the product that runs next
         {
             uint32_t i0, r;
             bool unit;
             unit_of(tid, 6, i0, r, unit);
 #pragma unroll
             for (uint32_t q = 0; q < NE; q++) y[q] = lds_get(t_lo, t_hi, i0 + q * (R << log_c) / NE);
-            unit4(y[0], y[1], y[2], y[3], 6, r, unit);
+            unit4_mul(y[0], y[1], y[2], y[3], 6, r, unit);
+            if constexpr (ST) {
+                // the first store product's entry under the pair's last additions
+#pragma unroll
+                for (uint32_t k = 0; k < TW_CHUNK_Q; k++) tw_unpack(nx_t, k, nx_q[k]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            unit4_add(y[0], y[1], y[2], y[3]);
         }
         uint32_t idx[NE];
 #pragma unroll
@@ -711,12 +759,27 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
             for (uint32_t q = 0; q < NE; q++) y[q] = fp_lazy_canon(y[q]);
         }
         if constexpr (ST) {
-            // the next pass's inter-pass twiddle, one at a time; rho' from the tile's base: its 4 columns share it (nx_s_log >= 2)
-            const uint32_t rho_n = (base >> a.nx_s_log) & ((1u << a.nx_B) - 1);
+            // the next pass's inter-pass twiddle, one product at a time (an entry is 32 registers next to the four results).
+            // Under product q the first PF words of entry q + 1 are in flight (what the registers allow); its other words are
+            // requested together when product q has freed theirs.  Any 256-bit y -> below p (1 + 2^-29): what the next pass's
+            // first stage pair takes without a reduction.
+            constexpr uint32_t PF = TW_CHUNK_Q / 2;
 #pragma unroll
             for (uint32_t q = 0; q < NE; q++) {
-                const uint32_t K_n = K_uniform | (((tid >> log_c) + q * (R / NE)) << a.t_log);
-                y[q] = store_twiddle(a, y[q], (rho_n << a.nx_t_log) | K_n);
+                uint4 pf[PF];
+                if (q + 1 < NE) {
+#pragma unroll
+                    for (uint32_t k = 0; k < PF; k++) pf[k] = nx_q[(q + 1) * nx_step + k];
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                y[q] = fp_mul_chunk(y[q], nx_t);
+                if (q + 1 < NE) {
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (uint32_t k = PF; k < TW_CHUNK_Q; k++) tw_unpack(nx_t, k, nx_q[(q + 1) * nx_step + k]);
+#pragma unroll
+                    for (uint32_t k = 0; k < PF; k++) tw_unpack(nx_t, k, pf[k]);
+                }
             }
         }
 #pragma unroll
