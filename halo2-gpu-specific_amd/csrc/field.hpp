@@ -33,6 +33,8 @@ struct FrParams {
                                         0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
     static constexpr uint32_t MOD2[8] = {0xe0000002u, 0x87c3eb27u, 0xf372e122u, 0x5067d090u,
                                          0x0302b0bau, 0x70a08b6du, 0xc2634053u, 0x60c89ce5u};  // 2r (the lazy domain of the NTT)
+    static constexpr uint32_t MOD4[8] = {0xc0000004u, 0x0f87d64fu, 0xe6e5c245u, 0xa0cfa121u,
+                                         0x06056174u, 0xe14116dau, 0x84c680a6u, 0xc19139cbu};  // 4r (its rows' bound: fp_lazy_sub_from4p)
     static constexpr uint32_t NMOD[8] = {0x0fffffffu, 0xbc1e0a6cu, 0x86468f6eu, 0xd7cc17b7u,
                                          0x7e7ea7a2u, 0x47afba49u, 0x1ece5fd6u, 0xcf9bb18du};  // 2^256 - r (fp_mul_const)
     static constexpr uint32_t PINV256[8] = {0xefffffffu, 0xc2e1f593u, 0x4c6911b3u, 0x6586864bu,
@@ -58,6 +60,8 @@ struct FqParams {
                                         0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
     static constexpr uint32_t MOD2[8] = {0xb0f9fa8eu, 0x7841182du, 0xd0e3951au, 0x2f02d522u,
                                          0x0302b0bbu, 0x70a08b6du, 0xc2634053u, 0x60c89ce5u};  // 2q
+    static constexpr uint32_t MOD4[8] = {0x61f3f51cu, 0xf082305bu, 0xa1c72a34u, 0x5e05aa45u,
+                                         0x06056176u, 0xe14116dau, 0x84c680a6u, 0xc19139cbu};  // 4q
     static constexpr uint32_t NMOD[8] = {0x278302b9u, 0xc3df73e9u, 0x978e3572u, 0x687e956eu,
                                          0x7e7ea7a2u, 0x47afba49u, 0x1ece5fd6u, 0xcf9bb18du};  // 2^256 - q
     static constexpr uint32_t PINV256[8] = {0xe4866389u, 0x87d20782u, 0x1eca6ac9u, 0x9ede7d65u,
@@ -283,6 +287,11 @@ H2_DEV Fp<P> fp_dbl(const Fp<P>& a) {
 // to the product instead of 48 + the product's own 16-24 of reduction; the canonical residue comes back once, at the
 // pass's store (fp_lazy_canon).  Same field elements as the canonical arithmetic at every point (mod p), hence bit-exact
 // results after the final canonicalisation.
+// Two ranges are wider or narrower than that and are used where they hold (k_ntt_pass8, tests/test_ntt_lazy_ranges_host.py):
+// 2^256 = 5.29 p and fp_mul_chunk returns values below p (1 + 2^-29), so the first operand of a product may be the sum of a
+// row (strictly below 4p) and such a product, or their difference with the offset 4p (fp_lazy_sub_from4p), both below
+// 5p + 2^-29 p; and the caller's data are canonical, below p, so a pass that loads them starts from bare sums
+// (fp_lazy_first_pair_canon).
 // a < 4p  ->  a or a - 2p, below 2p
 template <class P>
 H2_DEV Fp<P> fp_lazy_red2p(const Fp<P>& a) {
@@ -330,21 +339,27 @@ H2_DEV Fp<P> fp_lazy_add(const Fp<P>& a, const Fp<P>& b) {
 #endif
     return s;
 }
-// a - b + 2p as 256-bit integers (a, b < 2p -> in (0, 4p)); the two chains run one limb apart
-template <class P>
-H2_DEV Fp<P> fp_lazy_sub(const Fp<P>& a, const Fp<P>& b) {
+// limb i of M p, M = 1, 2, 4
+template <int M, class P>
+H2_DEV uint32_t fp_lazy_mod(const int i) {
+    static_assert(M == 1 || M == 2 || M == 4, "p, 2p and 4p are tabulated");
+    return M == 1 ? P::MOD[i] : (M == 2 ? P::MOD2[i] : P::MOD4[i]);
+}
+// a - b + M p as 256-bit integers, for operands with b < a + M p and a - b + M p < 2^256; the two chains run one limb apart
+template <int M, class P>
+H2_DEV Fp<P> fp_lazy_sub_off(const Fp<P>& a, const Fp<P>& b) {
     Fp<P> d, u;
 #ifdef H2_ASM_CHAINS
     uint64_t ca, cb;
     d.l[0] = sub_co(a.l[0], b.l[0], ca);
     d.l[1] = subb_co(a.l[1], b.l[1], ca);
-    u.l[0] = add_co(d.l[0], P::MOD2[0], cb);
+    u.l[0] = add_co(d.l[0], fp_lazy_mod<M, P>(0), cb);
 #pragma unroll
     for (int i = 2; i < 8; i++) {
         d.l[i] = subb_co(a.l[i], b.l[i], ca);
-        u.l[i - 1] = addc_co(d.l[i - 1], P::MOD2[i - 1], cb);
+        u.l[i - 1] = addc_co(d.l[i - 1], fp_lazy_mod<M, P>(i - 1), cb);
     }
-    u.l[7] = addc_co(d.l[7], P::MOD2[7], cb);
+    u.l[7] = addc_co(d.l[7], fp_lazy_mod<M, P>(7), cb);
 #else
     uint64_t borrow = 0, c = 0;
 #pragma unroll
@@ -355,12 +370,23 @@ H2_DEV Fp<P> fp_lazy_sub(const Fp<P>& a, const Fp<P>& b) {
     }
 #pragma unroll
     for (int i = 0; i < 8; i++) {
-        c += (uint64_t)d.l[i] + P::MOD2[i];
+        c += (uint64_t)d.l[i] + fp_lazy_mod<M, P>(i);
         u.l[i] = (uint32_t)c;
         c >>= 32;
     }
 #endif
     return u;  // the wrap of d and the carry out of u cancel: the true value is below 2^256
+}
+// a - b + 2p (a, b < 2p -> in (0, 4p))
+template <class P>
+H2_DEV Fp<P> fp_lazy_sub(const Fp<P>& a, const Fp<P>& b) {
+    return fp_lazy_sub_off<2>(a, b);
+}
+// a - b + 4p for a row b as LDS holds it, STRICTLY below 4p, and a product a (fp_mul_chunk: below p (1 + 2^-29)): in
+// (0, 5p + 2^-29 p), below 2^256 = 5.29 p -- a product's first operand and nothing else (it is not below 4p)
+template <class P>
+H2_DEV Fp<P> fp_lazy_sub_from4p(const Fp<P>& a, const Fp<P>& b) {
+    return fp_lazy_sub_off<4>(a, b);
 }
 // (a + b) brought below 2p / (a - b) brought into [0, 2p)   (a, b < 2p): fp_add / fp_sub with the modulus 2p
 template <class P>
@@ -682,21 +708,43 @@ H2_DEV Fp<P> fp_mul_chunk(const Fp<P>& x, const FpChunk<CL>& t) {
 // leaves: fp_mul_wide's result (below 2p) or fp_mul_chunk's (below p (1 + 2^-29)) -- and fp_lazy_red2p would hand each of
 // them back unchanged; so both forms compute the same 256-bit values, not merely the same residues.  Out: below 4p, like
 // every row in LDS.  Intermediates: y0, y1, y2 below 2p, y3 below p (1 + 2^-29).
+// FIRST_PAIR_CANON: the four operands are CANONICAL residues, below p -- the caller's data as the library takes them
+// (include/halo2_hip.h), the zeros of a padded call included -- so no sum of two of them reaches 2p and nothing is reduced at
+// all: y0 = x0 + x1 and y2 = x2 + x3 are bare additions (below 2p), y1 = x0 - x1 + p lies in (0, 2p), y3 is the product as
+// before.  The same residues as the other two forms, other representatives below 4p.  96 instructions next to the product
+// where FIRST_PAIR_4P has 200.
+enum FirstPair { FIRST_PAIR_2P = 0, FIRST_PAIR_4P = 1, FIRST_PAIR_CANON = 2 };
 template <int CL, class P>
-H2_DEV void fp_lazy_first_pair(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3, const FpChunk<CL>& w3, const bool red) {
-    if (red) {
-        x0 = fp_lazy_red2p(x0);
-        x1 = fp_lazy_red2p(x1);
-        x2 = fp_lazy_red2p(x2);
-        x3 = fp_lazy_red2p(x3);
+H2_DEV void fp_lazy_first_pair_of(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3, const FpChunk<CL>& w3, const FirstPair form) {
+    Fp<P> y0, y1, y2;
+    if (form == FIRST_PAIR_CANON) {
+        y0 = fp_lazy_add(x0, x1);
+        y1 = fp_lazy_sub_off<1>(x0, x1);
+        y2 = fp_lazy_add(x2, x3);
+    } else {
+        if (form == FIRST_PAIR_4P) {
+            x0 = fp_lazy_red2p(x0);
+            x1 = fp_lazy_red2p(x1);
+            x2 = fp_lazy_red2p(x2);
+            x3 = fp_lazy_red2p(x3);
+        }
+        y0 = fp_lazy_add_red(x0, x1);
+        y1 = fp_lazy_sub_red(x0, x1);
+        y2 = fp_lazy_red2p(fp_lazy_add(x2, x3));
     }
-    const Fp<P> y0 = fp_lazy_add_red(x0, x1), y1 = fp_lazy_sub_red(x0, x1);
-    const Fp<P> y2 = fp_lazy_red2p(fp_lazy_add(x2, x3));
     const Fp<P> y3 = fp_mul_chunk(fp_lazy_sub(x2, x3), w3);
     x0 = fp_lazy_add(y0, y2);
     x1 = fp_lazy_add(y1, y3);
     x2 = fp_lazy_sub(y0, y2);
     x3 = fp_lazy_sub(y1, y3);
+}
+template <int CL, class P>
+H2_DEV void fp_lazy_first_pair(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3, const FpChunk<CL>& w3, const bool red) {
+    fp_lazy_first_pair_of(x0, x1, x2, x3, w3, red ? FIRST_PAIR_4P : FIRST_PAIR_2P);
+}
+template <int CL, class P>
+H2_DEV void fp_lazy_first_pair_canon(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3, const FpChunk<CL>& w3) {
+    fp_lazy_first_pair_of(x0, x1, x2, x3, w3, FIRST_PAIR_CANON);
 }
 // w (Montgomery form) -> the table entry fp_mul_chunk reads: T_k = w_plain 2^(32 CL k + 32 (CL + 1)) mod p, one Montgomery
 // product of the plain value by the constant 2^e R mod p each (CHUNK_POW holds e = 64, 96 .. 288).

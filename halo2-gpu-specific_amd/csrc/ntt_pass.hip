@@ -511,38 +511,50 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     };
     auto bmul = [](const Fr& x, const Tw& t) __attribute__((always_inline)) -> Fr { return fp_mul_chunk(x, t); };
     // stages s and s + 1 on the rows p, p + h, p + 2h, p + 3h (h = 2^s) of one column, in registers, twiddle index r = p mod h:
-    // the arithmetic of k_ntt_pass's round4, operation for operation; x0 .. x3 come back in row order
+    // the butterflies of k_ntt_pass's round4 on the same residues; x0 .. x3 come back in row order
     // In two halves, so that the last stage pair can start the loads of what follows it between them.  unit4_mul: everything
-    // up to the last product; x0 .. x3 leave as y0, y1 (below 2p) and y2, y3 (products: below p (1 + 2^-29); y2 of a unit:
-    // below 2p).  unit4_add: the four sums and differences, below 4p.
+    // up to the last product; x0 .. x3 leave as y0, y1 (below 2p), y2 and n3 = -y3 (products: below p (1 + 2^-29); y2 of a
+    // unit: below 2p).  unit4_add: the four sums and differences, below 4p.
+    // The rows come in STRICTLY below 4p, and x2 is used as it comes: its sum with the product x3' = x3 wa is below
+    // 5p + 2^-29 p < 2^256 = 5.29 p, which a product takes as it is (fp_mul_chunk: any 256-bit operand), and so is the
+    // difference taken the other way round, x3' - x2 + 4p in (0, 5p + 2^-29 p): n3 = (x3' - x2 + 4p) wc is -y3, and unit4_add
+    // subtracts where it added.  One fp_lazy_red2p per unit less than reducing x2 first; the products' results are below
+    // p (1 + 2^-29) whatever went in, so the rows written are bounded as before.  (Not for k_ntt_pass: fp_mul_const and
+    // fp_mul_wide return values below 2p, and x2 + x3' could reach 6p.)  A unit takes its difference the other way round too,
+    // x3 - x2 + 2p of the reduced operands, so that one unit4_add serves both.
     auto unit4_mul = [&](Fr& x0, Fr& x1, Fr& x2, Fr& x3, const uint32_t s, const uint32_t r, const bool unit) __attribute__((always_inline)) {
         const uint32_t h = 1u << s;
         const bool mem = s == B - 2;   // the last stage pair: twiddles of every index
         x0 = fp_lazy_red2p(x0);
-        x2 = fp_lazy_red2p(x2);
+        Fr y2, n3;
         if (!unit) {
             const Tw wa = tw_get(r << (B - 1 - s), mem);
             x1 = bmul(x1, wa);
             x3 = bmul(x3, wa);
+            y2 = fp_lazy_add(x2, x3);            // below 5p + 2^-29 p
+            n3 = fp_lazy_sub_from4p(x3, x2);     // in (0, 5p + 2^-29 p)
         } else {
             x1 = fp_lazy_red2p(x1);
+            x2 = fp_lazy_red2p(x2);
             x3 = fp_lazy_red2p(x3);
+            y2 = fp_lazy_add(x2, x3);            // below 4p
+            n3 = fp_lazy_sub(x3, x2);            // in (0, 4p)
         }
         const Fr y0 = fp_lazy_add_red(x0, x1), y1 = fp_lazy_sub_red(x0, x1);
-        Fr y2 = fp_lazy_add(x2, x3), y3 = fp_lazy_sub(x2, x3);
         y2 = unit ? fp_lazy_red2p(y2) : bmul(y2, tw_get(r << (B - 2 - s), mem));
-        y3 = bmul(y3, tw_get((r + h) << (B - 2 - s), mem));
+        n3 = bmul(n3, tw_get((r + h) << (B - 2 - s), mem));
         x0 = y0;
         x1 = y1;
         x2 = y2;
-        x3 = y3;
+        x3 = n3;
     };
+    // y0, y1, y2 below 2p, n3 = -y3 below p (1 + 2^-29): rows y0 + y2, y1 + y3, y0 - y2, y1 - y3, each strictly below 4p
     auto unit4_add = [](Fr& x0, Fr& x1, Fr& x2, Fr& x3) __attribute__((always_inline)) {
-        const Fr y0 = x0, y1 = x1, y2 = x2, y3 = x3;
+        const Fr y0 = x0, y1 = x1, y2 = x2, n3 = x3;
         x0 = fp_lazy_add(y0, y2);
-        x1 = fp_lazy_add(y1, y3);
+        x1 = fp_lazy_sub(y1, n3);
         x2 = fp_lazy_sub(y0, y2);
-        x3 = fp_lazy_sub(y1, y3);
+        x3 = fp_lazy_add(y1, n3);
     };
     // the unit of lane `tid` in the round of stages s, s + 1: first LDS index, twiddle index (k_ntt_pass's round4)
     auto unit_of = [](const uint32_t tid, const uint32_t s, uint32_t& i0, uint32_t& r, bool& unit) __attribute__((always_inline)) {
@@ -689,9 +701,12 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
             const uint32_t i0 = (b << (2 + log_c)) + (is_last ? (tid >> 6) : (tid & (C - 1)));
             // Operands that left a product are below 2p as they are: a later pass's come from the store product of the pass
             // before it (tw_applied: below p (1 + 2^-29)) or from the twiddle product above (below 2p), a coset first pass's
-            // from its pre-scale.  Only a first pass that loads the caller's data (with or without pre3, which leaves every
-            // third element unmultiplied) has to reduce them.  Wave-uniform.
-            fp_lazy_first_pair(x[0], x[2], x[1], x[3], tw64, !(a.nprev != 0 || pre_scale));
+            // from its pre-scale.  A first pass that loads the caller's data and nothing else holds canonical residues, below p
+            // (the library's contract for every input; the zeros of a padded call are): no reduction either, and bare sums in
+            // place of the reducing ones (FIRST_PAIR_CANON).  Only with pre3, which leaves every third element as loaded next to
+            // two products below 2p, the operands are reduced as before.  Wave-uniform.
+            const FirstPair form = (a.nprev != 0 || pre_scale) ? FIRST_PAIR_2P : (a.has_pre3 ? FIRST_PAIR_4P : FIRST_PAIR_CANON);
+            fp_lazy_first_pair_of(x[0], x[2], x[1], x[3], tw64, form);
             lds_put(t_lo, t_hi, i0, x[0]);
             lds_put(t_lo, t_hi, i0 + 2 * C, x[1]);
             lds_put(t_lo, t_hi, i0 + C, x[2]);
