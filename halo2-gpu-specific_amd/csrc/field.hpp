@@ -702,6 +702,27 @@ H2_DEV Fp<P> fp_mul_chunk(const Fp<P>& x, const FpChunk<CL>& t) {
     return r;
 #endif
 }
+// fp_mul_chunk<1> with the entry taken PLANE BY PLANE: column c of the eight-chunk sweep is sum_j x_j (limb c of T_j), i.e. it
+// reads the eight words t.w[8 c .. 8 c + 7] and no other, so the 64-word entry never has to be live at once.  fetch(w, c)
+// fills w[0 .. 7] with plane c; on the device it is called AH (1 or 2) planes ahead of the column that is summed, between
+// the blocks of the generated schedule.  SREG: the words are wave-uniform and go to scalar registers (the operand class of
+// the modulus limbs; fetch has to produce them by scalar loads).  The same 256-bit result as fp_mul_chunk<1> on the entry.
+template <int AH, bool SREG = false, class P, class Fetch>
+H2_DEV Fp<P> fp_mul_chunk_planes(const Fp<P>& x, Fetch&& fetch) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(H2_PORTABLE_MUL)
+    // (generated for Fr only: tools/gen_fp_mul.py PLANE_FIELDS)
+    if constexpr (SREG) return fp_mul_chunk1_splanes_dev<AH>(x, fetch);
+    else return fp_mul_chunk1_planes_dev<AH>(x, fetch);
+#else
+    FpChunk<1> t;
+    for (int c = 0; c < 8; c++) {
+        uint32_t w[8];
+        fetch(w, c);
+        for (int k = 0; k < 8; k++) t.w[8 * c + k] = w[k];
+    }
+    return fp_mul_chunk<1>(x, t);
+#endif
+}
 // Stages 0 and 1 of a radix-2 DIT pass on the rows 4b .. 4b + 3 of one column, in the lazy domain: every twiddle is 1 but the
 // one of stage 1's second butterfly (w3).  x0 .. x3 in row order, in and out.  `red`: the four operands may be anywhere
 // below 4p and are brought below 2p first.  Without it they have to BE below 2p already, literally -- what a product
@@ -714,8 +735,9 @@ H2_DEV Fp<P> fp_mul_chunk(const Fp<P>& x, const FpChunk<CL>& t) {
 // before.  The same residues as the other two forms, other representatives below 4p.  96 instructions next to the product
 // where FIRST_PAIR_4P has 200.
 enum FirstPair { FIRST_PAIR_2P = 0, FIRST_PAIR_4P = 1, FIRST_PAIR_CANON = 2 };
-template <int CL, class P>
-H2_DEV void fp_lazy_first_pair_of(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3, const FpChunk<CL>& w3, const FirstPair form) {
+// (fp_lazy_first_pair_mul: the product by w3 is the caller's -- mul(d) = d w3 for any 256-bit d, below p (1 + 2^-29))
+template <class P, class Mul>
+H2_DEV void fp_lazy_first_pair_mul(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3, Mul&& mul, const FirstPair form) {
     Fp<P> y0, y1, y2;
     if (form == FIRST_PAIR_CANON) {
         y0 = fp_lazy_add(x0, x1);
@@ -732,11 +754,15 @@ H2_DEV void fp_lazy_first_pair_of(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3, co
         y1 = fp_lazy_sub_red(x0, x1);
         y2 = fp_lazy_red2p(fp_lazy_add(x2, x3));
     }
-    const Fp<P> y3 = fp_mul_chunk(fp_lazy_sub(x2, x3), w3);
+    const Fp<P> y3 = mul(fp_lazy_sub(x2, x3));
     x0 = fp_lazy_add(y0, y2);
     x1 = fp_lazy_add(y1, y3);
     x2 = fp_lazy_sub(y0, y2);
     x3 = fp_lazy_sub(y1, y3);
+}
+template <int CL, class P>
+H2_DEV void fp_lazy_first_pair_of(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3, const FpChunk<CL>& w3, const FirstPair form) {
+    fp_lazy_first_pair_mul(x0, x1, x2, x3, [&w3](const Fp<P>& d) { return fp_mul_chunk(d, w3); }, form);
 }
 template <int CL, class P>
 H2_DEV void fp_lazy_first_pair(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3, const FpChunk<CL>& w3, const bool red) {

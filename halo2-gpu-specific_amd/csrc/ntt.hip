@@ -411,8 +411,10 @@ PlanRef ntt_get_plan(DeviceCtx* ctx, uint32_t log_n, const uint64_t omega[4], hi
     // same values as chunk tables; the pair table stays for the general kernel (zero padding is a property of the call)
     auto bfly_entries = [](const NttPass& ps) { return ((1u << ps.B) >> 1) * (ps.shape.radix4 ? 2u : 1u); };
     auto chunk_entries = [](const NttPass& ps) { return ps.shape.fixed ? ((1u << ps.B) >> 1) * TW_CHUNK_FR : 0u; };
+    // ... and the values of index 0, 4, 8 .. once more as eight-chunk entries (the stage pairs before the last: TwChunk32)
+    auto chunk32_entries = [](const NttPass& ps) { return ps.shape.fixed ? TW_CHUNK32_ENTRIES * TW_CHUNK32_FR : 0u; };
     size_t total = lo_count + hi_count;
-    for (const NttPass& ps : pl->sched) total += bfly_entries(ps) + chunk_entries(ps);
+    for (const NttPass& ps : pl->sched) total += bfly_entries(ps) + chunk_entries(ps) + chunk32_entries(ps);
     H2_HIP(hipMalloc(&pl->tables, total * sizeof(Fr)));
     pl->table_bytes = total * sizeof(Fr);
     pl->tw_lo = pl->tables;
@@ -428,6 +430,9 @@ PlanRef ntt_get_plan(DeviceCtx* ctx, uint32_t log_n, const uint64_t omega[4], hi
         if (ps.shape.fixed) ntt_fill_pow(next, w, n >> ps.B, half, 2u, stream);
         pl->tw_chunk.push_back(ps.shape.fixed ? next : nullptr);
         next += chunk_entries(ps);
+        if (ps.shape.fixed) ntt_fill_pow(next, w, (n >> ps.B) * (half / TW_CHUNK32_ENTRIES), TW_CHUNK32_ENTRIES, 3u, stream);
+        pl->tw_chunk32.push_back(ps.shape.fixed ? next : nullptr);
+        next += chunk32_entries(ps);
         // A middle pass whose whole inter-pass twiddle set has <= 2^16 entries (pass 1 of every plan of three passes or more:
         // t_log is the first pass's width) gets it tabulated, as chunk entries in the order (rho << t_log) | K.  The pass
         // BEFORE it multiplies by them where it stores (pass_args: nx_tab / tw_applied): there a tile reads consecutive
@@ -491,6 +496,7 @@ static PassArgs pass_args(const NttPlan* pl, size_t p, const Fr* const* srcs, Fr
     }
     a.tw_bfly = pl->tw_bfly[p];
     a.tw_chunk = pl->tw_chunk[p];
+    a.tw_chunk32 = pl->tw_chunk32[p];
     a.tw_lo = pl->tw_lo;
     a.tw_hi = pl->tw_hi;
     a.tw_applied = pl->tw_inter[p] != nullptr;

@@ -61,6 +61,7 @@ struct NttPlan {
     // product fp_mul_const, for the passes with shape.radix4 (transforms >= 2^18)
     std::vector<const Fr*> tw_bfly;
     std::vector<const Fr*> tw_chunk;   // per pass of the fixed geometry: tw_bfly's values as chunk tables (fp_mul_chunk), else nullptr
+    std::vector<const Fr*> tw_chunk32; // ... and those of index 0, 4, 8 .. as eight-chunk entries (TwChunk32, 8 KiB), else nullptr
     // per pass: its full inter-pass twiddle set as chunk tables, w^(rho K S) at [(rho << t_log) | K] (the middle pass of a plan
     // of three passes or more), else nullptr.  The pass BEFORE it multiplies by them at its store (PassArgs::nx_tab).
     std::vector<const Fr*> tw_inter;

@@ -29,11 +29,13 @@
 namespace h2 {
 
 // ---------------------------------------------------------------- table generation
-// A twiddle table in one of three forms.  pair = 0: out[i] = w, Montgomery form (the operand of fp_mul / fp_mul_wide).
+// A twiddle table in one of four forms.  pair = 0: out[i] = w, Montgomery form (the operand of fp_mul / fp_mul_wide).
 // pair = 1: out[2 i] = w as a PLAIN residue, out[2 i + 1] = floor(w 2^256 / r) -- the operands of fp_mul_const (field.hpp), the
 // constant-operand product the passes with CW use for every twiddle they read from a table.
 // pair = 2: entry i (sizeof(TwChunk) bytes) = w's chunk residues, limb-major -- the operand of fp_mul_chunk, which the fixed
 // pass (k_ntt_pass8) uses for its butterfly twiddles.
+// pair = 3: entry i (sizeof(TwChunk32) bytes) = w's eight residues w 2^(32 j) 2^64 mod r, limb-major -- the operand of
+// fp_mul_chunk_planes, which k_ntt_pass8 uses for its wave-uniform twiddles.
 __device__ __forceinline__ void tw_store(Fr* out, uint32_t i, const Fr& w_mont, uint32_t pair) {
     if (!pair) {
         fp_store(out + i, w_mont);
@@ -45,6 +47,14 @@ __device__ __forceinline__ void tw_store(Fr* out, uint32_t i, const Fr& w_mont, 
         uint4* const q = reinterpret_cast<uint4*>(out) + (size_t)i * TW_CHUNK_Q;
 #pragma unroll
         for (uint32_t k = 0; k < TW_CHUNK_Q; k++) q[k] = make_uint4(t.w[4 * k], t.w[4 * k + 1], t.w[4 * k + 2], t.w[4 * k + 3]);
+        return;
+    }
+    if (pair == 3) {
+        TwChunk32 t;
+        fp_chunk_table(w_mont, t);
+        uint4* const q = reinterpret_cast<uint4*>(out) + (size_t)i * TW_CHUNK32_Q;
+#pragma unroll
+        for (uint32_t k = 0; k < TW_CHUNK32_Q; k++) q[k] = make_uint4(t.w[4 * k], t.w[4 * k + 1], t.w[4 * k + 2], t.w[4 * k + 3]);
         return;
     }
     Fr w, q;
@@ -471,7 +481,7 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
 //     order), i.e. unit bitrev6(l): its LDS writes are 256 B apart (8-way conflicts per lane group, as the bit-reversed
 //     writes of the unfused load phase were).
 // The first pair needs ONE butterfly twiddle (index 1 of stage 1, entry 64 of the table) before the tile's first barrier, i.e.
-// before the LDS copy of the table is ordered against its readers: every lane reads that one from the table in memory.
+// before the LDS copy of the table is ordered against its readers: that one comes from the table in memory (by scalar loads).
 // The butterfly twiddles are chunk tables (fp_mul_chunk: 88 multiply-adds per product instead of fp_mul_const's 115).  The
 // stage pairs before the last one read only the entries whose index is a multiple of 4: those 32 are in LDS, as TW_CHUNK_Q
 // planes of 16-byte words -- plane l holds limb l of the four residues of every twiddle, what one column of the product's
@@ -479,6 +489,10 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
 // pair reads all R/2 entries, every lane its own three and once per tile: those come from the table in memory (16 KiB, cache
 // resident; 384 bytes per lane next to the 256 bytes of its elements).  Tile planes 32 KiB + 4 KiB: four workgroups per CU
 // as with the pair tables -- the whole table in LDS (48 KiB) leaves three, which costs more than the shorter product gains.
+// Where every lane of a wave multiplies by the SAME twiddle -- the first stage pair's one twiddle, and all of round4(2), whose
+// twiddle index is the wave's index -- the entry is an EIGHT-chunk one (TwChunk32: 80 multiply-adds and 2 low products per
+// product) read from its 8 KiB table in memory by scalar loads, plane by plane, into scalar registers: bmul_s below.  The
+// same entries from LDS for round4(4) (16 ds_read_b128 per product instead of 8) measured slower: DESIGN.md 3.2.
 static constexpr uint32_t PASS8_TW_LDS = 32;   // entries in LDS: indices 0, 4, 8 ..
 static constexpr uint32_t PASS8_LDS = ((256u << 2) * 2 + PASS8_TW_LDS * TW_CHUNK_Q) * sizeof(uint4);
 static_assert(4 * PASS8_LDS <= 160u * 1024, "four workgroups of k_ntt_pass8 per CU");
@@ -510,6 +524,18 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
         return t;
     };
     auto bmul = [](const Fr& x, const Tw& t) __attribute__((always_inline)) -> Fr { return fp_mul_chunk(x, t); };
+    // x * (twiddle i) for a WAVE-UNIFORM i, a multiple of 4: the same eight-chunk entry from the table in memory through the
+    // constant address space, i.e. by scalar loads into scalar registers, which the multiply-adds read as they read the
+    // modulus limbs -- no vector register and no LDS read for the twiddle.  `i` has to be a scalar value (from `wave`).
+    typedef const __attribute__((address_space(4))) uint32_t* TwScalar;
+    const TwScalar tw32_s = (TwScalar)reinterpret_cast<const uint32_t*>(a.tw_chunk32);
+    auto bmul_s = [&](const Fr& x, const uint32_t i) __attribute__((always_inline)) -> Fr {
+        const TwScalar e = tw32_s + (i >> 2) * (uint32_t)(sizeof(TwChunk32) / sizeof(uint32_t));
+        return fp_mul_chunk_planes<1, true>(x, [e](uint32_t (&w)[8], const uint32_t c) __attribute__((always_inline)) {
+#pragma unroll
+            for (uint32_t k = 0; k < 8; k++) w[k] = e[8 * c + k];
+        });
+    };
     // stages s and s + 1 on the rows p, p + h, p + 2h, p + 3h (h = 2^s) of one column, in registers, twiddle index r = p mod h:
     // the butterflies of k_ntt_pass's round4 on the same residues; x0 .. x3 come back in row order
     // In two halves, so that the last stage pair can start the loads of what follows it between them.  unit4_mul: everything
@@ -525,12 +551,18 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     auto unit4_mul = [&](Fr& x0, Fr& x1, Fr& x2, Fr& x3, const uint32_t s, const uint32_t r, const bool unit) __attribute__((always_inline)) {
         const uint32_t h = 1u << s;
         const bool mem = s == B - 2;   // the last stage pair: twiddles of every index
+        const bool uni = s == 2;       // r = tid >> 6 is the wave's index (round4 passes `wave`): scalar twiddles
         x0 = fp_lazy_red2p(x0);
         Fr y2, n3;
         if (!unit) {
-            const Tw wa = tw_get(r << (B - 1 - s), mem);
-            x1 = bmul(x1, wa);
-            x3 = bmul(x3, wa);
+            if (uni) {
+                x1 = bmul_s(x1, r << (B - 1 - s));
+                x3 = bmul_s(x3, r << (B - 1 - s));
+            } else {
+                const Tw wa = tw_get(r << (B - 1 - s), mem);
+                x1 = bmul(x1, wa);
+                x3 = bmul(x3, wa);
+            }
             y2 = fp_lazy_add(x2, x3);            // below 5p + 2^-29 p
             n3 = fp_lazy_sub_from4p(x3, x2);     // in (0, 5p + 2^-29 p)
         } else {
@@ -541,8 +573,13 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
             n3 = fp_lazy_sub(x3, x2);            // in (0, 4p)
         }
         const Fr y0 = fp_lazy_add_red(x0, x1), y1 = fp_lazy_sub_red(x0, x1);
-        y2 = unit ? fp_lazy_red2p(y2) : bmul(y2, tw_get(r << (B - 2 - s), mem));
-        n3 = bmul(n3, tw_get((r + h) << (B - 2 - s), mem));
+        if (uni) {
+            y2 = unit ? fp_lazy_red2p(y2) : bmul_s(y2, r << (B - 2 - s));
+            n3 = bmul_s(n3, (r + h) << (B - 2 - s));
+        } else {
+            y2 = unit ? fp_lazy_red2p(y2) : bmul(y2, tw_get(r << (B - 2 - s), mem));
+            n3 = bmul(n3, tw_get((r + h) << (B - 2 - s), mem));
+        }
         x0 = y0;
         x1 = y1;
         x2 = y2;
@@ -576,10 +613,15 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
         unit = s == 0 || (by_r && r == 0);
     };
     const uint32_t tid = threadIdx.x;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (provably uniform: a scalar register)
     auto round4 = [&](const uint32_t s) __attribute__((always_inline)) {
         uint32_t i0, r;
         bool unit;
         unit_of(tid, s, i0, r, unit);
+        if (s == 2) {   // r = tid >> 6: the same value from the scalar register, so that the twiddles' addresses are scalar
+            r = wave;
+            unit = wave == 0;
+        }
         const uint32_t step = (1u << s) << log_c;
         Fr x0 = lds_get(t_lo, t_hi, i0), x1 = lds_get(t_lo, t_hi, i0 + step);
         Fr x2 = lds_get(t_lo, t_hi, i0 + 2 * step), x3 = lds_get(t_lo, t_hi, i0 + 3 * step);
@@ -602,10 +644,8 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     static_assert(PASS8_TW_LDS * TW_CHUNK_Q == 256, "one word of the LDS copy per lane");
     const uint4 w_fill = tw_tab[(size_t)(tid / TW_CHUNK_Q) * 4 * TW_CHUNK_Q + tid % TW_CHUNK_Q];
 
-    // stage 1's twiddle of index 1 for the first stage pair, straight from the table (wave-uniform address)
-    Tw tw64;
-#pragma unroll
-    for (uint32_t k = 0; k < TW_CHUNK_Q; k++) tw_unpack(tw64, k, tw_tab[(R >> 2) * TW_CHUNK_Q + k]);
+    // (stage 1's twiddle of index 1 for the first stage pair, entry R / 4, is read from the table in memory as the product
+    // runs: bmul_s)
 
     constexpr uint32_t NE = 4;
     {
@@ -706,7 +746,7 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
             // place of the reducing ones (FIRST_PAIR_CANON).  Only with pre3, which leaves every third element as loaded next to
             // two products below 2p, the operands are reduced as before.  Wave-uniform.
             const FirstPair form = (a.nprev != 0 || pre_scale) ? FIRST_PAIR_2P : (a.has_pre3 ? FIRST_PAIR_4P : FIRST_PAIR_CANON);
-            fp_lazy_first_pair_of(x[0], x[2], x[1], x[3], tw64, form);
+            fp_lazy_first_pair_mul(x[0], x[2], x[1], x[3], [&](const Fr& d) __attribute__((always_inline)) { return bmul_s(d, R >> 2); }, form);
             lds_put(t_lo, t_hi, i0, x[0]);
             lds_put(t_lo, t_hi, i0 + 2 * C, x[1]);
             lds_put(t_lo, t_hi, i0 + C, x[2]);

@@ -8,15 +8,24 @@ namespace h2 {
 static constexpr int NTT_BATCH_MAX = 16;  // vectors per launch of a batched transform (pointers travel in the kernel arguments)
 static constexpr int LO_BITS = 12;  // two-level twiddle tables: w^e = lo[e & 4095] * hi[e >> 12]
 
-using TwChunk = FpChunk<2>;   // four chunks of 64 bits (eight of 32 bits measured slower: DESIGN.md)
+using TwChunk = FpChunk<2>;   // four chunks of 64 bits: the entries a lane reads for itself, from LDS or from memory
 static constexpr uint32_t TW_CHUNK_FR = sizeof(TwChunk) / sizeof(Fr);   // table elements per entry
 static constexpr uint32_t TW_CHUNK_Q = sizeof(TwChunk) / sizeof(uint4);  // 16-byte words per entry
+// Eight chunks of 32 bits (80 multiply-adds and 2 low products per product instead of 88 and 3) for the twiddles of k_ntt_pass8
+// that are the same for a whole wave (its first stage pair, the round of stages 2 and 3): the entries of index 0, 4, 8 .. in a
+// table of their own, read by scalar loads, plane by plane, into scalar registers (fp_mul_chunk_planes).  The same form from
+// LDS for the per-lane twiddles of stages 4 and 5 measured slower, the whole table in LDS much slower.
+using TwChunk32 = FpChunk<1>;
+static constexpr uint32_t TW_CHUNK32_ENTRIES = 32;
+static constexpr uint32_t TW_CHUNK32_FR = sizeof(TwChunk32) / sizeof(Fr);
+static constexpr uint32_t TW_CHUNK32_Q = sizeof(TwChunk32) / sizeof(uint4);
 
 struct PassArgs {
     const Fr* in;
     Fr* out;
     const Fr* tw_bfly;  // R/2 entries: (w^(n/R))^e   (CW kernels: R/2 PAIRS -- plain value, quotient; see tw_store)
     const Fr* tw_chunk;  // k_ntt_pass8: the same R/2 values as chunk tables (tw_store's third form)
+    const Fr* tw_chunk32;  // k_ntt_pass8: the values of index 0, 4, 8 .. as eight-chunk entries (tw_store's fourth form)
     const Fr* tw_lo;    // min(n, 4096) entries: w^i
     const Fr* tw_hi;    // n >> 12 entries: w^(i << 12)   (unused when n <= 4096)
     const Fr* tw_direct;  // non-null (a last pass): inter-pass twiddle = tw_direct[(K << B) | rho], its load order (no generation multiply)
@@ -67,7 +76,7 @@ enum NttKernel : uint32_t {
 // a.B / a.log_c.  `device`: the current one (the LDS limit of the general kernels is raised once per device: 9-bit passes).
 void ntt_pass_launch(int device, NttKernel kernel, const PassArgs& a, uint32_t cnt, uint32_t threads, hipStream_t stream);
 
-// Table fillers: one kernel each on `stream` (none for an empty table).  `form`: tw_store's `pair` (ntt_pass.hip).
+// Table fillers: one kernel each on `stream` (none for an empty table).  `form`: tw_store's `pair` (ntt_pass.hip), 0 .. 3.
 void ntt_fill_pow(Fr* out, const Fr& base, uint32_t mul, uint32_t count, uint32_t form, hipStream_t stream);  // out[i] = base^(i mul)
 // out[(rho << kbits) | K] = base^((rho K << s_log) mod n): the complete inter-pass twiddle set of a middle pass (form 2:
 // sizeof(TwChunk) bytes per entry)

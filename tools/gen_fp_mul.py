@@ -28,7 +28,8 @@ FIELDS = {
 }
 W = (1 << 32) - 1
 TOP = (1 << 30) - 1  # limb 7 of an input < 2^254
-CHUNK_LIMBS = (2,)  # the chunk widths of schedule_chunk the header holds, in 32-bit limbs (1: measured slower in the NTT)
+CHUNK_LIMBS = (2,)  # the chunk widths of schedule_chunk the header holds as fp_mul_chunk_dev<P, CL>(a, whole entry)
+PLANE_FIELDS = ("FrParams",)  # fields whose eight-chunk product (chunk width 1) the header holds plane by plane: lower_planes
 
 
 def schedule(p, square=False, dual=False, wide=False):
@@ -329,12 +330,81 @@ def _schedule_block(terms):
     return instrs
 
 
+_TW = _re.compile(r"t\.w\[(\d+)\]")
+
+
+def lower_planes(lines, cls):
+    """The eight-chunk schedule (schedule_chunk(p, 1)) with its table entry taken PLANE BY PLANE.  Column c <= 7 of that sweep
+    is sum_j a_j * (limb c of T_j): it reads the eight words t.w[8 c .. 8 c + 7] -- one limb-major plane -- and no other table
+    word, and `lower` already cuts its blocks at the column boundaries (the m_i line and the shift end a run).  So the entry
+    never has to be live as a whole: ("fetch", c) at the top of column c is where the caller's fetch requests plane c + AH
+    (AH = 1 or 2 planes ahead; planes 0 .. AH - 1 before column 0), and the table operands are tp[c][k] = limb c of T_k.
+    cls "V": the words are vector registers (a per-lane entry: planes read from LDS between the blocks).
+    cls "S": the words are scalar registers, the operand class of the modulus limbs (a wave-uniform entry: planes read by
+    scalar loads).  A VOP3 instruction of gfx9 reads at most ONE scalar register or constant: every multiply-add here has
+    its first factor (a limb of x, or m_i) in a vector register, which check_planes asserts; the carry rotation and the
+    hazard distance are those of `lower` unchanged."""
+    assert cls in ("V", "S")
+    out = []
+    for item in lower(lines):
+        if item[0] == "c":
+            out.append(item)
+            g = _re.match(r"// column (\d+):", item[1])
+            if g and int(g.group(1)) <= 7:
+                out.append(("fetch", int(g.group(1))))
+            continue
+        instrs = []
+        for ins in item[1]:
+            if ins[0] == "mad":
+                g = _TW.fullmatch(ins[2])
+                if g:
+                    n = int(g.group(1))
+                    ins = ("mad", ins[1], "tp[%d][%d]" % (n // 8, n % 8), cls, ins[4])
+            instrs.append(ins)
+        out.append(("asm", instrs))
+    check_planes(out)
+    return out
+
+
+def check_planes(lowered, ahead=(1, 2)):
+    """column c's blocks read plane c only; with the fetches `ahead` planes early every word is requested before it is read
+    and at most ahead + 1 planes are live; no multiply-add has two scalar operands"""
+    for ah in ahead:
+        fetched, column = set(), None
+        for item in lowered:
+            if item[0] == "fetch":
+                column = item[1]
+                fetched |= set(range(ah)) if column == 0 else set()
+                if column + ah <= 7:
+                    fetched.add(column + ah)
+                fetched -= set(range(column))       # the planes of finished columns are dead
+                assert len(fetched) <= ah + 1
+            elif item[0] == "asm":
+                for ins in item[1]:
+                    if ins[0] != "mad":
+                        continue
+                    assert not ins[1].startswith(("tp[", "P::")), "the first factor is a vector register"
+                    g = _re.fullmatch(r"tp\[(\d)\]\[(\d)\]", ins[2])
+                    if g:
+                        assert int(g.group(1)) == column and column in fetched, "a column reads its own plane, fetched before"
+                    else:
+                        assert ins[3] == "S" and ins[2].startswith("P::MOD["), ins
+
+
 def emit(lowered, indent="    "):
     """C++ text of a lowered schedule"""
     text = []
     for item in lowered:
         if item[0] == "c":
             text.append(indent + item[1] if item[1] else "")
+            continue
+        if item[0] == "fetch":   # (lower_planes) the caller requests plane c + AH here; the first AH planes before column 0
+            c = item[1]
+            if c == 0:
+                text.append(indent + "fetch(tp[0], 0);")
+                text.append(indent + "if constexpr (AH > 1) fetch(tp[1], 1);")
+            if c + 1 <= 7:   # (& 7: the index of a discarded branch still has to be in range)
+                text.append(indent + "if constexpr (%d + AH <= 7) fetch(tp[(%d + AH) & 7], (%d + AH) & 7);" % (c, c, c))
             continue
         names, inputs, body = {}, [], []
 
@@ -481,7 +551,32 @@ def main():
             out.append("}")
             out.append("")
             print(name, "chunk", cl, {k: v for k, v in stats.items() if k != "column_max"})
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "halo2-gpu-specific_amd", "csrc", "fp_mul_gen.hpp")
+        # the eight-chunk product with the entry taken plane by plane (lower_planes), words in vector / scalar registers
+        if name in PLANE_FIELDS:
+            lines, stats = schedule_chunk(p, 1)
+            for cls, fn in (("V", "fp_mul_chunk1_planes_dev"), ("S", "fp_mul_chunk1_splanes_dev")):
+                out.append("// %s by a constant tabulated in 8 chunks of 32 bits, the entry read PLANE BY PLANE: fetch(w, c) fills w[k] with limb c of"
+                           % name)
+                out.append("// w 2^(32 k + 64) mod p (k = 0..7), %s; it is called for plane c + AH at the top of column c (AH = 1 or 2; the first"
+                           % ("vector registers" if cls == "V" else "SCALAR registers (one scalar operand per multiply-add)"))
+                out.append("// AH planes before column 0).  a < 2^256; result < p (1 + 2^-29), NOT reduced: %d bare multiply-adds, %d carry-setting,"
+                           % (stats["free"], stats["set"]))
+                out.append("// %d carry-accumulating, 2 low products" % stats["acc"])
+                out.append("template <int AH, class Fetch>")
+                out.append("__device__ __forceinline__ Fp<%s> %s(const Fp<%s>& a, Fetch&& fetch) {" % (name, fn, name))
+                out.append("    static_assert(AH == 1 || AH == 2, \"planes in flight ahead of the column that is summed\");")
+                out.append("    using P = %s;" % name)
+                out.append("    Fp<P> r;")
+                out.append("    uint64_t lo = 0, cy0, cy1, cy2;")
+                out.append("    uint32_t hi = 0;")
+                out.append("    uint32_t tp[8][8];")
+                out += emit(lower_planes(lines, cls))
+                out.append("    (void)cy0; (void)cy1; (void)cy2; (void)hi;")
+                out.append("    return r;")
+                out.append("}")
+                out.append("")
+            print(name, "chunk planes", {k: v for k, v in stats.items() if k != "column_max"})
+    path =os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "halo2-gpu-specific_amd", "csrc", "fp_mul_gen.hpp")
     with open(path, "w") as f:
         f.write("\n".join(out))
 
