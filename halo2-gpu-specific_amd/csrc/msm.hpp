@@ -1,4 +1,5 @@
-// msm.hpp -- MSM drivers (msm.hip)
+// msm.hpp -- the MSM as the rest of the library calls it: the drivers (msm.hip), the launch list (msm_kernels.hip) and the
+// shifted-base tables (msm_table.hip)
 #pragma once
 #include "common.hpp"
 
@@ -18,7 +19,7 @@ int msm_device_batch_ex(DeviceCtx* ctx, const Fr* const* d_scalars, const uint64
                         const uint32_t* bits_each, size_t count, const uint64_t* d_bases, size_t n, uint32_t max_bits,
                         void* d_scratch, size_t scratch_bytes, uint64_t* out_xyz, hipStream_t stream);
 size_t msm_batch_scratch_bytes(size_t n, uint32_t max_bits, size_t count);
-// shifted-base table of a device-resident base set (msm.hip "shifted-base tables"): built once, used by every
+// shifted-base table of a device-resident base set (msm_table.hip): built once, used by every
 // msm_device* call whose bases lie inside [d_bases, d_bases + n)
 int bases_precompute(const uint64_t* d_bases, size_t n, uint32_t digits, hipStream_t stream);
 int bases_forget(const uint64_t* d_bases);

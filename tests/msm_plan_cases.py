@@ -10,6 +10,8 @@ has to populate.  Three references, none of which shares code with another:
 """
 import collections
 import ctypes
+import json
+import os
 import random
 
 import numpy as np
@@ -22,7 +24,7 @@ FINISH = ("quads", "lanes")                        # H2_MSM_FINISH_*
 REDUCE = ("groups", "planes")                      # H2_MSM_REDUCE_*
 L_ENUM_COUNTS = {"H2_MSM_FORM_COUNT": 3, "H2_MSM_PART_COUNT": 3, "H2_MSM_FINISH_COUNT": 2, "H2_MSM_REDUCE_COUNT": 2}
 
-FINISH_SERIAL, MID_MAX, HEAVY_SPLIT, SKEW_ROUNDS = 32, 512, 64, 4   # csrc/msm.hip
+FINISH_SERIAL, MID_MAX, HEAVY_SPLIT, SKEW_ROUNDS = 32, 512, 64, 4   # csrc/msm_plan.hpp, csrc/msm_kernels.hip
 SIGN_BIT, BLOCK_INDEX0, BLOCK_ROWS, NO_PARTITION = 0x80000000, 0x40000000, 256, 0xFFFFFFFF
 HOT_SAMPLES, HOT_MIN = 64, 16
 SORT_CHECK_MAX_N = 1 << 15   # (2^13 would do for the digits; the skewed sort needs 2^15 rows to happen at all)
@@ -48,6 +50,32 @@ def last_launches(L):
     buf = (LaunchInfo * max(count, 1))()
     assert L.h2_msm_last_launches(ctypes.addressof(buf), count) == count
     return [buf[i].as_dict() for i in range(count)]
+
+
+RECORD_FIELDS = [k for k in _U32 + _U64 if k != "scratch"]   # what of a record is a function of the call's inputs
+GOLDEN_RECORDS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "msm_launch_records.json")
+_GOLDEN = {}
+
+
+def golden_records():
+    """tests/golden/msm_launch_records.json (golden/gen_msm_launch_records.py, recorded on an MI355X):
+    (child's name or None, row name) -> the row's inputs, knobs and launch records"""
+    if not _GOLDEN:
+        with open(GOLDEN_RECORDS) as f:
+            rows = json.load(f)["rows"]
+        _GOLDEN.update({(e["child"], e["name"]): e for e in rows})
+        assert len(_GOLDEN) == len(rows), "two recorded rows share a name"
+    return _GOLDEN
+
+
+def check_golden(child, row, recs):
+    """the launches of one row are the recorded ones, field by field (all but the scratch address)"""
+    want = golden_records()[(child, row.name)]["launches"]
+    got = [{k: r[k] for k in RECORD_FIELDS} for r in recs]
+    assert len(got) == len(want), "%d launches, %d recorded" % (len(got), len(want))
+    for i, (g, w) in enumerate(zip(got, want)):
+        diff = {k: (g[k], w[k]) for k in RECORD_FIELDS if g[k] != w[k]}
+        assert not diff, "launch %d differs from the recorded one (got, recorded): %s" % (i, diff)
 
 
 def branches(rec):

@@ -2,8 +2,8 @@
 (and, for n <= 256, the sum in Python integers), its launch record against what the row expects, and -- for rows that are one
 launch -- the partition bases, bucket starts, heavy count and sorted entries the launch left in the scratch against the
 digits recoded on the host.  tests/test_gpu_msm_plans.py imports the Runner; run as a script with the name of one of
-msm_plan_cases.CHILDREN (one knob setting per child process: most H2_MSM_* knobs are read once per process) it runs that
-setting's rows and prints the branches their records show."""
+msm_plan_cases.CHILDREN (one knob setting per child process, set before the library is loaded) it runs that setting's rows,
+compares their records with the recorded ones and prints the branches they show."""
 import ctypes
 import os
 import sys
@@ -189,9 +189,10 @@ class Runner:
             mc.check_sort(rec, starts, entries, mc.recode(cols, rec, table_n if rec["form"] == 1 else 0))
         return found
 
-    def run_rows(self, rows):
+    def run_rows(self, rows, child=None):
         for row in rows:
             recs, found = self.run(row)
+            mc.check_golden(child, row, recs)
             print("ROW %s: %s %s" % (row.name, sorted(set().union(*[mc.branches(r) for r in recs])), sorted(found)), flush=True)
         self.forget()
 
@@ -205,7 +206,7 @@ def main():
         assert os.environ.get(k) == v, "start this child with %s=%s" % (k, v)
     r = Runner(Oracle.get())
     try:
-        r.run_rows(rows)
+        r.run_rows(rows, child=name)
     finally:
         r.forget()
     print("BRANCHES %s" % " ".join(sorted(r.branches | {"class:" + c for c in r.classes})), flush=True)

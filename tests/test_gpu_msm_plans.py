@@ -1,6 +1,7 @@
-"""Every branch of the MSM launcher (csrc/msm.hip, msm_launch) at small pinned shapes, with evidence that it ran.
+"""Every branch of the MSM launcher (csrc/msm_plan.cpp msm_plan_launch, csrc/msm_kernels.hip msm_enqueue) at small pinned shapes,
+with evidence that it ran.
 
-One call of msm_launch picks a form (windowed, shifted-base table, fused group), a partition (k_partition<2048>, <16384>, the
+One planned launch picks a form (windowed, shifted-base table, fused group), a partition (k_partition<2048>, <16384>, the
 two-level k_part_a / k_part_b), a k_bucket_sort path per partition (plain, staged in LDS, skewed, the dominant value's
 short cut), k_acc_slice<4> or <5>, k_finish or k_finish_lane with four classes of bucket behind it, and k_reduce or the bit
 planes.  Part of that depends on the sampled scalars, so it cannot be told from the sizes: the launcher records what it
@@ -16,7 +17,9 @@ least one per form -- also with sum s_i P_i in Python integers (msm_plan_cases.i
   (c) single-launch rows of n <= 2^15: the scalars' digits, recoded in Python integers by the rule k_digits documents, give
       every bucket's size and its (row or table index, sign) entries as a set: `starts` and `sorted` are exactly that;
   (d) the branches of this process's rows are every branch default knobs reach at these sizes, and every knob child (one
-      fresh process per setting, one after another, compared with the oracle inside the child) reports the branch it is for.
+      fresh process per setting, one after another, compared with the oracle inside the child) reports the branch it is for;
+  (e) every row's launch records, but for the scratch address, equal tests/golden/msm_launch_records.json, recorded on an
+      MI355X before the launcher was split into plan and enqueue (the children compare theirs in the child).
 
 Rows (msm_plan_cases.WINDOWED_ROWS / TABLE_ROWS / FUSED_ROWS / CHILDREN; DESIGN.md's MSM section lists them with the wall
 clock).  Distributions: uniform, one value, 7/8 one value over whole 256-row blocks and ragged runs, 1/16 non-zero, three
@@ -82,6 +85,7 @@ def _run(runner, row):
     import msm_plan_worker  # noqa: F401
 
     recs, found = runner.run(row)
+    mc.check_golden(None, row, recs)
     SEEN[row.name] = (set().union(*[mc.branches(r) for r in recs]), found)
     print(row.name, "->", sorted(SEEN[row.name][0]), sorted(found))
 

@@ -1,5 +1,5 @@
 """GPU parity of the MSM over a shifted-base table (h2_dev_bases_precompute: all digits of a scalar share one bucket
-set, msm.hip) against the CPU oracle's `best_multiexp` (arithmetic.rs:20-108 restated) -- same group element for every
+set, msm_table.hip) against the CPU oracle's `best_multiexp` (arithmetic.rs:20-108 restated) -- same group element for every
 scalar distribution, bound, digit count, sub-range and batch shape the windowed pipeline is tested on."""
 import ctypes
 import os
