@@ -10,6 +10,7 @@
 #include "check.hpp"
 #include "common.hpp"
 #include "evalh.hpp"
+#include "evalh_desc.hpp"
 #include "g1mul.hpp"
 #include "g1ntt.hpp"
 #include "g1util.hpp"
@@ -301,10 +302,6 @@ int host_ntt(HostCall& call, HostResult& res, const Fr* src, Fr* d_a, const uint
     return res.write(d_a, call.stream);
 }
 const char* const BAD_LOG_N = "log_n exceeds the 2-adicity of Fr (S = 28)";
-
-void fr_to_u64x4(const Fr& v, uint64_t out[4]) {
-    for (int i = 0; i < 4; i++) out[i] = (uint64_t)v.l[2 * i] | ((uint64_t)v.l[2 * i + 1] << 32);
-}
 
 }  // namespace
 
@@ -1764,11 +1761,9 @@ uint64_t h2_evalh_generated_launches(void) { return evalh_generated_launches(); 
 // ------------------------------------------------------------------ evaluate_h
 // (the copy back is inside evalh_host / evalh_host_coeffs: the prefault of `values` starts once the descriptor is known to be
 // sound, runs under the wait for a slot, and is joined just before that call)
-static bool evalh_bad_sizes(const h2_evalh_desc* desc) { return desc->extended_k < desc->k || desc->extended_k > 28; }
-
 int h2_evaluate_h(const h2_evalh_desc* desc, uint64_t* values) {
     if (!desc || !values) return bad("h2_evaluate_h: null argument");
-    if (evalh_bad_sizes(desc)) return bad("h2_evaluate_h: bad k / extended_k");
+    if (const char* msg = evalh_validate(desc, "h2_evaluate_h", EVALH_HOST_EXTENDED)) return bad(msg);
     return guarded([&] {
         HostResult res(values, (size_t)1 << desc->extended_k);
         HostCall call;
@@ -1778,7 +1773,7 @@ int h2_evaluate_h(const h2_evalh_desc* desc, uint64_t* values) {
 
 int h2_evaluate_h_coeff(const h2_evalh_desc* desc, uint64_t* values) {
     if (!desc || !values) return bad("h2_evaluate_h_coeff: null argument");
-    if (evalh_bad_sizes(desc)) return bad("h2_evaluate_h_coeff: bad k / extended_k");
+    if (const char* msg = evalh_validate(desc, "h2_evaluate_h_coeff", EVALH_HOST_COEFF)) return bad(msg);
     return guarded([&] {
         HostResult res(values, (size_t)1 << desc->extended_k);
         return evalh_host_coeffs(desc, res.handed_over());      // (leases its devices itself)
@@ -1798,7 +1793,7 @@ int h2_quotient_poly_coeff(const h2_evalh_desc* desc, const uint64_t* t_evaluati
                            const uint64_t extended_ifft_divisor[4], uint64_t* out, size_t out_len) {
     if (!desc || !t_evaluations || !t_len || !g_coset || !g_coset_inv || !extended_omega_inv || !extended_ifft_divisor || !out)
         return bad("h2_quotient_poly_coeff: null argument");
-    if (evalh_bad_sizes(desc)) return bad("h2_quotient_poly_coeff: bad k / extended_k");
+    if (const char* msg = evalh_validate(desc, "h2_quotient_poly_coeff", EVALH_HOST_COEFF)) return bad(msg);
     const size_t size = (size_t)1 << desc->extended_k;
     if (out_len > size) return bad("h2_quotient_poly_coeff: out_len exceeds the extended domain");
     if (size % t_len) return bad("h2_quotient_poly_coeff: t_len does not divide the extended domain");

@@ -244,30 +244,7 @@ int check_gates_launch(DeviceCtx* ctx, const h2_evalh_desc* d, const uint32_t* d
     // the interpreter's work space is the library's (as h2_dev_evaluate_h's): per device, under its lock
     std::lock_guard<std::mutex> g(ctx->mu);
     char* block = (char*)ctx->evalh_scratch.get(align256(need) + inter_bytes);
-    Arena ar;
-    ar.dev = block;
-    EvalhProgram p{};
-    p.constants = (const Fr*)ar.put(d->constants, (size_t)d->n_constants * 4);
-    p.rotations = ar.put(d->rotations, d->n_rotations);
-    p.calcs = ar.put(d->calculations, d->n_calculations);
-    p.value_parts = ar.put(d->value_parts, d->n_value_parts);
-    p.fixed = (const Fr* const*)ar.put(d->fixed, d->n_fixed);
-    p.advice = (const Fr* const*)ar.put(d->advice, d->n_advice);
-    p.instance = (const Fr* const*)ar.put(d->instance, d->n_instance);
-    if (ar.off > need) {
-        set_last_error("h2_dev_check_gates: internal staging overflow");
-        return H2_ERR_INVALID;
-    }
-    H2_HIP(hipMemcpyAsync(block, ar.host.data(), ar.off, hipMemcpyHostToDevice, stream));
-    H2_HIP(hipStreamSynchronize(stream));  // the staging vector dies with this frame
-    p.n_calcs = d->n_calculations;
-    p.n_value_parts = d->n_value_parts;
-    p.extended_k = d->k;
-    p.rot_scale = 1;
-    p.y = fr_from_u64x4(d->y);
-    p.beta = fr_from_u64x4(d->beta);
-    p.gamma = fr_from_u64x4(d->gamma);
-    p.theta = fr_from_u64x4(d->theta);
+    const EvalhProgram p = evalh_stage_program(d, block, need, stream);   // (a gate program: its lookup and shuffle parts are empty)
     hipLaunchKernelGGL(k_check_gate_rows, dim3(blocks), dim3(threads), 0, stream, p, (Fr*)(block + align256(need)), d_rows,
                        (const unsigned long long*)d_row_count, (uint32_t)H2_CHECK_GATE | circuit << 8,
                        (unsigned long long*)d_count, d_records, (unsigned long long)cap);

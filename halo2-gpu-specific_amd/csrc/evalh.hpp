@@ -1,4 +1,4 @@
-// evalh.hpp -- evaluate_h drivers (evalh.hip)
+// evalh.hpp -- evaluate_h: the drivers (evalh.hip), the generated kernels' plans (evalh_plan.hip), the interpreter (evalh_interp.hip)
 #pragma once
 #include <functional>
 
@@ -6,7 +6,8 @@
 #include "evalh_gen.hpp"
 
 namespace h2 {
-// column pointers inside `d` are device pointers; the descriptor and its program arrays are host memory
+// column pointers inside `d` are device pointers; the descriptor and its program arrays are host memory.  Validates `d`
+// (evalh_desc.hpp, the device form); the two host drivers below take a descriptor their caller has validated in its form.
 int evalh_device(DeviceCtx* ctx, const h2_evalh_desc* d, Fr* d_values, hipStream_t stream);
 // everything in host memory
 int evalh_host(DeviceCtx* ctx, const h2_evalh_desc* d, uint64_t* values);
@@ -21,7 +22,7 @@ int evalh_host_coeffs(const h2_evalh_desc* d, uint64_t* values, const EvalhFinis
 // the devices evalh_host_coeffs would deal the cosets of this descriptor over
 uint32_t evalh_host_workers(const h2_evalh_desc* d);
 
-// ---- the generated form (evalh_gen.cpp builds it, evalh.hip loads and launches it)
+// ---- the generated form (evalh_gen.cpp builds it, evalh_plan.hip loads and launches it)
 struct EvalhPlan;  // the loaded kernels of one program on one device
 // The plan for this descriptor's program on the CURRENT device: from the cache, or generated + compiled + loaded now
 // (*cached: 1 memory, 2 disk, 0 built now).  nullptr when generation is switched off (H2_EVALH_JIT=0) or unavailable (no
@@ -62,4 +63,11 @@ void evalh_gen_info(const evgen::Generated& g, h2_evalh_info* info);
 size_t evalh_fill_stage_args(const evgen::Stage& st, const h2_evalh_desc* d, Fr* values, const Fr* tw_lo, const Fr* tw_hi,
                              size_t row_begin, size_t row_end, unsigned char* buf, size_t cap);
 uint64_t evalh_generated_launches();
+
+// ---- what only the three evaluate_h files share: rows [row_begin, row_end) of a validated descriptor
+// as the plan's generated stages
+void evalh_plan_launch(DeviceCtx* ctx, const EvalhPlan* plan, const h2_evalh_desc* d, Fr* d_values, size_t row_begin, size_t row_end,
+                       hipStream_t stream);
+// on the interpreter kernels (work space: ctx->evalh_scratch, under the caller's lock)
+int evalh_interpret(DeviceCtx* ctx, const h2_evalh_desc* d, Fr* d_values, size_t row_begin, size_t row_end, hipStream_t stream);
 }  // namespace h2

@@ -18,6 +18,7 @@
 //   * a program too wide for one kernel (register budget, 4 KiB of arguments) is cut into stages that each ADD their
 //     share of the sum into `values`.
 #include "evalh_gen.hpp"
+#include "evalh_desc.hpp"
 
 #include <dirent.h>
 #include <dlfcn.h>
@@ -282,7 +283,7 @@ struct Builder {
             default: fail("unknown value source");
         }
     }
-    // one `Calculation` (evaluation.rs:95-266; the interpreter's Interp::eval in evalh.hip)
+    // one `Calculation` (evaluation.rs:95-266; the interpreter's Interp::eval in evalh_interp.hpp)
     int calculation(const h2_calculation& c, uint32_t inter_limit) {
         const int a = source(c.a, inter_limit);
         switch (c.op) {
@@ -1066,10 +1067,8 @@ void program_hash(const h2_evalh_desc* d, const Options& opt, uint8_t out[32]) {
     h.u32(d->n_value_parts);
     h.update(d->value_parts, (size_t)d->n_value_parts * sizeof(h2_value_source));
     h.u32(d->n_lookups);
-    size_t n_lookup_calcs = 0;
-    for (uint32_t t = 0; t < d->n_lookups; t++) n_lookup_calcs += 1 + 2 * (size_t)d->lookup_sets[t];
     h.update(d->lookup_sets, (size_t)d->n_lookups * 4);
-    h.update(d->lookup_calcs, n_lookup_calcs * sizeof(h2_calculation));
+    h.update(d->lookup_calcs, evalh_lookup_calc_count(d) * sizeof(h2_calculation));
     h.u32(d->n_shuffles);
     h.update(d->shuffle_calcs, 2 * (size_t)d->n_shuffles * sizeof(h2_calculation));
     h.u32(d->n_fixed);

@@ -6,7 +6,7 @@
 // result calculations, the permutation argument's shape) is compiled ONCE into one or a few straight-line kernels --
 // intermediates in registers, every argument term folded in, loads issued ahead of their use -- by hipRTC, cached by the
 // hash of the program (memory, then a private directory on disk), and launched whenever a descriptor with that program
-// arrives through h2_evaluate_h / h2_evaluate_h_coeff / h2_dev_evaluate_h (evalh.hip).  No Python, no hipcc subprocess:
+// arrives through h2_evaluate_h / h2_evaluate_h_coeff / h2_dev_evaluate_h (evalh_plan.hip).  No Python, no hipcc subprocess:
 // any host that can fill the descriptor (the Rust drop-in of INTEGRATION.md) gets the generated kernels.
 #pragma once
 #include <stdint.h>
@@ -42,7 +42,7 @@ struct ScalarRef {
     uint32_t arg;
 };
 
-// Layout of a generated kernel's single argument (passed by value; the launcher in evalh.hip fills it):
+// Layout of a generated kernel's single argument (passed by value; the launcher in evalh_plan.hip fills it):
 //   offset 0   Fr* values; const Fr* tw_lo; const Fr* tw_hi; u64 row_begin; u64 row_end; u32 extended_k; u32 rot_scale;
 //   offset 48  Fr sc[n_scalars]  (32 B each, at least one)
 //   then       const Fr* cols[n_cols]  (at least one)

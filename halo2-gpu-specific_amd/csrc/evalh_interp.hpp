@@ -1,10 +1,13 @@
-// evalh_interp.hpp -- the interpreter of an evaluate_h program (evalh.hip's fallback kernels) and the host staging
+// evalh_interp.hpp -- the interpreter of an evaluate_h program (evalh_interp.hip's fallback kernels) and the host staging
 // arena that mirrors its program arrays to the device; shared with check.hip, which runs the same program row by row.
 #pragma once
 #include <cstring>
+#include <stdexcept>
 #include <vector>
 
 #include "common.hpp"
+#include "evalh_desc.hpp"
+#include "ntt.hpp"
 
 namespace h2 {
 
@@ -88,5 +91,62 @@ struct Arena {  // bump allocator over one host staging block mirrored to one de
         return d;
     }
 };
+
+// the pointer tables the argument kernels (k_evalh_perm, k_evalh_lookup) read, staged next to the program
+struct EvalhArgTables {
+    const Fr* const* perm_z;
+    const Fr* const* perm_cols;   // the column of each permutation column (evaluation.rs:1060-1064)
+    const Fr* const* perm_sigma;
+    const Fr* const* lookup_z;
+};
+
+// Mirrors the program arrays and column pointer tables of a validated descriptor (evalh_desc.hpp) into `block` (device, `need`
+// bytes: the caller's own formula) and returns the program over them, every member but the row range filled.  With `args`
+// the argument kernels' tables follow.  The copy has been made when this returns; `stream`'s owner holds the block's lock.
+inline EvalhProgram evalh_stage_program(const h2_evalh_desc* d, char* block, size_t need, hipStream_t stream,
+                                        EvalhArgTables* args = nullptr) {
+    Arena ar;
+    ar.dev = block;
+    auto put_table = [&](uint32_t table) {
+        return (const Fr* const*)ar.put(evalh_table(d, table), evalh_table_count(d, table));
+    };
+    EvalhProgram p{};
+    p.constants = (const Fr*)ar.put(d->constants, (size_t)d->n_constants * 4);
+    p.rotations = ar.put(d->rotations, d->n_rotations);
+    p.calcs = ar.put(d->calculations, d->n_calculations);
+    p.value_parts = ar.put(d->value_parts, d->n_value_parts);
+    p.lookup_calcs = ar.put(d->lookup_calcs, evalh_lookup_calc_count(d));
+    p.lookup_sets = ar.put(d->lookup_sets, d->n_lookups);
+    p.shuffle_calcs = ar.put(d->shuffle_calcs, 2 * (size_t)d->n_shuffles);
+    p.fixed = put_table(evgen::T_FIXED);
+    p.advice = put_table(evgen::T_ADVICE);
+    p.instance = put_table(evgen::T_INSTANCE);
+    if (args) {
+        args->perm_z = put_table(evgen::T_PERM_Z);
+        args->perm_sigma = put_table(evgen::T_PERM_SIGMA);
+        std::vector<const uint64_t*> cols(d->n_perm_columns);
+        for (uint32_t j = 0; d->n_perm_sets && j < d->n_perm_columns; j++) {
+            const uint32_t ty = d->perm_col_type[j];
+            cols[j] = evalh_column(d, ty == H2_ANY_ADVICE ? evgen::T_ADVICE : (ty == H2_ANY_FIXED ? evgen::T_FIXED : evgen::T_INSTANCE),
+                                   d->perm_col_index[j]);
+        }
+        args->perm_cols = (const Fr* const*)ar.put(cols.data(), cols.size());
+        args->lookup_z = put_table(evgen::T_LOOKUP_Z);
+    }
+    if (ar.off > need) throw std::runtime_error("evaluate_h program: internal staging overflow");
+    H2_HIP(hipMemcpyAsync(block, ar.host.data(), ar.off, hipMemcpyHostToDevice, stream));
+    H2_HIP(hipStreamSynchronize(stream));  // the staging vector dies with this frame
+    p.n_calcs = d->n_calculations;
+    p.n_value_parts = d->n_value_parts;
+    p.n_lookups = d->n_lookups;
+    p.n_shuffles = d->n_shuffles;
+    p.extended_k = d->extended_k;
+    p.rot_scale = 1u << (d->extended_k - d->k);
+    p.y = fr_from_u64x4(d->y);
+    p.beta = fr_from_u64x4(d->beta);
+    p.gamma = fr_from_u64x4(d->gamma);
+    p.theta = fr_from_u64x4(d->theta);
+    return p;
+}
 
 }  // namespace h2

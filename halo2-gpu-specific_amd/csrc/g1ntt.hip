@@ -142,10 +142,6 @@ __global__ void __launch_bounds__(G1NTT_BLOCK) k_g1ntt_normalize(const XYZZ* wor
     fp_store(&out[i].y, fp_mul(a.y, t));
 }
 
-void fr_to_u64x4(const Fr& a, uint64_t out[4]) {
-    for (int i = 0; i < 4; i++) out[i] = (uint64_t)a.l[2 * i] | ((uint64_t)a.l[2 * i + 1] << 32);
-}
-
 }  // namespace
 
 size_t g1_ntt_scratch_bytes(uint32_t log_n) { return log_n > G1NTT_MAX_LOG ? 0 : sizeof(XYZZ) << log_n; }

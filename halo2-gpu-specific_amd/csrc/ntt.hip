@@ -122,6 +122,9 @@ Fr fr_from_u64x4(const uint64_t v[4]) {
     }
     return r;
 }
+void fr_to_u64x4(const Fr& v, uint64_t out[4]) {
+    for (int i = 0; i < 4; i++) out[i] = (uint64_t)v.l[2 * i] | ((uint64_t)v.l[2 * i + 1] << 32);
+}
 
 // ---------------------------------------------------------------- the table cache
 // a device block its builder owns until it is published

@@ -148,6 +148,7 @@ void ntt_run_many(DeviceCtx* ctx, NttPlan* pl, const Fr* const* srcs, Fr* const*
                   uint32_t in_len, const Fr* pre3, const Fr* post3, hipStream_t stream, const Fr* scale_tab = nullptr,
                   uint32_t scale_mode = 0);
 Fr fr_from_u64x4(const uint64_t v[4]);
+void fr_to_u64x4(const Fr& v, uint64_t out[4]);
 // h2_ntt_shape: the passes of a 2^log_n transform over 2^in_log live inputs, 7 words each into out[0 .. 7 * min(passes, cap));
 // returns the number of passes.  Reads ntt_schedule and the launcher's own zskip / kernel selectors and knobs.
 size_t ntt_shape_query(uint32_t log_n, uint32_t in_log, uint32_t* out, size_t cap);

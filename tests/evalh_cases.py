@@ -69,6 +69,38 @@ def random_case(seed, k, extended_k, oracle, n_calcs=24, with_perm=True, lookup_
     return kw
 
 
+COLUMN_TABLES = ("fixed", "advice", "instance", "perm_z", "perm_sigma", "lookup_z", "lookup_m", "shuffle_z")
+
+
+def shared_columns_case(oracle, seed=31, j=3, k=5):
+    """A descriptor that names one vector more than once -- advice[1] is advice[0] and perm_sigma[0] is fixed[0], the same
+    array objects, so the same host pointers -- in both of its forms: (coefficient vectors of 2^k, the oracle's extended cosets
+    of them, the domain).  4 cosets of 32 rows: the smallest shape at which uploading each distinct vector once and pointing
+    every slot that names it at the one device copy can go wrong."""
+    import copy
+
+    d, _ = oracle.domain(j, k)
+    kw = random_case(seed, k, d.extended_k, oracle, n_calcs=40)
+    kw["zeta"], kw["extended_omega"] = d.fr("g_coset"), d.fr("extended_omega")
+    kw["advice"] = [kw["advice"][0], kw["advice"][0], kw["advice"][2]]
+    kw["perm_sigma"] = [kw["fixed"][0]] + kw["perm_sigma"][1:]
+    forms = {}   # id(random vector) -> (its first 2^k elements as coefficients, their extended coset): one pair per object
+
+    def form(col, which):
+        if id(col) not in forms:
+            c = np.ascontiguousarray(col[:1 << k])
+            forms[id(col)] = (c, oracle.coeff_to_extended(c, d, threads=8))
+        return forms[id(col)][which]
+
+    coeff, ext = copy.copy(kw), copy.copy(kw)
+    for which, out in ((0, coeff), (1, ext)):
+        for name in COLUMN_TABLES:
+            out[name] = [form(col, which) for col in kw[name]]
+        out["l0"], out["l_last"] = form(kw["l0"], which), form(kw["l_last"], which)
+        assert out["advice"][1] is out["advice"][0] and out["perm_sigma"][0] is out["fixed"][0]
+    return coeff, ext, d
+
+
 def oracle_evaluate_h(oracle, builder):
     import ctypes
 

@@ -172,6 +172,32 @@ def test_evaluate_h_from_coefficient_forms(oracle, seed, j, k, kwargs):
     assert lib().h2_quotient_poly_coeff(ctypes.byref(b.desc), vp(t), 3, *[vp(v) for v in scal], vp(out), len(out)) != 0   # t_len must divide
 
 
+def test_columns_named_more_than_once(oracle):
+    """one vector behind several column slots (advice[1] is advice[0], perm_sigma[0] is fixed[0]: the same host pointers) at
+    the (31, 3, 5) shape, 4 cosets of 32 rows: the host drivers upload each distinct vector once and point every slot that
+    names it at the one device copy -- h2_evaluate_h on extended cosets, h2_evaluate_h_coeff and h2_quotient_poly_coeff on
+    coefficient forms, each the oracle's bits"""
+    import ctypes
+
+    from evalh_cases import shared_columns_case
+    from halo2_gpu_specific_amd._lib import lib
+
+    coeff, ext, d = shared_columns_case(oracle)
+    want = oracle_evaluate_h(oracle, ev.Builder().build(**ext))
+    assert np.array_equal(ev.evaluate_h(ev.Builder().build(**ext)), want)
+    assert np.array_equal(ev.evaluate_h_coeff(ev.Builder().build(**coeff)), want)
+    _, t = oracle.domain(3, 5)
+    divided = want.copy()
+    oracle.lib.oracle_divide_by_vanishing_poly(divided.ctypes.data, len(divided), t.ctypes.data, len(t), 8)
+    want_coeff = oracle.extended_to_coeff(divided, d, threads=8)
+    b = ev.Builder().build(**coeff)
+    out = np.empty((len(want_coeff), 4), dtype=np.uint64)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)                                  # noqa: E731
+    scal = [d.fr(name) for name in ("g_coset", "g_coset_inv", "extended_omega_inv", "extended_ifft_divisor")]
+    assert lib().h2_quotient_poly_coeff(ctypes.byref(b.desc), vp(t), len(t), *[vp(v) for v in scal], vp(out), len(out)) == 0
+    assert np.array_equal(out, want_coeff)
+
+
 def test_host_lincomb(oracle):
     """h2_lincomb (host buffers; the GWC cuda branch's shape, gwc/prover.rs:57-151): res = sum_j coeffs[j] * polys[j]"""
     import ctypes

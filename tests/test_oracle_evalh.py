@@ -2,7 +2,7 @@
 independent Python big-integer restatement on small random Evaluator programs.  CPU only."""
 import pytest
 
-from evalh_cases import oracle_evaluate_h, python_evaluate_h, random_case
+from evalh_cases import oracle_evaluate_h, python_evaluate_h, random_case, shared_columns_case
 from halo2_gpu_specific_amd import evaluation as ev
 from h2util import from_mont
 
@@ -12,6 +12,12 @@ def test_oracle_evaluate_h_matches_bigint(oracle, seed, k, ek):
     kw = random_case(seed, k, ek, oracle)
     b = ev.Builder().build(**kw)
     assert from_mont(oracle_evaluate_h(oracle, b)) == python_evaluate_h(kw)
+
+
+def test_oracle_evaluate_h_with_shared_columns(oracle):
+    # one vector behind several column slots (the device test of the upload-once drivers uses this case)
+    _, ext, _ = shared_columns_case(oracle)
+    assert from_mont(oracle_evaluate_h(oracle, ev.Builder().build(**ext))) == python_evaluate_h(ext)
 
 
 def test_oracle_evaluate_h_degenerate(oracle):
