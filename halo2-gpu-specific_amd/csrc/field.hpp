@@ -772,6 +772,53 @@ template <int CL, class P>
 H2_DEV void fp_lazy_first_pair_canon(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3, const FpChunk<CL>& w3) {
     fp_lazy_first_pair_of(x0, x1, x2, x3, w3, FIRST_PAIR_CANON);
 }
+// The LAST stage pair of a pass before the last (k_ntt_pass8, stages 6 and 7: never a unit), whose four results go to a
+// product before anything else reads them -- the store product of the same kernel or the next pass's load product, both of
+// which take any 256-bit operand -- so nothing has to come back below 2p, or even below 4p.  With e = 2^-29:
+// fp_lazy_last_pair_loose_head: x0 below 2p (reduced by the caller), x1 = x1' a product, below p (1 + e) -> y0 = x0 + x1'
+// bare, below 3p (1 + e); y1 = x0 - x1' + 2p in [p (1 - e), 4p).
+// fp_lazy_last_pair_loose_add: with the products y2 and n3 = -y3, both below p (1 + e) -> the rows y0 + y2 < 4p (1 + e),
+// y1 - n3 + p in (0, 5p), y0 - y2 + 2p in (0, 5p + 3e p), y1 + n3 < 5p (1 + e): all below 2^256 = 5.29 p, none below 4p.
+// NOT for a round inside a tile: its rows would take the x2 role, which needs a row strictly below 4p (fp_lazy_sub_from4p).
+template <class P>
+H2_DEV void fp_lazy_last_pair_loose_head(const Fp<P>& x0, const Fp<P>& x1, Fp<P>& y0, Fp<P>& y1) {
+    y0 = fp_lazy_add(x0, x1);
+    y1 = fp_lazy_sub(x0, x1);
+}
+template <class P>
+H2_DEV void fp_lazy_last_pair_loose_add(Fp<P>& x0, Fp<P>& x1, Fp<P>& x2, Fp<P>& x3) {
+    const Fp<P> y0 = x0, y1 = x1, y2 = x2, n3 = x3;
+    x0 = fp_lazy_add(y0, y2);
+    x1 = fp_lazy_sub_off<1>(y1, n3);
+    x2 = fp_lazy_sub(y0, y2);
+    x3 = fp_lazy_add(y1, n3);
+}
+// The hand-over of a pass's results to the next pass, after the store products of a pass with ST (fp_mul_chunk): the N
+// results of a lane as canonical residues.  A product is below p (1 + 2^-29), so it is at or above p about once in 2^30
+// times and only with the top limb at MOD[7] or above: one compare of the largest top limb, and the subtractions behind ONE
+// branch that is almost never taken (on any lane of the wave: a scalar branch with no exec mask to save; fp_reduce_once
+// leaves the lanes below p as they are), placed after the last product, where the table entries are dead.  Every store with
+// ST ends here, in both pass kernels, so a pass whose load finds its twiddles applied holds canonical residues
+// (FIRST_PAIR_CANON).  BRANCH = false: the subtractions with no test, 24 instructions per result, for a kernel that has no
+// scalar registers left for the branch (k_ntt_pass, radix 2).
+template <bool BRANCH = true, int N, class P>
+H2_DEV void fp_chunk_handover(Fp<P> (&y)[N]) {
+    bool rare = true;
+    if (BRANCH) {
+        uint32_t top = y[0].l[7];
+#pragma unroll
+        for (int q = 1; q < N; q++) top = y[q].l[7] > top ? y[q].l[7] : top;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(H2_PORTABLE_MUL)
+        rare = __builtin_expect(__builtin_amdgcn_ballot_w64(top >= P::MOD[7]) != 0, 0);
+#else
+        rare = top >= P::MOD[7];
+#endif
+    }
+    if (rare) {
+#pragma unroll
+        for (int q = 0; q < N; q++) y[q] = fp_reduce_once(y[q]);
+    }
+}
 // w (Montgomery form) -> the table entry fp_mul_chunk reads: T_k = w_plain 2^(32 CL k + 32 (CL + 1)) mod p, one Montgomery
 // product of the plain value by the constant 2^e R mod p each (CHUNK_POW holds e = 64, 96 .. 288).
 template <int CL, class P>

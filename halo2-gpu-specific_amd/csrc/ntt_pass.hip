@@ -166,8 +166,9 @@ __device__ __forceinline__ Fr store_twiddle(const PassArgs& a, const Fr& y, cons
         const uint4 v = q[k];
         t.w[4 * k] = v.x; t.w[4 * k + 1] = v.y; t.w[4 * k + 2] = v.z; t.w[4 * k + 3] = v.w;
     }
-    // any 256-bit y (a pass hands on values below 4p) -> below p (1 + 2^-29) < 2p: what the next pass's first butterflies
-    // take as they are (k_ntt_pass8: with no reduction, fp_lazy_first_pair; k_ntt_pass: fp_lazy_red2p hands them back)
+    // any 256-bit y (k_ntt_pass hands on values below 4p) -> below p (1 + 2^-29); fp_chunk_handover, which every store with
+    // ST ends with, makes it the canonical residue: what the next pass's first butterflies take as they are (k_ntt_pass8:
+    // bare sums, FIRST_PAIR_CANON; k_ntt_pass: fp_lazy_red2p hands them back)
     return fp_mul_chunk(y, t);
 }
 
@@ -459,6 +460,8 @@ __global__ void __launch_bounds__(512, 4) k_ntt_pass(PassArgs a) {
                 const uint32_t K_n = K_uniform | (((e >> log_c) & (R - 1)) << a.t_log);
                 if (e < total) y[q] = store_twiddle(a, y[q], (rho_n << a.nx_t_log) | K_n);
             }
+            // (radix 2: every scalar register is in use and the branch would spill two more pairs: the form without one)
+            fp_chunk_handover<RADIX4>(y);
         }
 #pragma unroll
         for (uint32_t q = 0; q < NE; q++)
@@ -502,7 +505,12 @@ static_assert(4 * PASS8_LDS <= 160u * 1024, "four workgroups of k_ntt_pass8 per 
 // Loads that depend on nothing are issued before the waits they used to follow (profiles/ntt_tile_ends_isa.txt): at the head
 // the word of the LDS table copy, the four elements and the last pass's first two table entries are one batch, waited for
 // once; at the tail the store products keep the next entry's first half in flight.
-template <bool NLAST, bool ST = false>
+// PLAIN: the plain call -- one vector (no batch), in_len the whole vector, no pre3 / post3 product, no coset scale -- with the
+// pass's position known when the kernel is compiled: <true, true> the FIRST pass (canonical data in), <true, false> a MIDDLE
+// pass whose twiddles the pass before it applied (canonical too), <false> the LAST pass with its complete table (tw_direct).
+// ntt_pass_launch chooses it (pass8_plain); every other call runs the instantiations without it.  The element loads carry no
+// mask then, so the wait in front of the LDS fill counts the loads behind it, and the branches of the other calls are gone.
+template <bool NLAST, bool ST = false, bool PLAIN = false>
 __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     static_assert(!ST || NLAST, "a last pass stores the transform's output");
     constexpr uint32_t B = 8, R = 1u << B, log_c = 2, C = 1u << log_c;
@@ -572,7 +580,15 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
             y2 = fp_lazy_add(x2, x3);            // below 4p
             n3 = fp_lazy_sub(x3, x2);            // in (0, 4p)
         }
-        const Fr y0 = fp_lazy_add_red(x0, x1), y1 = fp_lazy_sub_red(x0, x1);
+        // the last stage pair of a pass before the last (never a unit: x1 is a product): its results go to a product and to
+        // nothing else, so y0 and y1 stay unreduced (field.hpp: fp_lazy_last_pair_loose_head / _add have the bounds)
+        Fr y0, y1;
+        if (NLAST && mem) {
+            fp_lazy_last_pair_loose_head(x0, x1, y0, y1);
+        } else {
+            y0 = fp_lazy_add_red(x0, x1);
+            y1 = fp_lazy_sub_red(x0, x1);
+        }
         if (uni) {
             y2 = unit ? fp_lazy_red2p(y2) : bmul_s(y2, r << (B - 2 - s));
             n3 = bmul_s(n3, (r + h) << (B - 2 - s));
@@ -586,7 +602,12 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
         x3 = n3;
     };
     // y0, y1, y2 below 2p, n3 = -y3 below p (1 + 2^-29): rows y0 + y2, y1 + y3, y0 - y2, y1 - y3, each strictly below 4p
-    auto unit4_add = [](Fr& x0, Fr& x1, Fr& x2, Fr& x3) __attribute__((always_inline)) {
+    // `loose` (after unit4_mul's loose form only): the same four residues below 2^256, for a product
+    auto unit4_add = [](Fr& x0, Fr& x1, Fr& x2, Fr& x3, const bool loose) __attribute__((always_inline)) {
+        if (loose) {
+            fp_lazy_last_pair_loose_add(x0, x1, x2, x3);
+            return;
+        }
         const Fr y0 = x0, y1 = x1, y2 = x2, n3 = x3;
         x0 = fp_lazy_add(y0, y2);
         x1 = fp_lazy_sub(y1, n3);
@@ -626,21 +647,21 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
         Fr x0 = lds_get(t_lo, t_hi, i0), x1 = lds_get(t_lo, t_hi, i0 + step);
         Fr x2 = lds_get(t_lo, t_hi, i0 + 2 * step), x3 = lds_get(t_lo, t_hi, i0 + 3 * step);
         unit4_mul(x0, x1, x2, x3, s, r, unit);
-        unit4_add(x0, x1, x2, x3);
+        unit4_add(x0, x1, x2, x3, false);   // (rows of a tile: strictly below 4p, whatever the pass)
         lds_put(t_lo, t_hi, i0, x0);
         lds_put(t_lo, t_hi, i0 + 2 * step, x2);
         lds_put(t_lo, t_hi, i0 + step, x1);
         lds_put(t_lo, t_hi, i0 + 3 * step, x3);
         __syncthreads();
     };
-    const bool is_last = NLAST ? false : a.is_last != 0;
+    const bool is_last = NLAST ? false : (PLAIN || a.is_last != 0);
     const uint32_t n_mask = (a.log_n >= 32) ? 0xffffffffu : ((1u << a.log_n) - 1);
 
     // The LDS copy of the table's entries 0, 4, 8 ..: one 16-byte word per lane.  Nothing reads it before the tile's first
     // barrier, so only its load is issued here; the word goes to LDS once the tile's element loads are in flight behind it:
-    // one memory round trip at the head of a tile, not a table round trip and then an element round trip.  (The wait in
-    // front of that ds_write compiles to vmcnt(0): the element loads are under exec masks, idx < in_len, so how many of them
-    // are behind this load is not known statically.  The elements are what the lane needs next in any case.)
+    // one memory round trip at the head of a tile, not a table round trip and then an element round trip.  (Without PLAIN the
+    // wait in front of that ds_write compiles to vmcnt(0): the element loads are under exec masks, idx < in_len, so how many
+    // of them are behind this load is not known statically.  The elements are what the lane needs next in any case.)
     static_assert(PASS8_TW_LDS * TW_CHUNK_Q == 256, "one word of the LDS copy per lane");
     const uint4 w_fill = tw_tab[(size_t)(tid / TW_CHUNK_Q) * 4 * TW_CHUNK_Q + tid % TW_CHUNK_Q];
 
@@ -650,14 +671,14 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
     constexpr uint32_t NE = 4;
     {
         const uint32_t tile_id = blockIdx.x;
-        const Fr* const in_p = a.batch ? a.in_b[blockIdx.y] : a.in;   // (wave-uniform: scalar loads from the kernel arguments)
-        Fr* const out_p = a.batch ? a.out_b[blockIdx.y] : a.out;
+        const Fr* const in_p = !PLAIN && a.batch ? a.in_b[blockIdx.y] : a.in;   // (wave-uniform: scalar loads from the kernel arguments)
+        Fr* const out_p = !PLAIN && a.batch ? a.out_b[blockIdx.y] : a.out;
         uint32_t base = 0, K_uniform = 0;
         if (!is_last) {
             const uint32_t chunks_per_hi = (1u << a.s_log) >> log_c;
             const uint32_t hi = tile_id / chunks_per_hi, lo0 = (tile_id % chunks_per_hi) << log_c;
             base = (hi << (B + a.s_log)) + lo0;
-            K_uniform = hi_to_K(hi, a);
+            if (!(PLAIN && ST)) K_uniform = hi_to_K(hi, a);   // (the plain first pass: no earlier digits)
         }
 
         // ---- load (+ zero pad, coset pre-scale, inter-pass twiddle): k_ntt_pass's, with the lane -> element map above
@@ -680,12 +701,18 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
             }
 #pragma unroll
             for (uint32_t q = 0; q < NE; q++) {
-                x[q] = fp_zero<FrParams>();
-                if (idx[q] < a.in_len) x[q] = fp_load(in_p + idx[q]);
+                if constexpr (PLAIN) {
+                    x[q] = fp_load(in_p + idx[q]);
+                } else {
+                    x[q] = fp_zero<FrParams>();
+                    if (idx[q] < a.in_len) x[q] = fp_load(in_p + idx[q]);
+                }
             }
-            const bool pre_scale = a.scale_mode == 1u && a.nprev == 0;
+            const bool pre_scale = !PLAIN && a.scale_mode == 1u && a.nprev == 0;
             // the last pass's table: its first two entries are requested with the elements, not after pre3
-            const bool direct = !NLAST && a.nprev != 0 && !a.tw_applied && a.tw_direct != nullptr && !pre_scale;
+            const bool direct = PLAIN ? !NLAST : (!NLAST && a.nprev != 0 && !a.tw_applied && a.tw_direct != nullptr && !pre_scale);
+            // PLAIN: a first or an applied middle pass multiplies by nothing at its load, the last pass by its table
+            const bool load_mul = PLAIN ? !NLAST : ((a.nprev != 0 && !a.tw_applied) || pre_scale);
             Fr wd[2];
             if (direct) {
 #pragma unroll
@@ -693,7 +720,7 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
             }
             __builtin_amdgcn_sched_barrier(0);   // (every load above is issued before the wait below)
             w_pl[(tid % TW_CHUNK_Q) * PASS8_TW_LDS + tid / TW_CHUNK_Q] = w_fill;
-            if (a.has_pre3) {
+            if (!PLAIN && a.has_pre3) {
 #pragma unroll
                 for (uint32_t q = 0; q < NE; q++) {
                     const uint32_t m = idx[q] % 3;
@@ -703,7 +730,7 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
                     if (m != 0) x[q] = tmul(x[q], w);
                 }
             }
-            if ((a.nprev != 0 && !a.tw_applied) || pre_scale) {
+            if (load_mul) {
                 if (direct) {
                     Fr w[2];
 #pragma unroll
@@ -739,13 +766,16 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
             // x[q] is row 4b + bitrev2(q) of unit b: stages 0 and 1 (every twiddle of stage 0 and index 0 of stage 1 is 1)
             const uint32_t b = is_last ? bitrev(tid & 63, B - 2) : (tid >> log_c);
             const uint32_t i0 = (b << (2 + log_c)) + (is_last ? (tid >> 6) : (tid & (C - 1)));
-            // Operands that left a product are below 2p as they are: a later pass's come from the store product of the pass
-            // before it (tw_applied: below p (1 + 2^-29)) or from the twiddle product above (below 2p), a coset first pass's
-            // from its pre-scale.  A first pass that loads the caller's data and nothing else holds canonical residues, below p
-            // (the library's contract for every input; the zeros of a padded call are): no reduction either, and bare sums in
-            // place of the reducing ones (FIRST_PAIR_CANON).  Only with pre3, which leaves every third element as loaded next to
-            // two products below 2p, the operands are reduced as before.  Wave-uniform.
-            const FirstPair form = (a.nprev != 0 || pre_scale) ? FIRST_PAIR_2P : (a.has_pre3 ? FIRST_PAIR_4P : FIRST_PAIR_CANON);
+            // Operands that left the twiddle product above are below 2p as they are, and so are a coset first pass's after its
+            // pre-scale.  A first pass that loads the caller's data and nothing else holds canonical residues, below p (the
+            // library's contract for every input; the zeros of a padded call are), and so does a pass whose twiddles the pass
+            // before it applied at its store (tw_applied: every store with ST ends with fp_chunk_handover, in both kernels): no
+            // reduction either, and bare sums in place of the reducing ones (FIRST_PAIR_CANON).  Only with pre3, which leaves
+            // every third element as loaded next to two products below 2p, the operands are reduced as before.  Wave-uniform;
+            // PLAIN: known when the kernel is compiled.
+            const FirstPair form = PLAIN ? (NLAST ? FIRST_PAIR_CANON : FIRST_PAIR_2P)
+                                   : a.tw_applied ? FIRST_PAIR_CANON
+                                   : (a.nprev != 0 || pre_scale) ? FIRST_PAIR_2P : (a.has_pre3 ? FIRST_PAIR_4P : FIRST_PAIR_CANON);
             fp_lazy_first_pair_mul(x[0], x[2], x[1], x[3], [&](const Fr& d) __attribute__((always_inline)) { return bmul_s(d, R >> 2); }, form);
             lds_put(t_lo, t_hi, i0, x[0]);
             lds_put(t_lo, t_hi, i0 + 2 * C, x[1]);
@@ -782,7 +812,7 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
                 for (uint32_t k = 0; k < TW_CHUNK_Q; k++) tw_unpack(nx_t, k, nx_q[k]);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            unit4_add(y[0], y[1], y[2], y[3]);
+            unit4_add(y[0], y[1], y[2], y[3], NLAST);
         }
         uint32_t idx[NE];
 #pragma unroll
@@ -793,14 +823,14 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
             else
                 idx[q] = ((tile_id << log_c) + c) + (k << a.t_log);
         }
-        if (is_last && a.scale_mode == 2u) {
+        if (!PLAIN && is_last && a.scale_mode == 2u) {
 #pragma unroll
             for (uint32_t q = 0; q < NE; q++) {
                 const uint32_t i = idx[q] & n_mask;
                 const Fr w = fp_mul(fp_load(a.sc_lo + (i & ((1u << LO_BITS) - 1))), fp_load(a.sc_hi + (i >> LO_BITS)));
                 y[q] = fp_reduce_once(fp_mul_wide(y[q], w));
             }
-        } else if (is_last && a.has_post3 && !a.hi_scaled) {
+        } else if (!PLAIN && is_last && a.has_post3 && !a.hi_scaled) {
 #pragma unroll
             for (uint32_t q = 0; q < NE; q++) {
                 const uint32_t m = idx[q] % 3;
@@ -816,8 +846,9 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
         if constexpr (ST) {
             // the next pass's inter-pass twiddle, one product at a time (an entry is 32 registers next to the four results).
             // Under product q the first PF words of entry q + 1 are in flight (what the registers allow); its other words are
-            // requested together when product q has freed theirs.  Any 256-bit y -> below p (1 + 2^-29): what the next pass's
-            // first stage pair takes without a reduction.
+            // requested together when product q has freed theirs.  Any 256-bit y (the loose last pair's rows are not below
+            // 4p) -> below p (1 + 2^-29), and canonical after fp_chunk_handover: what the next pass's first stage pair adds
+            // with bare sums.
             constexpr uint32_t PF = TW_CHUNK_Q / 2;
 #pragma unroll
             for (uint32_t q = 0; q < NE; q++) {
@@ -836,6 +867,14 @@ __global__ void __launch_bounds__(256, 4) k_ntt_pass8(PassArgs a) {
                     for (uint32_t k = 0; k < PF; k++) tw_unpack(nx_t, k, pf[k]);
                 }
             }
+            fp_chunk_handover(y);
+            // The store indices once more, from a lane id rebuilt here (the wave's index is a scalar register) that the compiler
+            // cannot tie to the one above (the empty statement reads the last product, so it stays behind it): kept from the
+            // head of the tile across the hand-over's branch, the indices or the lane id cost spilled registers.
+            uint32_t t = (wave << 6) | __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            asm volatile("" : "+v"(t) : "v"(y[NE - 1].l[7]));
+#pragma unroll
+            for (uint32_t q = 0; q < NE; q++) idx[q] = base + (((t >> log_c) + q * (R / NE)) << a.s_log) + (t & (C - 1));
         }
 #pragma unroll
         for (uint32_t q = 0; q < NE; q++) fp_store(out_p + idx[q], y[q]);
@@ -856,6 +895,20 @@ static const PassFn pass_fn_st[H2_NTT_KERNEL_COUNT] = {
     k_ntt_pass8<true, true>, nullptr, k_ntt_pass<true, true, true>, nullptr, k_ntt_pass<false, false, true>,
 };
 
+// the plain call of the fixed pass (k_ntt_pass8's PLAIN), by position
+static const PassFn pass8_plain_first = k_ntt_pass8<true, true, true>, pass8_plain_middle = k_ntt_pass8<true, false, true>,
+                    pass8_plain_last = k_ntt_pass8<false, false, true>;
+static PassFn pass8_plain(NttKernel kernel, const PassArgs& a, uint32_t cnt) {
+    if (cnt != 1 || a.batch || a.in_len < (1u << a.log_n) || a.has_pre3 || a.scale_mode != 0) return nullptr;
+    if (kernel == NK_PASS8) {
+        const bool table = a.nprev != 0 && !a.tw_applied && a.tw_direct != nullptr;   // (an inverse's divisor rides in it: hi_scaled)
+        return a.is_last && table && !(a.has_post3 && !a.hi_scaled) ? pass8_plain_last : nullptr;
+    }
+    if (kernel != NK_PASS8_DP || a.is_last) return nullptr;
+    if (a.nx_tab) return a.nprev == 0 ? pass8_plain_first : nullptr;
+    return a.nprev != 0 && a.tw_applied ? pass8_plain_middle : nullptr;
+}
+
 void ntt_pass_launch(int device, NttKernel kernel, const PassArgs& a, uint32_t cnt, uint32_t threads, hipStream_t stream) {
     const uint32_t R = 1u << a.B, C = 1u << a.log_c;
     const uint32_t ntiles = (1u << a.log_n) / (R * C);
@@ -870,7 +923,8 @@ void ntt_pass_launch(int device, NttKernel kernel, const PassArgs& a, uint32_t c
         }
     }
     const bool pass8 = kernel == NK_PASS8_DP || kernel == NK_PASS8;
-    const PassFn fn = a.nx_tab ? pass_fn_st[kernel] : pass_fn[kernel];
+    PassFn fn = a.nx_tab ? pass_fn_st[kernel] : pass_fn[kernel];
+    if (const PassFn plain = pass8_plain(kernel, a, cnt)) fn = plain;
     if (!fn) throw std::runtime_error("ntt_pass_launch: a last pass has no next pass to multiply for");
     hipLaunchKernelGGL(fn, dim3(ntiles, cnt), dim3(threads), pass8 ? (size_t)PASS8_LDS : lds, stream, a);
 }

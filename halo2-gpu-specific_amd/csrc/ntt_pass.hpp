@@ -30,7 +30,8 @@ struct PassArgs {
     const Fr* tw_hi;    // n >> 12 entries: w^(i << 12)   (unused when n <= 4096)
     const Fr* tw_direct;  // non-null (a last pass): inter-pass twiddle = tw_direct[(K << B) | rho], its load order (no generation multiply)
     // The inter-pass twiddles of a tabulated middle pass (the plan's tw_inter) are applied where the pass BEFORE it stores:
-    // tw_applied (that middle pass): the elements it loads carry their twiddle already, its load multiplies by nothing;
+    // tw_applied (that middle pass): the elements it loads carry their twiddle already, its load multiplies by nothing, and
+    // they are CANONICAL residues (every store product ends with fp_chunk_handover): its first stage pair reduces nothing;
     // nx_tab (the pass before it): the next pass's table, chunk entries (tw_store's third form) at [(rho' << nx_t_log) | K'], and
     // that pass's s_log / B / t_log -- the element stored at idx is the next pass's row rho' = (idx >> nx_s_log) & (2^nx_B - 1)
     // and its K' is this pass's K | k << t_log
@@ -74,6 +75,8 @@ enum NttKernel : uint32_t {
 
 // One pass over `cnt` vectors on `threads` lanes per tile; the grid and the dynamic LDS follow from the kernel and a.log_n /
 // a.B / a.log_c.  `device`: the current one (the LDS limit of the general kernels is raised once per device: 9-bit passes).
+// Which instantiation of `kernel` runs is the launcher's choice from `a`: with a.nx_tab the one that multiplies at its store,
+// and for the plain call of the fixed pass (one vector of full length, no scale) the one compiled for the pass's position.
 void ntt_pass_launch(int device, NttKernel kernel, const PassArgs& a, uint32_t cnt, uint32_t threads, hipStream_t stream);
 
 // Table fillers: one kernel each on `stream` (none for an empty table).  `form`: tw_store's `pair` (ntt_pass.hip), 0 .. 3.
