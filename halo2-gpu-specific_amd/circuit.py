@@ -17,16 +17,44 @@ from . import evaluation as ev
 R_MOD = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 
 
+class SelectorError(ValueError):
+    """a simple selector used where the reference panics (plonk/circuit.rs:889-970, :1340)"""
+
+
+class SelectorInSum(SelectorError):
+    """a simple selector inside an addition or a subtraction (circuit.rs:933, :954)"""
+
+
+class SelectorProduct(SelectorError):
+    """a product of two expressions that both contain a simple selector (circuit.rs:964, :893)"""
+
+
+class SelectorInArgument(SelectorError):
+    """a simple selector in a lookup or shuffle expression (circuit.rs:1340)"""
+
+
+class SelectorNotCompiled(SelectorError):
+    """a selector leaf reached an evaluator: ConstraintSystem.compress_selectors replaces them (synthesize_keygen calls it)"""
+
+
 class Expression:
     def __add__(self, o):
-        return Sum(self, _wrap(o))
+        o = _wrap(o)
+        if contains_simple_selector(self) or contains_simple_selector(o):
+            raise SelectorInSum("attempted to use a simple selector in an addition")
+        return Sum(self, o)
 
     def __sub__(self, o):
-        return Sum(self, Negated(_wrap(o)))
+        o = _wrap(o)
+        if contains_simple_selector(self) or contains_simple_selector(o):
+            raise SelectorInSum("attempted to use a simple selector in a subtraction")
+        return Sum(self, Negated(o))
 
     def __mul__(self, o):
         if isinstance(o, int):
             return Scaled(self, o % R_MOD)
+        if contains_simple_selector(self) and contains_simple_selector(o):
+            raise SelectorProduct("attempted to multiply two expressions containing simple selectors")
         return Product(self, o)
 
     __radd__ = __add__
@@ -77,6 +105,38 @@ class Instance(Query):
     kind, name = ev.VS_INSTANCE, "instance"
 
 
+class Selector:
+    """plonk/circuit.rs:253-311: one bit per row; `simple` ones may be combined with others into one fixed column"""
+
+    def __init__(self, index, simple):
+        self.index, self.simple = index, simple
+
+    def enable(self, region, offset):
+        region.enable_selector(self, offset)
+
+    def __eq__(self, o):
+        return isinstance(o, Selector) and (self.index, self.simple) == (o.index, o.simple)
+
+    def __hash__(self):
+        return hash((self.index, self.simple))
+
+    def __repr__(self):
+        return "Selector(%d, %s)" % (self.index, self.simple)
+
+
+class SelectorQuery(Expression):
+    """Expression::Selector: a leaf until compress_selectors substitutes it"""
+
+    def __init__(self, selector):
+        self.selector = selector
+
+    def degree(self):
+        return 1
+
+    def identifier(self):
+        return "selector[%d]" % self.selector.index
+
+
 class Negated(Expression):
     def __init__(self, e):
         self.e = e
@@ -121,6 +181,105 @@ class Scaled(Expression):
         return "%s*0x%064x" % (self.e.identifier(), self.c)
 
 
+def _children(e):
+    return [getattr(e, c) for c in ("e", "a", "b") if hasattr(e, c)]
+
+
+def contains_simple_selector(e):
+    """Expression::contains_simple_selector (circuit.rs:874-887); remembered on the node (expressions are not mutated), so
+    that the check every operator makes costs one look per operand however large the operand has grown"""
+    known = e.__dict__.get("_simple_selector")
+    if known is None:
+        known = e.selector.simple if isinstance(e, SelectorQuery) else any(contains_simple_selector(c) for c in _children(e))
+        e._simple_selector = known
+    return known
+
+
+def contains_selector(e):
+    """any selector leaf, simple or complex: what the evaluators refuse"""
+    return isinstance(e, SelectorQuery) or any(contains_selector(c) for c in _children(e))
+
+
+def extract_simple_selector(e):
+    """Expression::extract_simple_selector (circuit.rs:889-920): the simple selector of a gate polynomial, or None"""
+    if isinstance(e, SelectorQuery):
+        return e.selector if e.selector.simple else None
+    found = [s for s in (extract_simple_selector(c) for c in _children(e)) if s is not None]
+    if len(found) > 1:
+        raise SelectorProduct("two simple selectors cannot be in the same expression")
+    return found[0] if found else None
+
+
+def replace_selectors(e, replacements, must_be_nonsimple=False):
+    """circuit.rs:1665-1702: every selector leaf of `e` becomes replacements[its index]"""
+    if isinstance(e, SelectorQuery):
+        if must_be_nonsimple and e.selector.simple:
+            raise SelectorInArgument("simple selector %d in a lookup or shuffle expression" % e.selector.index)
+        return replacements[e.selector.index]
+    if isinstance(e, Negated):
+        return Negated(replace_selectors(e.e, replacements, must_be_nonsimple))
+    if isinstance(e, Scaled):
+        return Scaled(replace_selectors(e.e, replacements, must_be_nonsimple), e.c)
+    if isinstance(e, (Sum, Product)):
+        return type(e)(replace_selectors(e.a, replacements, must_be_nonsimple),
+                       replace_selectors(e.b, replacements, must_be_nonsimple))
+    return e
+
+
+def compress_selectors_plan(descriptions, max_degree):
+    """compress_selectors::process (plonk/circuit/compress_selectors.rs:51-230) without the rows: `descriptions` is a list
+    of (selector, max_degree of its gates or 0, conflicts) in selector order, conflicts = the selectors it shares a row
+    with (any container; symmetric).  -> (combinations, assignment): combinations[c] = the member selectors of new column c
+    in root order (member i holds the value i + 1 on its rows); assignment[selector] = (c, root, len(combinations[c])), the
+    substitute being q * prod_{r != root, 1 <= r <= len} (r - q) over the column's query q (substitute_expression)."""
+    combinations, assignment = [], {}
+    rest = []
+    for selector, degree, conflicts in descriptions:
+        if degree == 0:                                   # complex, or in no gate: a 0/1 column of its own
+            assignment[selector] = (len(combinations), 1, 1)
+            combinations.append([selector])
+        else:
+            rest.append((selector, degree, conflicts))
+    added = [False] * len(rest)
+    for i, (selector, degree, _) in enumerate(rest):
+        if added[i]:
+            continue
+        added[i] = True
+        if degree > max_degree:
+            raise ValueError("selector %d is in a gate of degree %d > %d" % (selector, degree, max_degree))
+        d, members = degree - 1, [i]
+        for j in range(i + 1, len(rest)):
+            if d + len(members) == max_degree:
+                break
+            if added[j] or any(rest[m][0] in rest[j][2] or rest[j][0] in rest[m][2] for m in members):
+                continue
+            new_d = max(d, rest[j][1] - 1)
+            if new_d + len(members) + 1 > max_degree:
+                continue
+            d = new_d
+            members.append(j)
+            added[j] = True
+        for root, m in enumerate(members, start=1):
+            assignment[rest[m][0]] = (len(combinations), root, len(members))
+        combinations.append([rest[m][0] for m in members])
+    return combinations, assignment
+
+
+def substitute_expression(query, root, length):
+    """q * prod_{r = 1 .. length, r != root} (r - q), built in the reference's order (compress_selectors.rs:197-204)"""
+    e = query
+    for r in range(1, length + 1):
+        if r != root:
+            e = Product(e, Sum(Constant(r), Negated(query)))
+    return e
+
+
+def _no_simple_selector(expressions, what):
+    for e in expressions:
+        if contains_simple_selector(e):
+            raise SelectorInArgument("expression containing simple selector supplied to %s argument" % what)
+
+
 class ConstraintSystem:
     def __init__(self, name="circuit"):
         self.name = name
@@ -136,6 +295,10 @@ class ConstraintSystem:
         self.shuffle_tracer = []     # (name, [input Expression], [shuffle Expression])
         self.range_checks = []       # (origin advice index, sort advice index, min, max, step): range_check::Argument
         self.constants = []          # fixed columns that take the constants of a floor planner (enable_constant)
+        self.num_selectors = 0
+        self.selectors = []          # Selector objects, by index
+        self.selector_map = []       # after compress_selectors: the fixed column each selector went to
+        self.uncompressed_fixed = None   # num_fixed before compress_selectors (None: not compressed)
 
     # -- columns ------------------------------------------------------------------------------------------
     def advice_column(self):
@@ -182,6 +345,62 @@ class ConstraintSystem:
         if column not in self.constants:
             self.constants.append(column)
             self.enable_equality(column)
+
+    # -- selectors (circuit.rs:1736-1753, :1603-1734) ------------------------------------------------------------------
+    def selector(self):
+        return self._selector(True)
+
+    def complex_selector(self):
+        return self._selector(False)
+
+    def _selector(self, simple):
+        sel = Selector(self.num_selectors, simple)
+        self.num_selectors += 1
+        self.selectors.append(sel)
+        return sel
+
+    def query_selector(self, selector):
+        if not isinstance(selector, Selector) or selector.index >= self.num_selectors:
+            raise TypeError("%r is not a selector of this constraint system" % (selector,))
+        return SelectorQuery(selector)
+
+    def selector_degrees(self):
+        """the largest degree of a gate polynomial each simple selector is in; 0 for complex selectors and those in no gate"""
+        degrees = [0] * self.num_selectors
+        for _, polys in self.gates:
+            for p in polys:
+                sel = extract_simple_selector(p)
+                if sel is not None:
+                    degrees[sel.index] = max(degrees[sel.index], p.degree())
+        return degrees
+
+    def compress_selectors(self, conflicts):
+        """circuit.rs:1603-1734.  `conflicts`: a num_selectors x num_selectors matrix (nested sequences or an array), true
+        where two selectors share a row.  Adds one fixed column per combination after the existing ones, each queried at
+        rotation 0, replaces every selector leaf, fills selector_map and returns the combinations (the
+        member selectors of each new column in root order).  num_selectors keeps its value."""
+        if self.uncompressed_fixed is not None:
+            raise ValueError("compress_selectors was called twice")
+        if len(conflicts) != self.num_selectors:
+            raise ValueError("%d rows of conflicts for %d selectors" % (len(conflicts), self.num_selectors))
+        degrees = self.selector_degrees()
+        max_degree = self.degree()
+        descriptions = [(i, degrees[i], {j for j in range(self.num_selectors) if j != i and conflicts[i][j]})
+                        for i in range(self.num_selectors)]
+        combinations, assignment = compress_selectors_plan(descriptions, max_degree)
+        self.uncompressed_fixed = self.num_fixed
+        queries = []
+        for _ in combinations:
+            column = self.fixed_column()
+            queries.append(self.query_fixed(column))
+        self.selector_map = [("fixed", self.uncompressed_fixed + assignment[i][0]) for i in range(self.num_selectors)]
+        replacements = [substitute_expression(queries[assignment[i][0]], assignment[i][1], assignment[i][2])
+                        for i in range(self.num_selectors)]
+        self.gates = [(name, [replace_selectors(p, replacements) for p in polys]) for name, polys in self.gates]
+        fix = lambda exprs: [replace_selectors(e, replacements, True) for e in exprs]   # noqa: E731
+        self.lookups = [(name, fix(table), [[fix(inputs) for inputs in st] for st in sets]) for name, table, sets in self.lookups]
+        self.shuffles = [[(name, fix(inp), fix(shf)) for name, inp, shf in group] for group in self.shuffles]
+        return combinations
 
     # -- queries (circuit.rs:1478-1560) -----------------------------------------------------------------------
     def _query(self, column, rotation):
@@ -232,6 +451,8 @@ class ConstraintSystem:
         for st in input_expressions_sets:
             for inputs in st:
                 assert len(inputs) == len(table_expressions)
+                _no_simple_selector(inputs, "lookup")
+        _no_simple_selector(table_expressions, "lookup")
         self.lookups.append((name, list(table_expressions), [[list(i) for i in st] for st in input_expressions_sets]))
 
     # -- the traced front end and its chunking passes -----------------------------------------------------------
@@ -239,6 +460,7 @@ class ConstraintSystem:
         """`lookup_any` (plonk/circuit.rs:1377-1406): pairs = [(input Expression, table Expression)]; lookups into the
         same table expressions are collected under one tracer entry"""
         inputs, table = [i for i, _ in pairs], [t for _, t in pairs]
+        _no_simple_selector(inputs + table, "lookup")
         ident = "".join(t.identifier() for t in table)
         if ident in self.lookup_tracer:
             self.lookup_tracer[ident][2].append((name, inputs))
@@ -275,6 +497,7 @@ class ConstraintSystem:
 
     def shuffle(self, name, pairs):
         """circuit.rs:1430-1442: pairs = [(input Expression, shuffle Expression)]"""
+        _no_simple_selector([e for pair in pairs for e in pair], "shuffle")
         self.shuffle_tracer.append((name, [i for i, _ in pairs], [s_ for _, s_ in pairs]))
         return len(self.shuffle_tracer) - 1
 
@@ -301,6 +524,7 @@ class ConstraintSystem:
         """units: [(name, [input Expression], [shuffle Expression])] sharing one product polynomial"""
         for _, inp, shf in units:
             assert len(inp) == len(shf)
+            _no_simple_selector(list(inp) + list(shf), "shuffle")
         self.shuffles.append([(nm, list(i), list(sh)) for nm, i, sh in units])
 
     # -- derived quantities -------------------------------------------------------------------------------
@@ -371,6 +595,9 @@ class GraphEvaluator:
         return self._calc(c.op, c.a, c.b, c.challenge, c.power)
 
     def add_expression(self, e):
+        if isinstance(e, SelectorQuery):
+            raise SelectorNotCompiled("selector %d was not compiled away: run ConstraintSystem.compress_selectors "
+                                      "(synthesize_keygen does) before the constraint system is evaluated" % e.selector.index)
         if isinstance(e, Constant):
             return self.add_constant(e.v)
         if isinstance(e, Query):

@@ -9,13 +9,16 @@
   ShuffleApiGroup    examples/shuffle_api_group.rs:127-176    V1
   MiniPlonk          examples/simple-example-2.rs:169-243     FlatFloorPlanner, strided bulk assignments
   Wide               circuits.wide, the benchmark's lookup-bearing circuit (no .rs text)
+  SimpleExample      examples/simple-example.rs:257-312       V1, one simple selector, a constant, a public input
+  TwoChip            examples/two-chip.rs:473-509             V1, two simple selectors (an add and a mul chip)
+  SelectorGates      simple, complex and unused selectors enabled in bulk, strided (no .rs text)
 
 Where an example assigns cell by cell in a loop, the class assigns the loop's range at once; the calls are otherwise the
 example's, in its order."""
 import numpy as np
 
 from . import circuits
-from .circuit import Constant
+from .circuit import R_MOD, Constant
 from .synthesis import V1, Circuit, FlatFloorPlanner
 
 
@@ -332,3 +335,190 @@ class Wide(Circuit):
             region.constrain_equal(first[0][:m], first[1][1:m + 1])
 
         layouter.assign_region("rows", body)
+
+
+def _copy_advice(region, cell, value, column, offset):
+    """AssignedCell::copy_advice (circuit.rs:131-147): a new cell with the value, constrained equal to the old one"""
+    new = region.assign_advice(column, offset, value)
+    region.constrain_equal(new, cell)
+    return new
+
+
+def _mul(a, b):
+    return None if a is None or b is None else a * b % R_MOD
+
+
+def _add(a, b):
+    return None if a is None or b is None else (a + b) % R_MOD
+
+
+class _Chip:
+    """the instructions the two examples share: a number is (cell, value); value None at keygen"""
+
+    def __init__(self, config):
+        self.config = config
+
+    def load_private(self, layouter, value):
+        return layouter.assign_region("load private", lambda region: (region.assign_advice(self.config.advice[0], 0, value), value))
+
+    def load_constant(self, layouter, constant):
+        return layouter.assign_region(
+            "load constant", lambda region: (region.assign_advice_from_constant(self.config.advice[0], 0, constant), constant))
+
+    def _binary(self, layouter, name, selector, op, a, b):
+        def body(region):
+            selector.enable(region, 0)
+            _copy_advice(region, a[0], a[1], self.config.advice[0], 0)
+            _copy_advice(region, b[0], b[1], self.config.advice[1], 0)
+            value = op(a[1], b[1])
+            return region.assign_advice(self.config.advice[0], 1, value), value
+
+        return layouter.assign_region(name, body)
+
+    def mul(self, layouter, a, b):
+        return self._binary(layouter, "mul", self.config.s_mul, _mul, a, b)
+
+    def add(self, layouter, a, b):
+        return self._binary(layouter, "add", self.config.s_add, _add, a, b)
+
+    def expose_public(self, layouter, num, row):
+        layouter.constrain_instance(num[0], self.config.instance, row)
+
+
+class SimpleExample(Circuit):
+    """c = constant * a^2 * b^2 by three multiplications under one simple selector; c is instance row 0 (the example: k = 4,
+    constant 7, a 2, b 3)"""
+    planner = V1
+
+    def __init__(self, constant=7, a=2, b=3):
+        self.constant, self.a, self.b = constant, a, b
+
+    def without_witnesses(self):
+        # the example's `Self::default()` also zeroes the constant, and hands keygen the full circuit; here keygen runs over
+        # this one, and the constant is part of the circuit's fixed cells
+        return SimpleExample(self.constant, None, None)
+
+    def public_inputs(self):
+        return [[self.constant * self.a ** 2 * self.b ** 2 % R_MOD]]
+
+    def configure(self, cs):
+        advice = [cs.advice_column(), cs.advice_column()]
+        instance = cs.instance_column()
+        constant = cs.fixed_column()
+        cs.enable_equality(instance)
+        cs.enable_constant(constant)
+        for column in advice:
+            cs.enable_equality(column)
+        s_mul = cs.selector()
+        lhs, rhs, out = cs.query_advice(advice[0]), cs.query_advice(advice[1]), cs.query_advice(advice[0], 1)
+        cs.create_gate("mul", [cs.query_selector(s_mul) * (lhs * rhs - out)])
+        return _Config(advice=advice, instance=instance, s_mul=s_mul)
+
+    def synthesize(self, config, layouter):
+        chip = _Chip(config)
+        a = chip.load_private(layouter.namespace("load a"), self.a)
+        b = chip.load_private(layouter.namespace("load b"), self.b)
+        constant = chip.load_constant(layouter.namespace("load constant"), self.constant)
+        ab = chip.mul(layouter.namespace("a * b"), a, b)
+        absq = chip.mul(layouter.namespace("ab * ab"), ab, ab)
+        c = chip.mul(layouter.namespace("constant * absq"), constant, absq)
+        chip.expose_public(layouter.namespace("expose c"), c, 0)
+
+
+class TwoChip(Circuit):
+    """d = (a + b) * c by an add chip and a mul chip, each with a simple selector of its own; d is instance row 0 (the example
+    draws a, b, c at random: here they are arguments)"""
+    planner = V1
+
+    def __init__(self, a=11, b=13, c=17):
+        self.a, self.b, self.c = a, b, c
+
+    def without_witnesses(self):
+        return TwoChip(None, None, None)
+
+    def public_inputs(self):
+        return [[(self.a + self.b) * self.c % R_MOD]]
+
+    def configure(self, cs):
+        advice = [cs.advice_column(), cs.advice_column()]
+        instance = cs.instance_column()
+        lhs, rhs, out = (lambda: cs.query_advice(advice[0])), (lambda: cs.query_advice(advice[1])), (lambda: cs.query_advice(advice[0], 1))
+        s_add = cs.selector()                                    # AddChip::configure
+        cs.create_gate("add", [cs.query_selector(s_add) * (lhs() + rhs() - out())])
+        for column in advice:                                    # MulChip::configure
+            cs.enable_equality(column)
+        s_mul = cs.selector()
+        cs.create_gate("mul", [cs.query_selector(s_mul) * (lhs() * rhs() - out())])
+        cs.enable_equality(instance)
+        return _Config(advice=advice, instance=instance, s_add=s_add, s_mul=s_mul)
+
+    def synthesize(self, config, layouter):
+        chip = _Chip(config)
+        a = chip.load_private(layouter.namespace("load a"), self.a)
+        b = chip.load_private(layouter.namespace("load b"), self.b)
+        c = chip.load_private(layouter.namespace("load c"), self.c)
+        ab = chip.add(layouter.namespace("a + b"), a, b)
+        d = chip.mul(layouter.namespace("(a + b) * c"), ab, c)
+        chip.expose_public(layouter.namespace("expose d"), d, 0)
+
+
+class SelectorGates(Circuit):
+    """Every kind of selector, enabled in bulk over the usable rows: row r is of kind r % 4 --
+      0  s_mul (a b = c) and the complex s_tab (s_tab a is in the table 0 .. 15)     1  s_add (a + b = c)
+      2  s_add and s_bool (b (1 - b) = 0) together, so that the two conflict         3  s_tab alone
+    and s_idle, in no gate, on every eighth row.  The cell a of row 4 is a copy of the cell a of row 0.  compress_selectors
+    gives s_tab and s_idle a column each, combines s_mul with s_add and leaves s_bool alone (the degree is 5)."""
+    planner = FlatFloorPlanner
+    TABLE = 16
+
+    def __init__(self, k, seed=0x53454C, witness=True):
+        self.k, self.seed, self.witness = k, seed, witness
+
+    def without_witnesses(self):
+        return SelectorGates(self.k, self.seed, witness=False)
+
+    def configure(self, cs):
+        a, b, c = cs.advice_column(), cs.advice_column(), cs.advice_column()
+        table = cs.lookup_table_column()
+        cs.enable_equality(a)
+        s_mul, s_add, s_bool, s_idle = cs.selector(), cs.selector(), cs.selector(), cs.selector()
+        s_tab = cs.complex_selector()
+        qa, qb, qc = cs.query_advice(a), cs.query_advice(b), cs.query_advice(c)
+        cs.create_gate("mul", [cs.query_selector(s_mul) * (qa * qb - qc)])
+        cs.create_gate("add", [cs.query_selector(s_add) * (qa + qb - qc)])
+        cs.create_gate("bool", [cs.query_selector(s_bool) * (qb * (Constant(1) - qb))])
+        cs.lookup("a in table", [(cs.query_selector(s_tab) * qa, cs.query_fixed(table))])
+        return _Config(a=a, b=b, c=c, table=table, s_mul=s_mul, s_add=s_add, s_bool=s_bool, s_idle=s_idle, s_tab=s_tab,
+                       rows=((1 << self.k) - 6) // 4 * 4)
+
+    def witness_columns(self, rows):
+        """-> a, b, c (u64 arrays of `rows` values)"""
+        rng = np.random.Generator(np.random.PCG64(self.seed))
+        kind = np.arange(rows) % 4
+        a = rng.integers(0, self.TABLE, size=rows, dtype=np.uint64)
+        b = rng.integers(0, self.TABLE, size=rows, dtype=np.uint64)
+        b[kind == 2] &= np.uint64(1)
+        a[4] = a[0]
+        c = np.where(kind == 0, a * b, a + b)
+        c[kind == 3] = rng.integers(0, 1 << 40, size=int((kind == 3).sum()), dtype=np.uint64)    # unconstrained
+        return a, b, c
+
+    def synthesize(self, config, layouter):
+        rows = config.rows
+        quarter = rows // 4
+        values = self.witness_columns(rows) if self.witness else (None, None, None)
+
+        def body(region):
+            cells = [region.assign_advice(column, 0, v, count=rows) for column, v in zip((config.a, config.b, config.c), values)]
+            region.enable_selector(config.s_mul, 0, stride=4, count=quarter)
+            region.enable_selector(config.s_add, 1, stride=4, count=quarter)
+            region.enable_selector(config.s_add, 2, stride=4, count=quarter)
+            region.enable_selector(config.s_bool, 2, stride=4, count=quarter)
+            region.enable_selector(config.s_tab, 0, stride=4, count=quarter)
+            region.enable_selector(config.s_tab, 3, stride=4, count=quarter)
+            region.enable_selector(config.s_tab, 3)                     # a row enabled twice
+            region.enable_selector(config.s_idle, 0, stride=8, count=(rows + 7) // 8)
+            region.constrain_equal(cells[0][0], cells[0][4])
+
+        layouter.assign_region("rows", body)
+        layouter.assign_table("range table", lambda table: table.assign_cell(config.table, 0, np.arange(self.TABLE, dtype=np.uint64)))

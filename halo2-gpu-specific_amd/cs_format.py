@@ -7,7 +7,9 @@ from . import circuit
 from .transcript import Q_MOD, R_MOD, point_to_bytes
 
 # Every integer is a little-endian u32; rotations are stored as `i32 as u32`; field constants as their canonical
-# 32-byte little-endian representation.  Selectors are compiled away before a key is written (keygen.rs:357).
+# 32-byte little-endian representation.  Selectors are compiled away before a key is written (compress_selectors,
+# circuit.rs:1603-1734): what remains of them is their count and `selector_map`, the fixed column each went to
+# (write_fixed_columns, helpers.rs:386-395: a count and the columns' indices); a selector LEAF has no code and is refused.
 _ANY = {"advice": 0, "fixed": 1, "instance": 2}          # plonk/circuit.rs:79-86
 _ANY_NAME = {v: k for k, v in _ANY.items()}
 _E_CONSTANT, _E_FIXED, _E_ADVICE, _E_INSTANCE, _E_NEGATED, _E_SUM, _E_PRODUCT, _E_SCALED = range(8)   # helpers.rs:590-599
@@ -60,6 +62,9 @@ def _expression_store(cs, e, out):
         out.append(_u32(_E_SCALED))
         _expression_store(cs, e.e, out)
         out.append((e.c % circuit.R_MOD).to_bytes(32, "little"))
+    elif isinstance(e, circuit.SelectorQuery):
+        raise circuit.SelectorNotCompiled("selector %d was not compiled away: the binary form has no selector leaf"
+                                          % e.selector.index)
     else:
         raise TypeError("cannot serialise %r" % (e,))
 
@@ -108,9 +113,14 @@ def _queried_cells(e, cells):
 
 def cs_store(cs):
     """write_cs (helpers.rs:406-456) -> bytes"""
-    out = [_u32(cs.num_advice), _u32(cs.num_instance), _u32(0), _u32(cs.num_fixed), _u32(len(cs.num_advice_queries))]
+    if cs.num_selectors != len(cs.selector_map):
+        raise circuit.SelectorNotCompiled("%d selectors were not compiled away: ConstraintSystem.compress_selectors"
+                                          % cs.num_selectors)
+    out = [_u32(cs.num_advice), _u32(cs.num_instance), _u32(cs.num_selectors), _u32(cs.num_fixed),
+           _u32(len(cs.num_advice_queries))]
     out += [_u32(v) for v in cs.num_advice_queries]
-    out.append(_u32(0))                                         # selector_map: no selectors
+    out.append(_u32(len(cs.selector_map)))                      # selector_map: write_fixed_columns
+    out += [_u32(index) for _, index in cs.selector_map]
     out.append(_u32(len(cs.constants)))                         # constants: write_fixed_columns (helpers.rs:386-395)
     out += [_u32(index) for _, index in cs.constants]
     for queries in (cs.advice_queries, cs.instance_queries, cs.fixed_queries):
@@ -151,17 +161,22 @@ def cs_store(cs):
 
 
 def cs_fetch(r, name="circuit"):
-    """read_cs (helpers.rs:458-561) -> ConstraintSystem; refuses what this prover does not implement (selectors that
-    were not compiled away)"""
+    """read_cs (helpers.rs:458-561) -> ConstraintSystem; refuses selectors that were not compiled away (a selector
+    count without a selector_map of that length)"""
     cs = circuit.ConstraintSystem(name)
     cs.num_advice, cs.num_instance = r.u32(), r.u32()
-    if r.u32():
-        raise IOError("circuit data with live selectors")
+    cs.num_selectors = r.u32()
     cs.num_fixed = r.u32()
     cs.num_advice_queries = [r.u32() for _ in range(r.u32())]
-    selector_map = [r.u32() for _ in range(r.u32())]
+    cs.selector_map = [("fixed", r.u32()) for _ in range(r.u32())]
+    if len(cs.selector_map) != cs.num_selectors:
+        raise IOError("circuit data with live selectors")
+    if any(index >= cs.num_fixed for _, index in cs.selector_map):
+        raise IOError("a selector mapped to a fixed column the circuit data does not have")
+    cs.selectors = [None] * cs.num_selectors                    # simple or complex: keygen-time information only
+    if cs.num_selectors:
+        cs.uncompressed_fixed = cs.num_fixed - len(set(cs.selector_map))
     cs.constants = [("fixed", r.u32()) for _ in range(r.u32())]
-    del selector_map                                            # keygen-time information only
     lists = []
     for _ in range(3):
         lists.append([(r.u32(), r.i32()) for _ in range(r.u32())])

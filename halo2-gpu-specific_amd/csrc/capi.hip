@@ -20,6 +20,7 @@
 #include "logup.hpp"
 #include "permmap.hpp"
 #include "place.hpp"
+#include "selectors.hpp"
 #include "rangecheck.hpp"
 #include "resident.hpp"
 #include "scan.hpp"
@@ -1598,6 +1599,48 @@ int h2_dev_cells_place(const h2_place_segment* segments, size_t count, size_t n,
         DeviceCtx* ctx = current_ctx();
         return cells_place_launch(segments, count, n, out_form, d_scratch, pick_stream(ctx, stream));
     });
+}
+
+// ------------------------------------------------------------------ selectors: bitmaps and combination columns
+size_t h2_selectors_mark_scratch_bytes(size_t count) { return selectors_mark_scratch_bytes(count); }
+
+int h2_dev_selectors_mark(const h2_selector_segment* segments, size_t count, size_t n, size_t num_selectors, void* d_bitmaps,
+                          void* d_scratch, size_t scratch_bytes, void* stream) {
+    if (const char* what = selectors_mark_validate(segments, count, n, num_selectors, d_bitmaps, d_scratch, scratch_bytes))
+        return bad((std::string("h2_dev_selectors_mark: ") + what).c_str());
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return selectors_mark_launch(segments, count, n, (uint32_t*)d_bitmaps, d_scratch, pick_stream(ctx, stream));
+    });
+}
+
+int h2_dev_selectors_conflicts(const void* d_bitmaps, size_t num_selectors, size_t n, void* d_matrix, void* stream) {
+    if (const char* what = selectors_conflicts_validate(d_bitmaps, num_selectors, n, d_matrix))
+        return bad((std::string("h2_dev_selectors_conflicts: ") + what).c_str());
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return selectors_conflicts_launch((const uint32_t*)d_bitmaps, num_selectors, n, (uint8_t*)d_matrix,
+                                          pick_stream(ctx, stream));
+    });
+}
+
+int h2_dev_selectors_combine(const h2_selector_column* plan, size_t columns, const h2_selector_member* members,
+                             size_t num_members, size_t n, size_t num_selectors, const void* d_bitmaps, uint32_t out_form,
+                             void* stream) {
+    if (const char* what = selectors_combine_validate(plan, columns, members, num_members, n, num_selectors, d_bitmaps, out_form))
+        return bad((std::string("h2_dev_selectors_combine: ") + what).c_str());
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return selectors_combine_launch(plan, columns, members, n, (const uint32_t*)d_bitmaps, pick_stream(ctx, stream));
+    });
+}
+
+int h2_selectors_combine(const h2_selector_column* plan, size_t columns, const h2_selector_member* members, size_t num_members,
+                         size_t n, size_t num_selectors, const void* bitmaps, uint32_t out_form) {
+    if (const char* what = selectors_combine_validate(plan, columns, members, num_members, n, num_selectors, bitmaps, out_form))
+        return bad((std::string("h2_selectors_combine: ") + what).c_str());
+    selectors_combine_host(plan, columns, members, n, (const uint32_t*)bitmaps);
+    return H2_OK;
 }
 
 // ------------------------------------------------------------------ rational (Assigned) cells

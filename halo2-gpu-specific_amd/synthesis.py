@@ -12,6 +12,10 @@ per cell of a 2^22-row column.  Values are a Python integer (one cell, or the sa
 (compact cells: 8 bytes each), an (m, 4) u64 array (canonical cells), a device tensor of either shape (values torch code
 computed on the device: they never visit the host), or None (keygen, `without_witnesses`).
 
+Selectors (`cs.selector()`, `Region.enable_selector`) are kept as one bit per row -- `HostSelectors` in numpy, `DeviceSelectors`
+as device bitmaps (csrc/selectors.hip) -- and become fixed columns after the planner has run: the conflict matrix of the
+activations, `ConstraintSystem.compress_selectors`, then one combination column per group, appended to the fixed columns.
+
 Two assemblies sit behind one interface: `HostColumns` writes numpy columns; `DeviceColumns` gathers the ranges into a segment
 list that ONE launch of h2_dev_cells_place (csrc/place.hip) places into resident columns.  The reference lets a later
 assignment of a cell win; the device assembly keeps that by flushing its queue before it queues a segment that may overlap a
@@ -30,8 +34,13 @@ PLACE_OUT_CANONICAL, PLACE_OUT_MONTGOMERY = 0, 1                                
 # h2_place_segment: dst, src, first_row, stride, count (u64 each), form, reserved (u32 each)
 PLACE_SEGMENT = np.dtype([("dst", "<u8"), ("src", "<u8"), ("first_row", "<u8"), ("stride", "<u8"), ("count", "<u8"),
                           ("form", "<u4"), ("reserved", "<u4")])
+# h2_selector_segment, h2_selector_column, h2_selector_member
+SELECTOR_SEGMENT = np.dtype([("selector", "<u4"), ("reserved", "<u4"), ("first_row", "<u8"), ("stride", "<u8"), ("count", "<u8")])
+SELECTOR_COLUMN = np.dtype([("dst", "<u8"), ("first_member", "<u4"), ("num_members", "<u4")])
+SELECTOR_MEMBER = np.dtype([("value", "<u8", (4,)), ("selector", "<u4"), ("reserved", "<u4")])
 _MASK64 = (1 << 64) - 1
-_COLUMN_ORDER = {"instance": 0, "advice": 1, "fixed": 2}                               # Column's Ord (plonk/circuit.rs:47-105)
+# Column's Ord (plonk/circuit.rs:47-105); a region's selectors order after all real columns (RegionColumn, layouter.rs:143-166)
+_COLUMN_ORDER = {"instance": 0, "advice": 1, "fixed": 2, "selector": 3}
 
 
 # -- errors (plonk/error.rs) ---------------------------------------------------------------------------------------------
@@ -308,13 +317,120 @@ class DeviceColumns:
         return self.columns
 
 
+# -- selector activations: one bit per row, two assemblies ------------------------------------------------------------------
+def selector_plan_tables(combinations, destinations, montgomery):
+    """the h2_selector_column / h2_selector_member tables of `combinations` (ConstraintSystem.compress_selectors: the member
+    selectors of each new column, in root order) written to the columns at the addresses `destinations`: member i takes the
+    value i + 1, canonical or as a Montgomery residue"""
+    plan = np.zeros(len(combinations), dtype=SELECTOR_COLUMN)
+    members = np.zeros(sum(len(c) for c in combinations), dtype=SELECTOR_MEMBER)
+    at = 0
+    for c, (group, dst) in enumerate(zip(combinations, destinations)):
+        plan[c] = (dst, at, len(group))
+        for root, selector in enumerate(group, start=1):
+            members[at] = (_limbs((root << 256) % R_MOD if montgomery else root), selector, 0)
+            at += 1
+    return plan, members
+
+
+class HostSelectors:
+    """numpy boolean activations, (num_selectors, n)"""
+
+    def __init__(self, count, n):
+        self.count, self.n = count, n
+        self.bits = np.zeros((count, n), dtype=bool)
+
+    def enable(self, index, row, stride, count):
+        if count:
+            self.bits[index, row:row + (count - 1) * stride + 1:stride] = True
+
+    def conflicts(self):
+        """the exclusion matrix of compress_selectors.rs:102-127, whole: 1 where two different selectors share a row"""
+        packed = np.packbits(self.bits, axis=1)
+        matrix = np.zeros((self.count, self.count), dtype=np.uint8)
+        for i in range(self.count):
+            for j in range(i):
+                matrix[i, j] = matrix[j, i] = np.bitwise_and(packed[i], packed[j]).any()
+        return matrix
+
+    def bitmaps(self):
+        """the activations as h2_dev_selectors_mark leaves them: (num_selectors, ceil(n / 32)) u32 words"""
+        words = (self.n + 31) // 32
+        padded = np.zeros((self.count, words * 32), dtype=bool)
+        padded[:, :self.n] = self.bits
+        return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view("<u4").reshape(self.count, words)
+
+    def combine(self, combinations):
+        """-> one canonical (n, 4) u64 column per combination: i + 1 on the rows of member i"""
+        columns = []
+        for group in combinations:
+            column = np.zeros((self.n, 4), dtype=np.uint64)
+            for root, selector in enumerate(group, start=1):
+                column[self.bits[selector], 0] = root
+            columns.append(column)
+        return columns
+
+
+class DeviceSelectors:
+    """(num_selectors, ceil(n / 32)) u32 bitmaps on the device.  `enable` queues a segment; the queue is flushed by ONE launch of
+    h2_dev_selectors_mark.  The conflict matrix (num_selectors^2 bytes: all the host sees of the activations) and the
+    combination columns -- canonical, or Montgomery with `montgomery`, as DeviceColumns writes the other fixed columns -- are
+    computed where the bits are (csrc/selectors.hip)."""
+
+    def __init__(self, device, count, n, montgomery=False):
+        self.D, self.count, self.n = device, count, n
+        self.montgomery, self.out_form = montgomery, PLACE_OUT_MONTGOMERY if montgomery else PLACE_OUT_CANONICAL
+        self.words = (n + 31) // 32
+        torch = device.torch
+        with torch.cuda.stream(device.tstream):
+            self.bitmaps = torch.zeros(count * self.words, dtype=torch.int32, device=device.dev)
+        self.queue, self.rows_marked, self.flushes = [], 0, 0
+
+    def enable(self, index, row, stride, count):
+        if count:
+            self.queue.append((index, 0, row, stride if count > 1 else 1, count))     # one row: any stride is stride 1
+
+    def flush(self):
+        if not self.queue:
+            return
+        D = self.D
+        segs = np.array(self.queue, dtype=SELECTOR_SEGMENT)
+        nbytes = D.L.h2_selectors_mark_scratch_bytes(len(segs))
+        scratch = D.scratch(nbytes)
+        check(D.L.h2_dev_selectors_mark(segs.ctypes.data, len(segs), self.n, self.count, self.bitmaps.data_ptr(),
+                                        scratch.data_ptr(), nbytes, D.stream), "h2_dev_selectors_mark")
+        self.rows_marked += int(segs["count"].sum())
+        self.flushes += 1
+        self.queue = []
+
+    def conflicts(self):
+        self.flush()
+        D, torch = self.D, self.D.torch
+        with torch.cuda.stream(D.tstream):
+            matrix = torch.empty(self.count * self.count, dtype=torch.uint8, device=D.dev)
+        check(D.L.h2_dev_selectors_conflicts(self.bitmaps.data_ptr(), self.count, self.n, matrix.data_ptr(), D.stream),
+              "h2_dev_selectors_conflicts")
+        with torch.cuda.stream(D.tstream):
+            return matrix.cpu().numpy().reshape(self.count, self.count)
+
+    def combine(self, combinations):
+        self.flush()
+        D = self.D
+        columns = [D.empty(self.n) for _ in combinations]           # every row is written
+        plan, members = selector_plan_tables(combinations, [c.data_ptr() for c in columns], self.montgomery)
+        check(D.L.h2_dev_selectors_combine(plan.ctypes.data, len(plan), members.ctypes.data, len(members), self.n, self.count,
+                                           self.bitmaps.data_ptr(), self.out_form, D.stream), "h2_dev_selectors_combine")
+        return columns
+
+
 # -- the constraint-system side of an assignment pass -------------------------------------------------------------------------
 class _Assembly:
     """What the layouters assign into (the reference's `Assignment`): keygen keeps fixed cells, copies and constants and drops
     advice values (keygen.rs:100-215); the witness pass keeps advice and drops the rest (prover.rs:85-162)."""
 
-    def __init__(self, cs, k, keygen, columns, instances=None):
+    def __init__(self, cs, k, keygen, columns, instances=None, selectors=None):
         self.cs, self.k, self.n, self.keygen, self.columns, self.instances = cs, k, 1 << k, keygen, columns, instances
+        self.selectors = selectors                   # keygen: HostSelectors / DeviceSelectors of a circuit that has selectors
         self.usable = self.n - (cs.blinding_factors() + 1)
         self.copies, self.first_unassigned = [], {}
         self.positions = {column: i for i, column in enumerate(cs.perm_columns)}
@@ -338,6 +454,16 @@ class _Assembly:
         if vals.kind == "none":
             raise SynthesisError("no value for %s[%d]" % column)
         self.columns.place(column[1], row, stride, vals)
+
+    def enable_selector(self, selector, row, stride, count):
+        """keygen.rs:122-137; the witness pass ignores selectors (prover.rs: WitnessCollection::enable_selector)"""
+        if not self.keygen or count == 0:
+            return
+        if selector.index >= self.cs.num_selectors or self.selectors is None:
+            raise BoundsFailure("no selector %d" % selector.index)
+        if row < 0 or row + (count - 1) * stride >= self.usable:
+            raise NotEnoughRowsAvailable(self.k)
+        self.selectors.enable(selector.index, row, stride, count)
 
     def fill_from_row(self, column, row, value):
         if row >= self.usable:                       # keygen.rs:206
@@ -414,6 +540,17 @@ class Region:
 
     def assign_fixed(self, column, offset, values, stride=1, count=None):
         return self._assign("fixed", column, offset, values, stride, count)
+
+    def enable_selector(self, selector, offset, stride=1, count=1):
+        """enables `selector` on the rows offset, offset + stride, ... (`count` of them) of the region"""
+        if stride < 1 or offset < 0 or count < 0:
+            raise ValueError("offset >= 0, stride >= 1 and count >= 0")
+        if self._shape is not None:                  # v1.rs:453: a selector is a column of the region's shape
+            self._shape.columns.add(("selector", selector.index))
+            if count:
+                self._shape.row_count = max(self._shape.row_count, offset + (count - 1) * stride + 1)
+        else:
+            self._asm.enable_selector(selector, self._start + offset, stride, count)
 
     def assign_advice_from_constant(self, column, offset, constant):
         cells = self.assign_advice(column, offset, int(constant))
@@ -631,7 +768,9 @@ def synthesize_keygen(device, circuit, k, planner=None, resident=False, montgome
     """configure + the keygen pass of `circuit` (keygen.rs:236-300) -> (cs, fixed, copies), as `keygen` takes them.
     `planner`: the circuit's own (`Circuit.planner`), V1 when it names none.  `resident`: the fixed columns are built on
     `device` (DeviceColumns) and returned as device tensors -- canonical, or with `montgomery` as the residues
-    `keygen(..., fixed_montgomery=True)` takes as they are; otherwise numpy columns (`device` may be None)."""
+    `keygen(..., fixed_montgomery=True)` takes as they are; otherwise numpy columns (`device` may be None).  A circuit with
+    selectors comes back with them compiled away: `cs` is the compressed constraint system and `fixed` ends with its
+    combination columns, built from device bitmaps when `resident`."""
     cs = ConstraintSystem(type(circuit).__name__)
     config = circuit.configure(cs)
     cs.chunk_lookups()
@@ -640,9 +779,16 @@ def synthesize_keygen(device, circuit, k, planner=None, resident=False, montgome
     if n < cs.minimum_rows():
         raise NotEnoughRowsAvailable(k)
     columns = DeviceColumns(device, cs.num_fixed, n, montgomery) if resident else HostColumns(cs.num_fixed, n)
-    assembly = _Assembly(cs, k, True, columns)
+    selectors = None
+    if cs.num_selectors:
+        selectors = DeviceSelectors(device, cs.num_selectors, n, montgomery) if resident else HostSelectors(cs.num_selectors, n)
+    assembly = _Assembly(cs, k, True, columns, selectors=selectors)
     _planner(circuit, planner).synthesize(assembly, circuit.without_witnesses(), config)
-    return cs, columns.finish(), assembly.copies_array()
+    fixed = columns.finish()
+    if selectors is not None:                        # keygen.rs:276-282: the selectors become fixed columns
+        combinations = cs.compress_selectors(selectors.conflicts())
+        fixed = list(fixed) + selectors.combine(combinations)
+    return cs, fixed, assembly.copies_array()
 
 
 def synthesize_witness(device, circuit, cs_or_pk, k, planner=None, resident=True, instances=None, alloc=None, stats=None):
@@ -656,7 +802,10 @@ def synthesize_witness(device, circuit, cs_or_pk, k, planner=None, resident=True
     cs = getattr(cs_or_pk, "cs", cs_or_pk)
     probe = ConstraintSystem(cs.name)
     config = circuit.configure(probe)               # configure is deterministic: the same columns as at keygen
-    if (probe.num_advice, probe.num_fixed, probe.num_instance) != (cs.num_advice, cs.num_fixed, cs.num_instance):
+    # a compressed `cs` has one more fixed column per combination of selectors than `configure` declares
+    declared_fixed = cs.num_fixed - len(set(cs.selector_map))
+    if (probe.num_advice, probe.num_fixed, probe.num_instance, probe.num_selectors) != (cs.num_advice, declared_fixed,
+                                                                                      cs.num_instance, cs.num_selectors):
         raise ValueError("the circuit does not configure the constraint system it is proved under")
     n = 1 << k
     columns = DeviceColumns(device, cs.num_advice, n, timed=stats is not None) if resident else HostColumns(cs.num_advice, n, alloc)

@@ -180,6 +180,9 @@ def _evaluate(e, adv, fix, ins):
             else:
                 b, a = out.pop(), out.pop()
                 out.append((a + b if isinstance(node, hc.Sum) else a * b) % R_MOD)
+        elif isinstance(node, hc.SelectorQuery):
+            raise hc.SelectorNotCompiled("selector %d was not compiled away: a verifying key holds the constraint system "
+                                         "after ConstraintSystem.compress_selectors" % node.selector.index)
         else:
             raise VerifyError("unknown expression node %r" % (node,))
     return out[0]

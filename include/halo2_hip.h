@@ -367,6 +367,56 @@ size_t h2_cells_place_scratch_bytes(size_t count);
 int h2_dev_cells_place(const h2_place_segment *segments, size_t count, size_t n, uint32_t out_form, void *d_scratch,
                        size_t scratch_bytes, void *stream);
 
+/* Selectors (plonk/circuit.rs:253-311) on the device: the front end keeps every selector's activations as a bitmap and
+ * writes the fixed columns `ConstraintSystem::compress_selectors` (plonk/circuit.rs:1603-1734) asks for from the bits.
+ * d_bitmaps: num_selectors x ceil(n / 32) u32 words, selector-major; bit r % 32 of word r / 32 of a selector is its row r.
+ * The CALLER zeroes them before the first mark.  1 <= num_selectors < 2^16, 1 <= n <= 2^31.
+ *   h2_dev_selectors_mark       sets the bit of every row of `count` segments (selector, first_row, stride, count: rows
+ *                               first_row + j * stride, j < count) by ONE launch whose work is split by cells.  A row may be
+ *                               enabled any number of times, within a call or across calls.  `segments` is a HOST array, read
+ *                               before the call returns.  d_scratch: h2_selectors_mark_scratch_bytes(count) bytes, 16-byte
+ *                               aligned.
+ *   h2_dev_selectors_conflicts  d_matrix (num_selectors^2 bytes, row-major) := 1 where two DIFFERENT selectors share a row
+ *                               below n, else 0: exact, symmetric, zero diagonal (the exclusion matrix of
+ *                               plonk/circuit/compress_selectors.rs:102-127).
+ *   h2_dev_selectors_combine    writes `columns` columns of n rows (n x 4 u64).  Column c has the members
+ *                               members[first_member .. first_member + num_members): a row takes the 32-byte `value` of the
+ *                               member whose selector is enabled there (the last such member, should several be), else zero.
+ *                               The values are written as given: the caller supplies them in out_form (CANONICAL or
+ *                               MONTGOMERY, the H2_PLACE_OUT_* numbers), the form the columns are then in.  `plan` and
+ *                               `members` are HOST arrays, read before the call returns.
+ *   h2_selectors_combine        the same over HOST bitmaps and HOST columns, on the host (tests).
+ * The device calls are asynchronous on `stream`.  All return H2_ERR_INVALID without touching a device, h2_last_error naming the
+ * reason, for a null or misaligned pointer, n or num_selectors out of range, a selector index >= num_selectors, stride 0, a
+ * segment whose last row is not below n, members outside the member table, a value not below the modulus, an unknown form or
+ * too small a scratch. */
+typedef struct {
+    uint32_t selector;
+    uint32_t reserved;
+    uint64_t first_row;
+    uint64_t stride;
+    uint64_t count;
+} h2_selector_segment;
+typedef struct {
+    void *dst;
+    uint32_t first_member;
+    uint32_t num_members;
+} h2_selector_column;
+typedef struct {
+    uint64_t value[4];
+    uint32_t selector;
+    uint32_t reserved;
+} h2_selector_member;
+size_t h2_selectors_mark_scratch_bytes(size_t count);
+int h2_dev_selectors_mark(const h2_selector_segment *segments, size_t count, size_t n, size_t num_selectors, void *d_bitmaps,
+                          void *d_scratch, size_t scratch_bytes, void *stream);
+int h2_dev_selectors_conflicts(const void *d_bitmaps, size_t num_selectors, size_t n, void *d_matrix, void *stream);
+int h2_dev_selectors_combine(const h2_selector_column *plan, size_t columns, const h2_selector_member *members,
+                             size_t num_members, size_t n, size_t num_selectors, const void *d_bitmaps, uint32_t out_form,
+                             void *stream);
+int h2_selectors_combine(const h2_selector_column *plan, size_t columns, const h2_selector_member *members, size_t num_members,
+                         size_t n, size_t num_selectors, const void *bitmaps, uint32_t out_form);
+
 /* Rational cells (`Assigned<F>`, plonk/assigned.rs) resolved to field elements, as poly::batch_invert_assigned
  * (poly.rs:148-173) does for keygen's fixed columns and the fork's assign_advice cell by cell (plonk/prover.rs:1607-1612):
  * for each of `cols` columns of n rows, out[r] = num[r] / den[r], and 0 where den[r] = 0 (`Assigned::evaluate`).  All

@@ -8,7 +8,16 @@
 and the placement kernel's achieved bytes per second (8 bytes read and 32 written per cell of route 3; the launch timed by
 events, the copy of its segment table included).  Every route runs twice; the second run, which finds its pinned memory
 already allocated, is reported -- page-locking is a cost of the first proof, not of every one.
-usage: python tools/synthesis_bench.py [K] [QUADS]"""
+
+With `selectors` as third argument the tool times a selector-bearing keygen instead (circuits_frontend.SelectorGates: five
+selectors over all usable rows, four combination columns), medians of five runs each:
+
+  A  the host assembly (numpy activations, conflicts and combination columns) + the upload of every fixed column
+  B  the device assembly: segments marked into bitmaps, conflicts and combination columns by csrc/selectors.hip
+
+and the bytes per second of h2_dev_selectors_combine alone (32 bytes written per row and column, 4 bytes read per member and
+32 rows; timed by events).
+usage: python tools/synthesis_bench.py [K] [QUADS] [selectors]"""
 import os
 import sys
 import time
@@ -27,6 +36,62 @@ k = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 quads = int(sys.argv[2]) if len(sys.argv) > 2 else 16
 n, ncols = 1 << k, 4 * quads
 D = prover.Device()
+
+
+def selector_leg():
+    from halo2_gpu_specific_amd import synthesis
+
+    circuit = circuits_frontend.SelectorGates(k)
+
+    def host_route():
+        _, fixed, _ = prover.synthesize_keygen(None, circuit, k)
+        resident = [D.upload(column) for column in fixed]
+        D.sync()
+        return resident
+
+    def device_route():
+        _, fixed, _ = prover.synthesize_keygen(D, circuit, k, resident=True)
+        D.sync()
+        return fixed
+
+    results = {}
+    for name, route in (("A host assembly + upload", host_route), ("B device assembly", device_route)):
+        times = []
+        for _ in range(5):
+            D.sync()
+            begin = time.perf_counter()
+            results[name] = route()
+            times.append(time.perf_counter() - begin)
+        print("selector keygen, k = %d, route %-26s median %.2f ms (runs: %s)"
+              % (k, name, 1e3 * float(np.median(times)), ", ".join("%.2f" % (1e3 * t) for t in times)))
+    for a, b in zip(*results.values()):
+        assert torch.equal(a[:4096], b[:4096]) and torch.equal(a[n - 4096:], b[n - 4096:]), "the routes differ"
+    # the combine kernel alone: the circuit's own activations and plan
+    cs, _, _ = prover.synthesize_keygen(None, circuits_frontend.SelectorGates(6), 6)
+    rows = (n - 6) // 4 * 4
+    dev = synthesis.DeviceSelectors(D, 5, n)
+    for selector, first, stride in ((0, 0, 4), (1, 1, 4), (1, 2, 4), (2, 2, 4), (4, 0, 4), (4, 3, 4), (3, 0, 8)):
+        dev.enable(selector, first, stride, (rows - first + stride - 1) // stride)
+    dev.flush()
+    combinations = [[3], [4], [0, 1], [2]]
+    assert [cs.selector_map[s][1] - 1 for group in combinations for s in group] == [0, 1, 2, 2, 3]
+    times = []
+    for _ in range(5):
+        begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        begin.record(D.tstream)
+        dev.combine(combinations)
+        end.record(D.tstream)
+        end.synchronize()
+        times.append(begin.elapsed_time(end))
+    moved = len(combinations) * n * 32 + sum(len(g) for g in combinations) * n // 8
+    print("h2_dev_selectors_combine, k = %d: %d columns, %.1f MiB, median %.3f ms: %.2f TB/s (runs: %s ms)"
+          % (k, len(combinations), moved / 2**20, float(np.median(times)), moved / (float(np.median(times)) * 1e-3) / 1e12,
+             ", ".join("%.3f" % t for t in times)))
+
+
+if sys.argv[3:4] == ["selectors"]:
+    selector_leg()
+    sys.exit(0)
 circuit = circuits_frontend.Wide(k, quads)
 cs = circuits.wide(quads)
 
