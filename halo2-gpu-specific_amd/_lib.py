@@ -137,6 +137,11 @@ SYMBOLS = {
     "h2_dev_selectors_conflicts": (ctypes.c_int, [_vp, _sz, _sz, _vp, _vp]),
     "h2_dev_selectors_combine": (ctypes.c_int, [_vp, _sz, _vp, _sz, _sz, _sz, _vp, _u32, _vp]),
     "h2_selectors_combine": (ctypes.c_int, [_vp, _sz, _vp, _sz, _sz, _sz, _vp, _u32]),
+    "h2_coverage_scratch_bytes": (_sz, [_sz, _sz, _sz, _sz, _sz]),
+    "h2_dev_coverage_mark": (ctypes.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "h2_dev_coverage_check": (ctypes.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "h2_coverage_mark": (ctypes.c_int, [_vp, _sz, _vp, _sz, _vp, _sz]),
+    "h2_coverage_check": (ctypes.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _sz]),
     "h2_check_scratch_bytes": (_sz, [_sz]),
     "h2_dev_check_nonzero_rows": (ctypes.c_int, [_vp, _sz, _vp, _vp, _vp]),
     "h2_dev_check_gates": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _sz, _vp]),

@@ -1,4 +1,5 @@
-"""check_witness: MockProver::run(..).verify() (dev.rs:932-1340) on the device, reported as MockProver's failures."""
+"""check_witness, check_assignments and check_circuit: MockProver::run(..).verify() (dev.rs:932-1340) on the device, reported as
+MockProver's failures."""
 import ctypes
 import hashlib
 import time
@@ -9,6 +10,7 @@ import numpy as np
 from ._lib import check
 from .circuit import compile_compress
 from .domain import _vp
+from .synthesis import CHECK_CELL, synthesize_coverage, synthesize_witness
 from .transcript import R_MOD
 from .witness import _compress, _compress_desc, _instance_columns, _witness_sets
 
@@ -18,18 +20,32 @@ ConstraintNotSatisfied = namedtuple("ConstraintNotSatisfied", "gate_index gate_n
 Lookup = namedtuple("Lookup", "name lookup_index input_set_index input_fail_index row circuit")
 Shuffle = namedtuple("Shuffle", "name group_index shuffle_index row circuit")
 Permutation = namedtuple("Permutation", "column row circuit")
+# dev.rs:959-1000: `column` = (kind, index) of the cell gate `gate_index` reads at `row`, `offset` = row - the region's start
+CellNotAssigned = namedtuple("CellNotAssigned", "gate_index gate_name region_index region_name column offset row")
 
 
-def check_failures(cs, records):
+def _record_order(r):
+    """cell failures first (verify_at_rows chains them first), by (region, gate, query, row); then the rest"""
+    circuit, k = r[0] >> 8, r[0] & 0xFF
+    return (circuit, -1, r[2], r[1], r[3]) if k == CHECK_CELL else (circuit, k, r[1], r[2], r[3])
+
+
+def check_failures(cs, records, coverage=None):
     """h2_check_records -- (kind, index, sub, row) rows, kind = H2_CHECK_* | circuit << 8 -- as MockProver's failures, in the
-    order MockProver chains them: circuit by circuit; gates, lookups, shuffles, then the permutation; within a kind by index,
-    sub-index and row."""
-    gate_of = [(gi, name, pi) for gi, (name, polys) in enumerate(cs.gates) for pi in range(len(polys))]
+    order MockProver chains them: circuit by circuit; unassigned cells (by region, gate, queried cell and row), gates, lookups,
+    shuffles, then the permutation; within a kind by index, sub-index and row.  Records of kind H2_CHECK_CELL are named with
+    the region and gate tables of `coverage` (synthesize_coverage), the others with `cs`."""
+    gate_of = [(gi, name, pi) for gi, (name, polys) in enumerate(cs.gates) for pi in range(len(polys))] if cs is not None else []
     keyed = []
-    for kind, index, sub, row in sorted({tuple(int(v) for v in r) for r in records},
-                                        key=lambda r: (r[0] >> 8, r[0] & 0xFF, r[1], r[2], r[3])):
+    for kind, index, sub, row in sorted({tuple(int(v) for v in r) for r in records}, key=_record_order):
         circuit, k = kind >> 8, kind & 0xFF
-        if k == CHECK_GATE:
+        if k == CHECK_CELL:
+            if coverage is None:
+                raise ValueError("check: a cell record needs the coverage it came from")
+            name, _, cells = coverage.gates[index >> 16]
+            keyed.append(CellNotAssigned(index >> 16, name, sub, coverage.regions[sub][0], cells[index & 0xFFFF][0],
+                                         row - coverage.start(sub), row))
+        elif k == CHECK_GATE:
             gi, name, pi = gate_of[index]
             keyed.append(ConstraintNotSatisfied(gi, name, pi, row, circuit))
         elif k == CHECK_LOOKUP:
@@ -71,9 +87,10 @@ def check_witness(device, pk, advice, instances=(), seed=0, max_failures=1024, m
       copies    every cell of every permutation column, all n rows, against the cell its cycle maps it to
     A reported failure is always real; a real one is missed with probability <= (parts or tuple length) x n / r < 2^-200.
 
-    Out of scope: MockProver's CellNotAssigned and ConstraintPoisoned (a dense witness has no unassigned cells; cells in rows
-    >= usable are read as the caller supplied them), gate rows in the blinding region, any change to create_proof*, and the
-    Rust shims under integration/.  `timings` (a dict): filled with the seconds of each phase (synchronising between them)."""
+    Out of scope: MockProver's ConstraintPoisoned (cells in rows >= usable are read as the caller supplied them), gate rows in
+    the blinding region, any change to create_proof*, and the Rust shims under integration/.  An unassigned cell of a dense
+    witness is a zero here; a gate enabled over one is found by check_assignments, which takes the circuit and not the witness.
+    `timings` (a dict): filled with the seconds of each phase (synchronising between them)."""
     D, L, torch = device, device.L, device.torch
     cs, dom = pk.cs, pk.domain
     n = dom.n
@@ -173,14 +190,47 @@ def check_witness(device, pk, advice, instances=(), seed=0, max_failures=1024, m
     return check_result(cs, host, cap)
 
 
-def check_result(cs, words, cap):
+def check_result(cs, words, cap, coverage=None):
     """(failures, total) of check_witness's downloaded block: u32 words = [u64 count, 2 pad][cap records of 4]; when the
     count exceeds cap only the first cap slots hold records"""
     total = int(np.ascontiguousarray(words[:2]).view(np.uint64)[0])
-    return check_failures(cs, words[4:4 + 4 * cap].reshape(-1, 4)[:min(total, cap)]), total
+    return check_failures(cs, words[4:4 + 4 * cap].reshape(-1, 4)[:min(total, cap)], coverage), total
+
+
+def check_assignments(device, circuit, k, planner=None, max_failures=1024, resident=True, timings=None):
+    """MockProver's VerifyFailure::CellNotAssigned (dev.rs:959-1000): every cell that a gate reads from a row on which a
+    region enabled one of the gate's selectors must have been assigned BY THAT REGION.  -> (failures, total): the first
+    max_failures of them as CellNotAssigned tuples sorted by (region, gate, queried cell, row), and their exact number.
+
+    One assignment pass of `circuit` (synthesize_coverage: no value is placed, missing ones are keygen's business) queues the
+    regions' assignments and enabled rows; with `resident` one launch marks the cells in a device bit array and one launch
+    tests every enabled row of every gate against it (csrc/coverage.hip); otherwise numpy does both (`device` may be None).
+    The definition, with what differs from the reference, is DESIGN.md 3b, "Checking assignments".  `timings` (a dict): the
+    seconds of synthesize, mark, check and download."""
+    cap = max(int(max_failures), 0)
+    begin = time.perf_counter()
+    coverage = synthesize_coverage(device, circuit, k, planner, resident)
+    if timings is not None:
+        timings["synthesize"] = timings.get("synthesize", 0.0) + time.perf_counter() - begin
+    records, total = coverage.check(cap, timings) if resident else coverage.check(cap)
+    return check_failures(None, records, coverage), total
+
+
+def check_circuit(device, pk, circuit, k, instances=(), planner=None, seed=0, max_failures=1024, resident=True, timings=None):
+    """MockProver::run(k, &circuit, instances).verify(): check_assignments, then the witness pass of `circuit`
+    (synthesize_witness) and check_witness on what it assigned.  -> (failures, total): the unassigned cells first, the rest in
+    check_witness's order, at most max_failures of either; `total` counts both exactly."""
+    cells, cell_total = check_assignments(device, circuit, k, planner, max_failures, resident, timings)
+    advice, first_unassigned = synthesize_witness(device, circuit, pk, k, planner, resident, instances=list(instances) or None)
+    failures, total = check_witness(device, pk, advice, list(instances), seed, max_failures, first_unassigned=first_unassigned,
+                                    timings=timings)
+    return cells + failures, cell_total + total
 
 
 def _describe_failure(f):
+    if isinstance(f, CellNotAssigned):
+        return "region %d '%s' enables gate %d '%s' over %s column %d at offset %d (row %d), a cell it never assigned" % (
+            f.region_index, f.region_name, f.gate_index, f.gate_name, f.column[0], f.column[1], f.offset, f.row)
     where = "circuit %d: " % f.circuit if f.circuit else ""
     if isinstance(f, ConstraintNotSatisfied):
         return "%sgate %d '%s' polynomial %d is not satisfied at row %d" % (where, f.gate_index, f.gate_name, f.poly_index, f.row)
@@ -193,13 +243,25 @@ def _describe_failure(f):
     return "%scopy constraint of %s column %d broken at row %d" % (where, f.column[0], f.column[1], f.row)
 
 
+def _raise_failures(what, name, failures, total, shown):
+    lines = [_describe_failure(f) for f in failures[:shown]]
+    more = total - len(lines)
+    raise ValueError("%s does not satisfy circuit '%s': %d failure(s)\n  %s%s" % (
+        what, name, total, "\n  ".join(lines), "\n  ... and %d more" % more if more > 0 else ""))
+
+
+def assert_circuit_satisfied(device, pk, circuit, k, instances=(), planner=None, seed=0, max_failures=1024, resident=True, shown=10):
+    """MockProver::assert_satisfied (dev.rs:1354-1370) over check_circuit: raises ValueError with the first `shown` failures
+    described and the total when there is any"""
+    failures, total = check_circuit(device, pk, circuit, k, instances, planner, seed, max_failures, resident)
+    if total:
+        _raise_failures("the circuit's synthesis", pk.cs.name, failures, total, shown)
+
+
 def assert_satisfied(device, pk, advice, instances=(), seed=0, max_failures=1024, montgomery=False, first_unassigned=None,
                      shown=10):
     """MockProver::assert_satisfied (dev.rs:1354-1370): check_witness, raising ValueError with the first `shown` failures
     (gate, lookup or column name and row) and the total when there is any"""
     failures, total = check_witness(device, pk, advice, instances, seed, max_failures, montgomery, first_unassigned)
     if total:
-        lines = [_describe_failure(f) for f in failures[:shown]]
-        more = total - len(lines)
-        raise ValueError("the witness does not satisfy circuit '%s': %d failure(s)\n  %s%s" % (
-            pk.cs.name, total, "\n  ".join(lines), "\n  ... and %d more" % more if more > 0 else ""))
+        _raise_failures("the witness", pk.cs.name, failures, total, shown)

@@ -210,6 +210,29 @@ def extract_simple_selector(e):
     return found[0] if found else None
 
 
+def gate_cells(cs):
+    """[(gate name, S(g), Q(g))] of an UNCOMPRESSED constraint system, what MockProver's CellNotAssigned asks of a gate
+    (dev.rs:959-1000): S(g) the sorted indices of the selectors at the gate's SelectorQuery leaves, simple or complex; Q(g) the
+    distinct ((kind, column), rotation) cells of its advice, fixed and instance leaves, by first appearance -- the polynomials
+    in order, each depth first and left to right"""
+    out = []
+    for name, polys in cs.gates:
+        selectors, cells = set(), {}
+
+        def walk(e):
+            if isinstance(e, SelectorQuery):
+                selectors.add(e.selector.index)
+            elif isinstance(e, Query):
+                cells.setdefault(((e.name, e.column), e.rotation), None)
+            for child in _children(e):
+                walk(child)
+
+        for p in polys:
+            walk(p)
+        out.append((name, sorted(selectors), list(cells)))
+    return out
+
+
 def replace_selectors(e, replacements, must_be_nonsimple=False):
     """circuit.rs:1665-1702: every selector leaf of `e` becomes replacements[its index]"""
     if isinstance(e, SelectorQuery):

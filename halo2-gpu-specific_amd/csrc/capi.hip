@@ -21,6 +21,7 @@
 #include "permmap.hpp"
 #include "place.hpp"
 #include "selectors.hpp"
+#include "coverage.hpp"
 #include "rangecheck.hpp"
 #include "resident.hpp"
 #include "scan.hpp"
@@ -1640,6 +1641,53 @@ int h2_selectors_combine(const h2_selector_column* plan, size_t columns, const h
     if (const char* what = selectors_combine_validate(plan, columns, members, num_members, n, num_selectors, bitmaps, out_form))
         return bad((std::string("h2_selectors_combine: ") + what).c_str());
     selectors_combine_host(plan, columns, members, n, (const uint32_t*)bitmaps);
+    return H2_OK;
+}
+
+// ------------------------------------------------------------------ coverage: the cells each region assigned (coverage.hip)
+size_t h2_coverage_scratch_bytes(size_t segments, size_t planes, size_t queries, size_t uses, size_t earlier) {
+    return coverage_scratch_bytes(segments, planes, queries, uses, earlier);
+}
+
+int h2_dev_coverage_mark(const h2_coverage_plane* planes, size_t num_planes, const h2_coverage_segment* segments, size_t count,
+                         void* d_bits, size_t words, void* d_scratch, size_t scratch_bytes, void* stream) {
+    if (const char* what = coverage_mark_validate(planes, num_planes, segments, count, d_bits, words, true, d_scratch, scratch_bytes))
+        return bad((std::string("h2_dev_coverage_mark: ") + what).c_str());
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return coverage_mark_launch(planes, segments, count, (uint32_t*)d_bits, d_scratch, pick_stream(ctx, stream));
+    });
+}
+
+int h2_dev_coverage_check(const h2_coverage_plane* planes, size_t num_planes, const h2_coverage_query* queries,
+                          size_t num_queries, const h2_coverage_use* uses, size_t num_uses, const uint32_t* earlier,
+                          size_t num_earlier, size_t n, const void* d_bits, size_t words, void* d_scratch, size_t scratch_bytes,
+                          uint64_t* d_count, h2_check_record* d_records, size_t cap, void* stream) {
+    if (const char* what = coverage_check_validate(planes, num_planes, queries, num_queries, uses, num_uses, earlier, num_earlier, n,
+                                                   d_bits, words, true, d_scratch, scratch_bytes, d_count, d_records, cap))
+        return bad((std::string("h2_dev_coverage_check: ") + what).c_str());
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return coverage_check_launch(planes, num_planes, queries, num_queries, uses, num_uses, earlier, num_earlier, n,
+                                     (const uint32_t*)d_bits, d_scratch, d_count, d_records, cap, pick_stream(ctx, stream));
+    });
+}
+
+int h2_coverage_mark(const h2_coverage_plane* planes, size_t num_planes, const h2_coverage_segment* segments, size_t count,
+                     void* bits, size_t words) {
+    if (const char* what = coverage_mark_validate(planes, num_planes, segments, count, bits, words, false, nullptr, 0))
+        return bad((std::string("h2_coverage_mark: ") + what).c_str());
+    coverage_mark_host(planes, segments, count, (uint32_t*)bits);
+    return H2_OK;
+}
+
+int h2_coverage_check(const h2_coverage_plane* planes, size_t num_planes, const h2_coverage_query* queries, size_t num_queries,
+                      const h2_coverage_use* uses, size_t num_uses, const uint32_t* earlier, size_t num_earlier, size_t n,
+                      const void* bits, size_t words, uint64_t* count, h2_check_record* records, size_t cap) {
+    if (const char* what = coverage_check_validate(planes, num_planes, queries, num_queries, uses, num_uses, earlier, num_earlier, n,
+                                                   bits, words, false, nullptr, 0, count, records, cap))
+        return bad((std::string("h2_coverage_check: ") + what).c_str());
+    coverage_check_host(planes, queries, uses, num_uses, earlier, n, (const uint32_t*)bits, count, records, cap);
     return H2_OK;
 }
 

@@ -27,8 +27,9 @@ from .arithmetic import (OP_ADDGAMMA, OP_CONSTANT, OP_LCBETA, OP_LCTHETA, OP_MUL
                          OP_SUM_C)                          # Device.eval_op's operations: H2_OP_* of include/halo2_hip.h
 from .assigned import (ASSIGNED_BAD_ROWS, ASSIGNED_FORM_CANONICAL, ASSIGNED_FORM_COMPACT, ASSIGNED_FORM_MONTGOMERY,  # noqa: F401
                        ASSIGNED_OK, ASSIGNED_STATUS_WORDS, Rational, resolve_rational)
-from .check import (CHECK_COPY, CHECK_GATE, CHECK_LOOKUP, CHECK_SHUFFLE, ConstraintNotSatisfied, Lookup, Permutation,  # noqa: F401
-                    Shuffle, assert_satisfied, check_failures, check_result, check_witness)
+from .check import (CHECK_CELL, CHECK_COPY, CHECK_GATE, CHECK_LOOKUP, CHECK_SHUFFLE, CellNotAssigned, ConstraintNotSatisfied,  # noqa: F401
+                    Lookup, Permutation, Shuffle, assert_circuit_satisfied, assert_satisfied, check_assignments, check_circuit,
+                    check_failures, check_result, check_witness)
 from .circuit import compile_evaluator  # noqa: F401
 from .cs_format import vk_digest, vk_digest_preimage  # noqa: F401
 from .device import CosetTables, Device, footprint, g1_ntt, max_scalar_bits, parse_bytes, sharding_description  # noqa: F401
@@ -38,9 +39,9 @@ from .keygen import (PERM_MAPPING_SORT_TILE, PM_INTERNAL, PM_OK, PM_OUT_OF_BOUND
 from .multiopen import _gwc, _shplonk
 from .parallel import allgather_rows, allreduce_counts, allreduce_max, coset_unmix_matrix, exchange_cosets, msm_split_range, scatter_cosets
 from .params import Params  # noqa: F401
-from .synthesis import (AssignedCells, BoundsFailure, Circuit, ColumnNotInPermutation, DeviceColumns, FlatFloorPlanner,  # noqa: F401
-                        HostColumns, Layouter, NotEnoughColumnsForConstants, NotEnoughRowsAvailable, Region, SynthesisError, Table, V1,
-                        region_starts, synthesize_keygen, synthesize_witness)
+from .synthesis import (AssignedCells, BoundsFailure, Circuit, ColumnNotInPermutation, DeviceColumns, DeviceCoverage,  # noqa: F401
+                        FlatFloorPlanner, HostColumns, HostCoverage, Layouter, NotEnoughColumnsForConstants, NotEnoughRowsAvailable, Region, SynthesisError, Table, V1,
+                        region_starts, synthesize_coverage, synthesize_keygen, synthesize_witness)
 from .transcript import Blake2bWrite, R_MOD, fr_to_mont_limbs, g1_add_affine
 from .witness import (RC_FORM_CANONICAL, RC_FORM_COMPACT, RC_FORM_MONTGOMERY, RC_IN_USE, RC_NO_FIT, RC_OK, RC_OUT_OF_RANGE,  # noqa: F401
                       RC_STATUS_WORDS, RC_UNSUPPORTED, _compress, _instance_columns, _witness_sets, complete_range_check_witness,

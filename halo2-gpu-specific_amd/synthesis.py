@@ -20,6 +20,10 @@ Two assemblies sit behind one interface: `HostColumns` writes numpy columns; `De
 list that ONE launch of h2_dev_cells_place (csrc/place.hip) places into resident columns.  The reference lets a later
 assignment of a cell win; the device assembly keeps that by flushing its queue before it queues a segment that may overlap a
 queued one of the same column.
+
+A third pass keeps no value at all: `synthesize_coverage` records WHICH cells each region assigns and which selector rows it
+enables -- `HostCoverage` in numpy, `DeviceCoverage` as region-tagged bits on the device (csrc/coverage.hip) -- for
+check.check_assignments, MockProver's CellNotAssigned ("Checking assignments").
 """
 import math
 import time
@@ -27,7 +31,7 @@ import time
 import numpy as np
 
 from ._lib import check
-from .circuit import R_MOD, ConstraintSystem
+from .circuit import R_MOD, ConstraintSystem, gate_cells
 
 PLACE_FORM_CANONICAL, PLACE_FORM_COMPACT, PLACE_FORM_BROADCAST = 0, 1, 2               # H2_PLACE_FORM_*
 PLACE_OUT_CANONICAL, PLACE_OUT_MONTGOMERY = 0, 1                                       # H2_PLACE_OUT_*
@@ -38,6 +42,15 @@ PLACE_SEGMENT = np.dtype([("dst", "<u8"), ("src", "<u8"), ("first_row", "<u8"), 
 SELECTOR_SEGMENT = np.dtype([("selector", "<u4"), ("reserved", "<u4"), ("first_row", "<u8"), ("stride", "<u8"), ("count", "<u8")])
 SELECTOR_COLUMN = np.dtype([("dst", "<u8"), ("first_member", "<u4"), ("num_members", "<u4")])
 SELECTOR_MEMBER = np.dtype([("value", "<u8", (4,)), ("selector", "<u4"), ("reserved", "<u4")])
+# h2_coverage_plane, h2_coverage_segment, h2_coverage_query, h2_coverage_use
+COVERAGE_PLANE = np.dtype([("first_word", "<u8"), ("row_lo", "<u4"), ("rows", "<u4")])
+COVERAGE_SEGMENT = np.dtype([("plane", "<u4"), ("reserved", "<u4"), ("first_row", "<u8"), ("stride", "<u8"), ("count", "<u8")])
+COVERAGE_QUERY = np.dtype([("plane", "<u4"), ("column", "<u4"), ("rotation", "<i4"), ("reserved", "<u4")])
+COVERAGE_USE = np.dtype([("region", "<u4"), ("gate", "<u4"), ("first_query", "<u4"), ("num_queries", "<u4"),
+                         ("first_earlier", "<u4"), ("num_earlier", "<u4"), ("first_row", "<u8"), ("stride", "<u8"), ("count", "<u8")])
+COVERAGE_NO_PLANE = 0xFFFFFFFF                                                         # H2_COVERAGE_NO_PLANE
+COVERAGE_MAX_WORDS = 1 << 30                                                           # the bit array: 4 GiB at the most
+CHECK_CELL = 4                                                                         # H2_CHECK_CELL
 _MASK64 = (1 << 64) - 1
 # Column's Ord (plonk/circuit.rs:47-105); a region's selectors order after all real columns (RegionColumn, layouter.rs:143-166)
 _COLUMN_ORDER = {"instance": 0, "advice": 1, "fixed": 2, "selector": 3}
@@ -423,6 +436,204 @@ class DeviceSelectors:
         return columns
 
 
+# -- which cells each region assigned: MockProver's CellNotAssigned, two assemblies ---------------------------------------------
+class _Coverage:
+    """The regions of one assignment pass: their names and planner starts, the cells they assigned and the selector rows
+    they enabled, both as queued (first_row, stride, count) segments, and -- once the pass has ended and every extent is known
+    -- the tables of include/halo2_hip.h over them ("Checking assignments").  `check(cap)` of the two
+    subclasses gives (records, total): the (H2_CHECK_CELL, gate << 16 | query, region, cell_row) rows of the failures, at most
+    `cap` of them, and their exact number."""
+
+    def __init__(self, cs, n):
+        self.n = n
+        self.gates = gate_cells(cs)                   # (name, S(g), Q(g)) per gate
+        if len(self.gates) >= 1 << 16 or any(len(cells) >= 1 << 16 for _, _, cells in self.gates):
+            raise ValueError("check_assignments takes fewer than 2^16 gates of fewer than 2^16 queried cells each")
+        if any(abs(rotation) >= n for _, _, cells in self.gates for _, rotation in cells):
+            raise ValueError("a gate queries a rotation of n rows or more")
+        self.gates_of = {}
+        for g, (_, selectors, _) in enumerate(self.gates):
+            for s in selectors:
+                self.gates_of.setdefault(s, []).append(g)
+        self.regions, self.segments, self.enables = [], [], []      # (name, planner start); (region, column, row, stride, count) x 2
+        self.starts = self.tables = None
+
+    def enter_region(self, name, start):
+        self.regions.append((name, start))
+        return len(self.regions) - 1
+
+    def assign(self, region, column, row, stride, count):
+        if count:
+            self.segments.append((region, column, row, stride if count > 1 else 1, count))
+
+    def enable(self, region, selector, row, stride, count):
+        if count:
+            self.enables.append((region, selector, row, stride if count > 1 else 1, count))
+
+    def build(self):
+        """-> (planes, segments, queries, uses, earlier, words): the tables of the pass, built once; fills `starts`"""
+        if self.tables is not None:
+            return self.tables
+        extents = {}                                  # (region, column) -> [first row, last row]: a plane, in order of appearance
+        for region, column, row, stride, count in self.segments:
+            last = row + (count - 1) * stride
+            box = extents.setdefault((region, column), [row, last])
+            box[0], box[1] = min(box[0], row), max(box[1], last)
+        plane_of, planes, words = {}, np.zeros(len(extents), dtype=COVERAGE_PLANE), 0
+        self.starts = [start for _, start in self.regions]
+        lowest = {}
+        for i, ((region, column), (lo, hi)) in enumerate(extents.items()):
+            plane_of[(region, column)] = i
+            planes[i] = (words, lo, hi - lo + 1)
+            words += (hi - lo + 1 + 31) // 32
+            lowest[region] = min(lowest.get(region, lo), lo)
+        for region, lo in lowest.items():            # dev.rs:286-330: a region starts at its smallest assigned row
+            self.starts[region] = lo
+        if words > COVERAGE_MAX_WORDS:
+            raise ValueError("the regions' extents add up to %d cells: more than the 2^35 bits (4 GiB) of one coverage bit array"
+                             % (32 * words))
+        segments = np.zeros(len(self.segments), dtype=COVERAGE_SEGMENT)
+        if self.segments:
+            segments["plane"] = [plane_of[(region, column)] for region, column, _, _, _ in self.segments]
+            segments["first_row"], segments["stride"], segments["count"] = np.array(
+                [seg[2:] for seg in self.segments], dtype=np.uint64).T
+        queries, query_at, uses, earlier, seen = [], {}, [], [], {}
+        for region, selector, row, stride, count in self.enables:
+            for g in self.gates_of.get(selector, ()):
+                key, cells = (region, g), self.gates[g][2]
+                if key not in query_at:
+                    query_at[key] = len(queries)
+                    queries.extend((plane_of.get((region, column), COVERAGE_NO_PLANE), _COLUMN_ORDER[column[0]] << 28 | column[1],
+                                    rotation, 0) for column, rotation in cells)
+                # the uses of this region and gate so far that may hold one of these rows: the kernel skips what they hold
+                singles, spans = seen.setdefault(key, ({}, []))
+                first_earlier, last = len(earlier), row + (count - 1) * stride
+                if count == 1:
+                    if row in singles:
+                        earlier.append(singles[row])
+                else:
+                    earlier.extend(u for r, u in singles.items() if row <= r <= last and (r - row) % stride == 0)
+                earlier.extend(u for other, u in spans if DeviceColumns._may_overlap((row, stride, count), other))
+                if count == 1:
+                    singles.setdefault(row, len(uses))
+                else:
+                    spans.append(((row, stride, count), len(uses)))
+                uses.append((region, g, query_at[key], len(cells), first_earlier, len(earlier) - first_earlier, row, stride, count))
+        self.tables = (planes, segments, np.array(queries, dtype=COVERAGE_QUERY).reshape(-1),
+                       np.array(uses, dtype=COVERAGE_USE).reshape(-1), np.array(earlier, dtype=np.uint32), max(words, 1))
+        self.cells_marked = int(segments["count"].sum())
+        self.rows_enabled = int(self.tables[3]["count"].sum())
+        return self.tables
+
+    def start(self, region):
+        """the row `offset`s of region `region` count from: its smallest assigned row; the planner's start if it assigned none"""
+        self.build()
+        return self.starts[region]
+
+
+def _sorted_cell_records(records):
+    """(m, 4) u32 records of kind H2_CHECK_CELL by (region, gate, query, row)"""
+    return records[np.lexsort((records[:, 3], records[:, 1], records[:, 2]))] if len(records) else records
+
+
+class HostCoverage(_Coverage):
+    """numpy over the same tables: one boolean per bit of the planes, the uses' rows as index arrays.  The host path of
+    check_assignments (`device` may be None) and the twin the device's result is tested against; failures come out sorted."""
+
+    def mark(self):
+        planes, segments, _, _, _, words = self.build()
+        bits = np.zeros(32 * words, dtype=bool)
+        for plane, _, row, stride, count in segments.tolist():
+            at = 32 * int(planes[plane]["first_word"]) + row - int(planes[plane]["row_lo"])
+            bits[at:at + (count - 1) * stride + 1:stride] = True
+        return bits
+
+    def bitmap(self):
+        """the marked bits as h2_dev_coverage_mark leaves them: u32 words"""
+        return np.ascontiguousarray(np.packbits(self.mark(), bitorder="little")).view("<u4")
+
+    def check(self, cap=None):
+        planes, _, queries, uses, _, _ = self.build()
+        bits, found = self.mark(), []
+        for region, gate, first_query, num_queries, _, _, row, stride, count in uses.tolist():
+            rows = row + stride * np.arange(count, dtype=np.int64)
+            for q in range(num_queries):
+                plane, _, rotation, _ = queries[first_query + q].tolist()
+                cell = (rows + self.n + rotation) % self.n
+                ok = np.zeros(count, dtype=bool)
+                if plane != COVERAGE_NO_PLANE:
+                    first_word, lo, height = planes[plane].tolist()
+                    inside = (cell >= lo) & (cell < lo + height)
+                    ok[inside] = bits[32 * first_word + cell[inside] - lo]
+                bad = cell[~ok]
+                if len(bad):
+                    found.append(np.stack([np.full(len(bad), CHECK_CELL), np.full(len(bad), gate << 16 | q),
+                                           np.full(len(bad), region), bad], axis=1))
+        records = np.unique(np.concatenate(found), axis=0).astype(np.uint32) if found else np.zeros((0, 4), dtype=np.uint32)
+        records = _sorted_cell_records(records)
+        return (records if cap is None else records[:cap]), len(records)
+
+
+class DeviceCoverage(_Coverage):
+    """The bit array on the device: ONE launch of h2_dev_coverage_mark for every queued assignment, ONE launch of
+    h2_dev_coverage_check for every enabled row of every gate (csrc/coverage.hip); the failure block comes back in one
+    download.  `timings` (a dict) receives the seconds of mark, check and download, synchronising between them."""
+
+    def __init__(self, device, cs, n):
+        _Coverage.__init__(self, cs, n)
+        self.D, self.bits, self.mark_launches, self.check_launches = device, None, 0, 0
+
+    def mark(self):
+        if self.bits is not None:
+            return self.bits
+        D, torch = self.D, self.D.torch
+        planes, segments, _, _, _, words = self.build()
+        with torch.cuda.stream(D.tstream):
+            self.bits = torch.zeros(words, dtype=torch.int32, device=D.dev)
+        if len(segments):
+            nbytes = D.L.h2_coverage_scratch_bytes(len(segments), 0, 0, 0, 0)
+            scratch = D.scratch(nbytes)
+            check(D.L.h2_dev_coverage_mark(planes.ctypes.data, len(planes), segments.ctypes.data, len(segments), self.bits.data_ptr(),
+                                           words, scratch.data_ptr(), nbytes, D.stream), "h2_dev_coverage_mark")
+            self.mark_launches += 1
+        return self.bits
+
+    def bitmap(self):
+        with self.D.torch.cuda.stream(self.D.tstream):
+            return self.mark().cpu().numpy().view("<u4")
+
+    def check(self, cap=1024, timings=None):
+        D, torch = self.D, self.D.torch
+        planes, _, queries, uses, earlier, words = self.build()
+        begin = time.perf_counter()
+
+        def phase(name):
+            nonlocal begin
+            if timings is not None:
+                D.sync()
+                timings[name] = timings.get(name, 0.0) + time.perf_counter() - begin
+                begin = time.perf_counter()
+
+        bits = self.mark()
+        phase("mark")
+        with torch.cuda.stream(D.tstream):            # [u64 count, pad][cap x 16 B], as check_witness's block
+            blob = torch.zeros(4 * (cap + 1), dtype=torch.int32, device=D.dev)
+        if len(uses):
+            nbytes = D.L.h2_coverage_scratch_bytes(0, len(planes), len(queries), len(uses), len(earlier))
+            scratch = D.scratch(nbytes)
+            check(D.L.h2_dev_coverage_check(planes.ctypes.data, len(planes), queries.ctypes.data, len(queries), uses.ctypes.data,
+                                            len(uses), earlier.ctypes.data, len(earlier), self.n, bits.data_ptr(), words,
+                                            scratch.data_ptr(), nbytes, blob.data_ptr(), blob.data_ptr() + 16, cap, D.stream),
+                  "h2_dev_coverage_check")
+            self.check_launches += 1
+        phase("check")
+        with torch.cuda.stream(D.tstream):
+            host = blob.cpu().numpy().view(np.uint32)
+        phase("download")
+        total = int(np.ascontiguousarray(host[:2]).view(np.uint64)[0])
+        return _sorted_cell_records(host[4:4 + 4 * cap].reshape(-1, 4)[:min(total, cap)]), total
+
+
 # -- the constraint-system side of an assignment pass -------------------------------------------------------------------------
 class _Assembly:
     """What the layouters assign into (the reference's `Assignment`): keygen keeps fixed cells, copies and constants and drops
@@ -496,6 +707,52 @@ class _Assembly:
 
     def copies_array(self):
         return np.concatenate(self.copies) if self.copies else np.zeros((0, 4), dtype=np.int64)
+
+
+class _CoverageAssembly(_Assembly):
+    """The assembly of check_assignments: it places no values and records, per region, which cells are assigned and which
+    selector rows enabled (dev.rs:600-760).  Towards missing values it is keygen -- advice cells need none, fixed cells do --
+    and it keeps keygen's NotEnoughRowsAvailable and BoundsFailure checks.  What happens outside every region (a table's
+    fill_from_row, the planners' constants) belongs to none (dev.rs:691, :729: current_region is None)."""
+
+    def __init__(self, cs, k, coverage):
+        _Assembly.__init__(self, cs, k, True, None)
+        self.coverage, self.region = coverage, None
+
+    def enter_region(self, name, start):
+        self.region = self.coverage.enter_region(name, start)
+
+    def exit_region(self):
+        self.region = None
+
+    def assign(self, column, row, stride, vals):
+        if vals.count == 0:
+            return
+        self._check(column, row, row + (vals.count - 1) * stride)
+        if column[0] == "fixed" and vals.kind == "none":
+            raise SynthesisError("no value for %s[%d]" % column)
+        if self.region is not None:
+            self.coverage.assign(self.region, column, row, stride, vals.count)
+
+    def enable_selector(self, selector, row, stride, count):
+        if count == 0:
+            return
+        if selector.index >= self.cs.num_selectors:
+            raise BoundsFailure("no selector %d" % selector.index)
+        if row < 0 or row + (count - 1) * stride >= self.usable:
+            raise NotEnoughRowsAvailable(self.k)
+        self.coverage.enable(self.region, selector.index, row, stride, count)
+
+    def fill_from_row(self, column, row, value):
+        if row >= self.usable:
+            raise NotEnoughRowsAvailable(self.k)
+
+    def copy(self, left, lrows, right, rrows):
+        for column, rows in ((left, lrows), (right, rrows)):
+            if len(rows):
+                self._check(column, int(rows.min()), int(rows.max()))
+            if len(lrows) and column not in self.positions:
+                raise ColumnNotInPermutation(column)
 
 
 # -- what a circuit's `synthesize` sees ---------------------------------------------------------------------------------------
@@ -635,20 +892,36 @@ class Layouter:
         self._asm, self._starts, self._shapes = assembly, starts, shapes
         self._regions, self._tables, self.constants = 0, set(), []
 
+    def _announced(self, name, start, body):
+        """`body()` between enter_region(name, start) and exit_region() of an assembly that tracks regions (the coverage
+        assembly); tables are regions too (flat.rs:188, v1.rs:367)"""
+        if not hasattr(self._asm, "enter_region"):
+            return body()
+        self._asm.enter_region(name, start)
+        try:
+            return body()
+        finally:
+            self._asm.exit_region()
+
     def assign_region(self, name, fn):
         index = self._regions
         self._regions += 1
         if self._shapes is not None:
             self._shapes.append(_Shape(index))
             return fn(Region(self._asm, 0, self.constants, self._shapes[-1]))
-        return fn(Region(self._asm, 0 if self._starts is None else self._starts[index], self.constants))
+        start = 0 if self._starts is None else self._starts[index]
+        return self._announced(name, start, lambda: fn(Region(self._asm, start, self.constants)))
 
     def assign_table(self, name, fn):
         if self._shapes is not None:                  # v1.rs:209: tables take no part in the measurement
             return
-        table = Table(self._asm, self._tables)
-        fn(table)
-        table.finish()
+
+        def body():
+            table = Table(self._asm, self._tables)
+            fn(table)
+            table.finish()
+
+        self._announced(name, 0, body)
 
     def constrain_instance(self, cells, instance_column, row):
         if self._shapes is None:
@@ -816,6 +1089,23 @@ def synthesize_witness(device, circuit, cs_or_pk, k, planner=None, resident=True
         stats.update(cells_placed=columns.cells_placed, flushes=columns.flushes, pack_seconds=columns.pack_seconds,
                      flush_seconds=columns.flush_seconds, kernel_ms=columns.kernel_ms)
     return advice, dict(assembly.first_unassigned)
+
+
+def synthesize_coverage(device, circuit, k, planner=None, resident=True):
+    """configure + one assignment pass of `circuit` that keeps WHICH cells each region assigns and which selector rows it
+    enables, and no value -> the coverage object: DeviceCoverage (`resident`: the bits live on `device`) or HostCoverage
+    (`device` may be None), with the region table (`regions`: (name, planner start) in the order of the assign_region /
+    assign_table calls; `start(r)`) and the gate table (`gates`) of the constraint system as `configure` leaves it, selectors
+    uncompressed.  `check(cap)` runs the check; check.check_assignments wraps it."""
+    cs = ConstraintSystem(type(circuit).__name__)
+    config = circuit.configure(cs)
+    n = 1 << k
+    if n < cs.minimum_rows():
+        raise NotEnoughRowsAvailable(k)
+    coverage = DeviceCoverage(device, cs, n) if resident else HostCoverage(cs, n)
+    _planner(circuit, planner).synthesize(_CoverageAssembly(cs, k, coverage), circuit, config)
+    coverage.build()
+    return coverage
 
 
 def region_starts(circuit, planner=None):

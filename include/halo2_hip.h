@@ -862,6 +862,7 @@ int h2_dev_max_scalar_bits(const void *const *d_cols, size_t count, size_t n, vo
  *                                     usable rows (the reference reports rows of its sorted tuples instead: dev.rs:1209-1262,
  *                                     an order that compression destroys)
  *   (COPY, column, 0, row)            value(column, row) != value(mapping(column, row))
+ *   (CELL, gate << 16 | query, region, cell_row)   h2_dev_coverage_check below: a cell an enabled gate reads, unassigned
  * Every entry adds to a caller-zeroed device u64 *d_count and appends to a caller-owned device buffer of `cap` records: one
  * agent-scope atomic per wave, a record written only when its slot is < cap -- the count is exact after the buffer fills,
  * which records were kept then is not specified.  One buffer may collect every check of a witness: one download.
@@ -871,7 +872,7 @@ int h2_dev_max_scalar_bits(const void *const *d_cols, size_t count, size_t n, vo
  * (Schwartz-Zippel); copies and single-column lookups are exact.
  * Every entry is asynchronous on `stream` and returns H2_ERR_INVALID for bad arguments without touching the device. */
 typedef struct { uint32_t kind, index, sub, row; } h2_check_record;
-enum { H2_CHECK_GATE = 0, H2_CHECK_LOOKUP = 1, H2_CHECK_SHUFFLE = 2, H2_CHECK_COPY = 3 };
+enum { H2_CHECK_GATE = 0, H2_CHECK_LOOKUP = 1, H2_CHECK_SHUFFLE = 2, H2_CHECK_COPY = 3, H2_CHECK_CELL = 4 };
 /* device scratch (bytes) of h2_dev_check_lookup / h2_dev_check_shuffle for columns of n rows */
 size_t h2_check_scratch_bytes(size_t n);
 /* The screen's compaction: appends every row r < usable_rows with d_values[r] != 0 to d_rows (room for usable_rows u32) and
@@ -896,6 +897,77 @@ int h2_dev_check_shuffle(const void *d_input, const void *d_shuffle, size_t usab
  * reported as a failure of its cell. */
 int h2_dev_check_copies(const void *const *d_columns, size_t n_columns, const uint32_t *d_map_col, const uint32_t *d_map_row,
                         size_t n, uint32_t circuit, uint64_t *d_count, h2_check_record *d_records, size_t cap, void *stream);
+
+/* ---- checking assignments (MockProver's VerifyFailure::CellNotAssigned, dev.rs:959-1000) -------------------------------------
+ * Which cells each REGION of an assignment pass assigned, one bit per cell, and every cell an enabled gate reads tested
+ * against the bits of the region that enabled it ("Checking assignments").
+ *   plane     one (region, column) pair: the rows [row_lo, row_lo + rows) the region spans in that column.  Its bits start at
+ *             u32 word `first_word` of ONE bit array of `words` words that holds every plane, each on a word boundary; bit
+ *             (r - row_lo) % 32 of word first_word + (r - row_lo) / 32 is row r.  The CALLER zeroes the array before the mark.
+ *   segment   `count` assigned cells of a plane, `stride` rows apart from the absolute row `first_row` on.
+ *   query     one cell a gate reads, as seen from one region: the region's plane of the cell's column, or
+ *             H2_COVERAGE_NO_PLANE where the region has none (every such cell is unassigned), and the rotation, |rotation| < n.
+ *             `column` is for whoever reads the table; the library does not look at it.
+ *   use       one segment of rows a region enabled a gate on: rows first_row, first_row + stride, ... (`count` of them, all
+ *             below n), the gate (< 2^16) and its queries [first_query, first_query + num_queries), num_queries < 2^16.  Rows
+ *             that one of the EARLIER uses earlier[first_earlier .. first_earlier + num_earlier) (indices into `uses`, each
+ *             below the use's own) holds are skipped: the caller lists there the uses of the same region and gate that may
+ *             share a row with this one, so that no failure is reported twice.
+ *   h2_dev_coverage_mark   sets the bit of every cell of `count` segments in ONE launch: stride-1 segments word by word (one
+ *                          atomic OR per 32 cells), the others cell by cell.
+ *   h2_dev_coverage_check  for every row of every use and every query q of its gate: cell_row = (row + n + rotation) mod n;
+ *                          unless the query's plane spans cell_row and holds its bit, the record
+ *                          (H2_CHECK_CELL, gate << 16 | q - first_query, region, cell_row) is appended to the block of the
+ *                          witness checks above (caller-zeroed *d_count, `cap` records), in ONE launch.
+ *   h2_coverage_mark / h2_coverage_check   the same over a HOST bit array, count and records, on the host.
+ * d_scratch: h2_coverage_scratch_bytes(segments, planes, queries, uses, earlier) bytes, 16-byte aligned (a mark asks with the
+ * last four 0, a check with segments 0).  The tables are HOST arrays, read before the call returns; the device calls are
+ * asynchronous on `stream`.  All return H2_ERR_INVALID without touching a device, h2_last_error naming the call and the
+ * reason, for a null or misaligned pointer, n outside 1 .. 2^31, words above 2^30, stride 0, a segment outside its plane, a
+ * plane outside the bit array, a plane, query or earlier index out of range, a gate or a query count of 2^16 or more, a use
+ * whose last row is not below n, or too small a scratch. */
+#define H2_COVERAGE_NO_PLANE 0xffffffffu
+typedef struct {
+    uint64_t first_word;
+    uint32_t row_lo;
+    uint32_t rows;
+} h2_coverage_plane;
+typedef struct {
+    uint32_t plane;
+    uint32_t reserved;
+    uint64_t first_row;
+    uint64_t stride;
+    uint64_t count;
+} h2_coverage_segment;
+typedef struct {
+    uint32_t plane;
+    uint32_t column;
+    int32_t rotation;
+    uint32_t reserved;
+} h2_coverage_query;
+typedef struct {
+    uint32_t region;
+    uint32_t gate;
+    uint32_t first_query;
+    uint32_t num_queries;
+    uint32_t first_earlier;
+    uint32_t num_earlier;
+    uint64_t first_row;
+    uint64_t stride;
+    uint64_t count;
+} h2_coverage_use;
+size_t h2_coverage_scratch_bytes(size_t segments, size_t planes, size_t queries, size_t uses, size_t earlier);
+int h2_dev_coverage_mark(const h2_coverage_plane *planes, size_t num_planes, const h2_coverage_segment *segments, size_t count,
+                         void *d_bits, size_t words, void *d_scratch, size_t scratch_bytes, void *stream);
+int h2_dev_coverage_check(const h2_coverage_plane *planes, size_t num_planes, const h2_coverage_query *queries,
+                          size_t num_queries, const h2_coverage_use *uses, size_t num_uses, const uint32_t *earlier,
+                          size_t num_earlier, size_t n, const void *d_bits, size_t words, void *d_scratch, size_t scratch_bytes,
+                          uint64_t *d_count, h2_check_record *d_records, size_t cap, void *stream);
+int h2_coverage_mark(const h2_coverage_plane *planes, size_t num_planes, const h2_coverage_segment *segments, size_t count,
+                     void *bits, size_t words);
+int h2_coverage_check(const h2_coverage_plane *planes, size_t num_planes, const h2_coverage_query *queries, size_t num_queries,
+                      const h2_coverage_use *uses, size_t num_uses, const uint32_t *earlier, size_t num_earlier, size_t n,
+                      const void *bits, size_t words, uint64_t *count, h2_check_record *records, size_t cap);
 
 /* ---- screening the points of an SRS ------------------------------------------------------------------------------------
  * The reference takes the points of its parameters as they come: Params::read unwraps `from_bytes` per point
