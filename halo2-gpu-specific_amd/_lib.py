@@ -142,6 +142,9 @@ SYMBOLS = {
     "h2_dev_coverage_check": (ctypes.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp]),
     "h2_coverage_mark": (ctypes.c_int, [_vp, _sz, _vp, _sz, _vp, _sz]),
     "h2_coverage_check": (ctypes.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _sz]),
+    "h2_values_limits": (ctypes.c_int, [_vp]),
+    "h2_dev_values_eval": (ctypes.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "h2_values_eval": (ctypes.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz]),
     "h2_check_scratch_bytes": (_sz, [_sz]),
     "h2_dev_check_nonzero_rows": (ctypes.c_int, [_vp, _sz, _vp, _vp, _vp]),
     "h2_dev_check_gates": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _sz, _vp]),

@@ -12,6 +12,7 @@
   SimpleExample      examples/simple-example.rs:257-312       V1, one simple selector, a constant, a public input
   TwoChip            examples/two-chip.rs:473-509             V1, two simple selectors (an add and a mul chip)
   SelectorGates      simple, complex and unused selectors enabled in bulk, strided (no .rs text)
+  ShuffleGatesValues ShuffleGates with its witness computed on the device by Values (values.py), at any height
 
 Where an example assigns cell by cell in a loop, the class assigns the loop's range at once; the calls are otherwise the
 example's, in its order."""
@@ -20,6 +21,7 @@ import numpy as np
 from . import circuits
 from .circuit import R_MOD, Constant
 from .synthesis import V1, Circuit, FlatFloorPlanner
+from .values import Value
 
 
 class _Config:
@@ -522,3 +524,70 @@ class SelectorGates(Circuit):
 
         layouter.assign_region("rows", body)
         layouter.assign_table("range table", lambda table: table.assign_cell(config.table, 0, np.arange(self.TABLE, dtype=np.uint64)))
+
+
+class ShuffleGatesValues(Circuit):
+    """ShuffleGates with its witness computed by Values (values.py): the random originals come from the same seeded stream as
+    circuits.shuffle_gates_witness, the shuffle is a `take`, and the running product is
+    z = ((compress(original) + beta) / (compress(shuffled) + beta)).cumprod() -- one fused launch for the denominators, one
+    batch inversion, one launch for the quotients and one scan, at any height up to usable - 1.  Keygen passes unknowns:
+    there is no branch on a witness flag.  `device`: where the Values live (None: the host backend)."""
+    planner = V1
+
+    def __init__(self, k, width=4, height=32, theta=111, beta=222, seed=0x5348554646, device=None, originals=None):
+        self.k, self.width, self.height, self.theta, self.beta, self.seed, self.device = k, width, height, theta, beta, seed, device
+        self.originals = originals            # [Value] * width, unknown at keygen; drawn on first use otherwise
+        self._columns = None
+
+    def without_witnesses(self):
+        return ShuffleGatesValues(self.k, self.width, self.height, self.theta, self.beta, self.seed, self.device,
+                                  [Value.unknown(self.height)] * self.width)
+
+    configure = ShuffleGates.configure
+
+    def witness_inputs(self):
+        """the originals and the shuffle's order, as circuits.shuffle_gates_witness draws them"""
+        import random
+
+        rnd = random.Random(self.seed)
+        H = self.height
+        original = [np.array([rnd.randrange(R_MOD).to_bytes(32, "little") for _ in range(H)], dtype="V32").view(np.uint64).reshape(H, 4)
+                    for _ in range(self.width)]
+        order = list(range(H))
+        for row in range(H - 1, 0, -1):
+            other = rnd.getrandbits(32) % row
+            order[row], order[other] = order[other], order[row]
+        return [Value.from_limbs(self.device, col) for col in original], np.array(order, dtype=np.int64)
+
+    def columns(self):
+        """[original] * W + [shuffled] * W + [z] as Values, built once"""
+        if self._columns is None:
+            order = None
+            if self.originals is None:
+                self.originals, order = self.witness_inputs()
+            original = self.originals
+            shuffled = [col.take(order) if col.known else col for col in original]
+
+            def compress(cols):
+                acc = cols[0]
+                for col in cols[1:]:
+                    acc = acc * self.theta + col
+                return acc
+
+            z = ((compress(original) + self.beta) / (compress(shuffled) + self.beta)).cumprod()
+            self._columns = list(original) + shuffled + [z]
+        return self._columns
+
+    def synthesize(self, config, layouter):
+        H, W = self.height, self.width
+        columns = self.columns()
+
+        def body(region):
+            region.assign_fixed(config.q_first, 0, 1)
+            region.assign_fixed(config.q_last, H, 1)
+            region.assign_fixed(config.q_shuffle, 0, 1, count=H)
+            for i, column in enumerate(config.original + config.shuffled):
+                region.assign_advice(column, 0, columns[i], count=H)
+            return region.assign_advice(config.z, 0, columns[2 * W], count=H + 1)
+
+        return layouter.assign_region("Shuffle original into shuffled", body)

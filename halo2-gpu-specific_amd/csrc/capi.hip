@@ -26,6 +26,7 @@
 #include "resident.hpp"
 #include "scan.hpp"
 #include "srscheck.hpp"
+#include "values.hpp"
 
 using namespace h2;
 
@@ -1688,6 +1689,36 @@ int h2_coverage_check(const h2_coverage_plane* planes, size_t num_planes, const 
                                                    bits, words, false, nullptr, 0, count, records, cap))
         return bad((std::string("h2_coverage_check: ") + what).c_str());
     coverage_check_host(planes, queries, uses, num_uses, earlier, n, (const uint32_t*)bits, count, records, cap);
+    return H2_OK;
+}
+
+// ------------------------------------------------------------------ values: witness arithmetic, one fused launch (values.hip)
+int h2_values_limits(h2_values_caps* out) {
+    if (!out) return bad("h2_values_limits: null argument");
+    values_caps(out);
+    return H2_OK;
+}
+
+int h2_dev_values_eval(const h2_values_leaf* leaves, size_t num_leaves, const uint64_t* constants, size_t num_constants,
+                       const h2_values_op* ops, size_t num_ops, const h2_values_output* outputs, size_t num_outputs, size_t m,
+                       void* stream) {
+    if (m == 0) return H2_OK;
+    ValProgram P;
+    if (const char* what = values_lower(leaves, num_leaves, constants, num_constants, ops, num_ops, outputs, num_outputs, m, true, &P))
+        return bad((std::string("h2_dev_values_eval: ") + what).c_str());
+    return guarded([&] {
+        DeviceCtx* ctx = current_ctx();
+        return values_eval_launch(P, m, pick_stream(ctx, stream));
+    });
+}
+
+int h2_values_eval(const h2_values_leaf* leaves, size_t num_leaves, const uint64_t* constants, size_t num_constants,
+                   const h2_values_op* ops, size_t num_ops, const h2_values_output* outputs, size_t num_outputs, size_t m) {
+    if (m == 0) return H2_OK;
+    ValProgram P;
+    if (const char* what = values_lower(leaves, num_leaves, constants, num_constants, ops, num_ops, outputs, num_outputs, m, false, &P))
+        return bad((std::string("h2_values_eval: ") + what).c_str());
+    values_eval_host(P, m);
     return H2_OK;
 }
 

@@ -43,6 +43,7 @@ from .synthesis import (AssignedCells, BoundsFailure, Circuit, ColumnNotInPermut
                         FlatFloorPlanner, HostColumns, HostCoverage, Layouter, NotEnoughColumnsForConstants, NotEnoughRowsAvailable, Region, SynthesisError, Table, V1,
                         region_starts, synthesize_coverage, synthesize_keygen, synthesize_witness)
 from .transcript import Blake2bWrite, R_MOD, fr_to_mont_limbs, g1_add_affine
+from .values import Value  # noqa: F401
 from .witness import (RC_FORM_CANONICAL, RC_FORM_COMPACT, RC_FORM_MONTGOMERY, RC_IN_USE, RC_NO_FIT, RC_OK, RC_OUT_OF_RANGE,  # noqa: F401
                       RC_STATUS_WORDS, RC_UNSUPPORTED, _compress, _instance_columns, _witness_sets, complete_range_check_witness,
                       complete_range_check_witness_device, range_check_assigner, range_check_complete_device)

@@ -10,7 +10,8 @@ assemblies the assignments end up in.
 The front end is a BULK one: an assignment covers a range of cells (`count` cells `stride` rows apart), never one Python call
 per cell of a 2^22-row column.  Values are a Python integer (one cell, or the same value for `count` cells), a 1-D u64 array
 (compact cells: 8 bytes each), an (m, 4) u64 array (canonical cells), a device tensor of either shape (values torch code
-computed on the device: they never visit the host), or None (keygen, `without_witnesses`).
+computed on the device: they never visit the host), a `Value` (values.py: field arithmetic computed on the device; an unknown
+Value is None with its count), or None (keygen, `without_witnesses`).
 
 Selectors (`cs.selector()`, `Region.enable_selector`) are kept as one bit per row -- `HostSelectors` in numpy, `DeviceSelectors`
 as device bitmaps (csrc/selectors.hip) -- and become fixed columns after the planner has run: the conflict matrix of the
@@ -32,6 +33,7 @@ import numpy as np
 
 from ._lib import check
 from .circuit import R_MOD, ConstraintSystem, gate_cells
+from .values import Value
 
 PLACE_FORM_CANONICAL, PLACE_FORM_COMPACT, PLACE_FORM_BROADCAST = 0, 1, 2               # H2_PLACE_FORM_*
 PLACE_OUT_CANONICAL, PLACE_OUT_MONTGOMERY = 0, 1                                       # H2_PLACE_OUT_*
@@ -92,11 +94,20 @@ def _limbs(v):
 
 
 class _Values:
-    """one assignment's values: kind = "none" | "int" | "host" | "device"; compact = one u64 per cell"""
+    """one assignment's values: kind = "none" | "int" | "host" | "device"; compact = one u64 per cell.  A known Value is
+    canonical cells of its backend, materialised when `data` is first read (a pass that keeps no values never does)"""
 
     def __init__(self, values, count):
-        self.data, self.compact = values, False
-        if values is None:
+        self._lazy, self.data, self.compact = None, values, False
+        if isinstance(values, Value):
+            if count is not None and count != values.count:
+                raise ValueError("%d values for %d cells" % (values.count, count))
+            self.count = values.count
+            if values.known:
+                self.kind, self._lazy = "host" if values.device is None else "device", values
+            else:
+                self.kind, self.data = "none", None
+        elif values is None:
             self.kind, self.count = "none", 1 if count is None else count
         elif isinstance(values, (int, np.integer)):
             self.kind, self.data, self.count = "int", int(values) % R_MOD, 1 if count is None else count
@@ -115,6 +126,16 @@ class _Values:
         if count is not None and self.kind in ("host", "device") and count != self.count:
             raise ValueError("%d values for %d cells" % (self.count, count))
 
+    @property
+    def data(self):
+        if self._lazy is not None:
+            self._data, self._lazy = self._lazy.tensor(), None
+        return self._data
+
+    @data.setter
+    def data(self, values):
+        self._data = values
+
     def first(self):
         """the first value as an integer (a table column's default)"""
         if self.kind == "int":
@@ -129,10 +150,14 @@ class _Values:
 
 class AssignedCells:
     """`count` assigned cells of one column, `stride` rows apart from `row` on: what an assignment returns and what the
-    constraints of a region take.  Slicing gives the sub-range."""
+    constraints of a region take.  Slicing gives the sub-range.  `value()`: the Value the cells were assigned from
+    (`AssignedCell::value()`, circuit.rs), unknown when they were assigned from anything else."""
 
-    def __init__(self, column, row, count=1, stride=1):
-        self.column, self.row, self.count, self.stride = column, row, count, stride
+    def __init__(self, column, row, count=1, stride=1, value=None):
+        self.column, self.row, self.count, self.stride, self._value = column, row, count, stride, value
+
+    def value(self):
+        return self._value if self._value is not None else Value.unknown(self.count)
 
     def __len__(self):
         return self.count
@@ -142,10 +167,12 @@ class AssignedCells:
             start, stop, step = key.indices(self.count)
             if step < 1:
                 raise ValueError("cells are sliced forwards")
-            return AssignedCells(self.column, self.row + start * self.stride, len(range(start, stop, step)), self.stride * step)
+            return AssignedCells(self.column, self.row + start * self.stride, len(range(start, stop, step)), self.stride * step,
+                                 None if self._value is None else self._value[key])
         if not -self.count <= key < self.count:
             raise IndexError(key)
-        return AssignedCells(self.column, self.row + (key % self.count) * self.stride, 1, 1)
+        return AssignedCells(self.column, self.row + (key % self.count) * self.stride, 1, 1,
+                             None if self._value is None else self._value[key])
 
     def rows(self):
         return self.row + self.stride * np.arange(self.count, dtype=np.int64)
@@ -788,7 +815,7 @@ class Region:
                 self._shape.row_count = max(self._shape.row_count, offset + (vals.count - 1) * stride + 1)
         else:
             self._asm.assign(column, self._start + offset, stride, vals)
-        return AssignedCells(column, self._start + offset, vals.count, stride)
+        return AssignedCells(column, self._start + offset, vals.count, stride, values if isinstance(values, Value) else None)
 
     def assign_advice(self, column, offset, values, stride=1, count=None):
         """`values` to the cells offset, offset + stride, ... of an advice column; an integer with `count`: that value in
@@ -811,6 +838,7 @@ class Region:
 
     def assign_advice_from_constant(self, column, offset, constant):
         cells = self.assign_advice(column, offset, int(constant))
+        cells._value = Value.full(None, 1, int(constant))
         self.constrain_constant(cells, constant)
         return cells
 

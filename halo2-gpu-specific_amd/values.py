@@ -1,0 +1,865 @@
+"""`Value`: bulk arithmetic over the BN254 scalar field for the bodies of `synthesize` -- the reference's `Value<F>`,
+`AssignedCell::value()` and `Assigned<F>` (circuit.rs, plonk/assigned.rs), for ranges of cells instead of one cell.
+
+A Value is a lazily evaluated array of `count` field elements bound to a `Device` (or to no device: the host backend of the
+CPU suite).  Operators build an expression; nothing runs until `tensor()`, `to_ints()`, `Value.materialize([...])` or an
+assignment asks for the elements.  Then the compiler below turns the expression into as few launches of the fused evaluator
+(csrc/values.hip, h2_dev_values_eval; DESIGN.md 3b, "Computing a witness") as its caps allow:
+
+  common subexpressions   equal subexpressions of the Values materialised together are evaluated once (hash-consing, with
+                          the operands of + and * in one order)
+  evaluation order        Sethi-Ullman: the operand that needs more slots first
+  slots                   assigned by last use, the lowest free slot first (slot 0 is a register in the kernel); a result
+                          that only the next op reads takes no slot (the kernel's `last`)
+  over the caps           the largest subexpression that fits a launch is materialised on its own and read back as a leaf
+  slices                  a[i:j:s] is a view; it reaches the leaves as an offset and a stride and costs nothing
+  inversions              staged by depth: every denominator of one depth is written into one buffer, inverted by ONE
+                          h2_dev_batch_invert (Montgomery residues in and out, zeros stay zero) and read back as leaves --
+                          k nested levels of division cost k + 1 evaluator launches and k inversions (per distinct length,
+                          and per `outputs` denominators of one length)
+  scans, concat, take     their operands are materialised first; their results are leaves
+
+Device work is allocated and launched under the device's compute stream, as check.py does, so that an assignment's flush
+(DeviceColumns._flush) sees finished values.  `device.values_launches` / `device.values_inversions` count the calls.
+"""
+import numpy as np
+
+from ._lib import check, lib
+from .circuit import R_MOD
+from .domain import _fr
+
+FORM_CANONICAL, FORM_MONTGOMERY, FORM_COMPACT = 0, 1, 2                                  # H2_ASSIGNED_FORM_*
+OP_CODES = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "neg": 4, "select": 5, "iszero": 6}  # H2_VALUES_*
+KIND_LEAF, KIND_CONST, KIND_SLOT, KIND_LAST = 0, 1, 2, 3                                 # H2_VALUES_LEAF / CONST / SLOT / LAST
+NO_SLOT = 0xFFFFFFFF                                                                     # H2_VALUES_NO_SLOT
+# h2_values_leaf, h2_values_op, h2_values_output, h2_values_caps
+VALUES_LEAF = np.dtype([("ptr", "<u8"), ("first", "<u8"), ("stride", "<u8"), ("len", "<u8"), ("form", "<u4"), ("reserved", "<u4")])
+VALUES_OP = np.dtype([("op", "<u4"), ("dst", "<u4"), ("a", "<u4"), ("b", "<u4"), ("c", "<u4")])
+VALUES_OUTPUT = np.dtype([("ptr", "<u8"), ("first", "<u8"), ("slot", "<u4"), ("form", "<u4")])
+VALUES_CAPS = np.dtype([("leaves", "<u4"), ("ops", "<u4"), ("constants", "<u4"), ("outputs", "<u4"), ("slots", "<u4"),
+                        ("blocks", "<u4"), ("threads", "<u4"), ("reserved", "<u4")])
+_MASK64 = (1 << 64) - 1
+_R = (1 << 256) % R_MOD
+_R_INV = pow(_R, -1, R_MOD)
+_LIMITS = None
+
+
+def limits():
+    """h2_values_limits as a dict: the caps of one launch (leaves, ops, constants, outputs, slots) and its grid (blocks, threads)"""
+    global _LIMITS
+    if _LIMITS is None:
+        caps = np.zeros(1, dtype=VALUES_CAPS)
+        check(lib().h2_values_limits(caps.ctypes.data), "h2_values_limits")
+        _LIMITS = {name: int(caps[0][name]) for name in VALUES_CAPS.names if name != "reserved"}
+    return _LIMITS
+
+
+def ints_to_limbs(values):
+    return np.array([[(v >> (64 * j)) & _MASK64 for j in range(4)] for v in values], dtype=np.uint64).reshape(len(values), 4)
+
+
+def limbs_to_ints(a):
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    return [int.from_bytes(row.tobytes(), "little") for row in a]
+
+
+# -- backends ----------------------------------------------------------------------------------------------------------------
+class _HostBackend:
+    """numpy buffers, h2_values_eval, Python integers for inversions and scans: the test oracle's second opinion"""
+    device = None
+
+    def __init__(self):
+        self.values_launches = self.values_inversions = 0
+
+    def count(self, launches=0, inversions=0):
+        self.values_launches += launches
+        self.values_inversions += inversions
+
+    def empty(self, n):
+        return np.zeros((n, 4), dtype=np.uint64)
+
+    def data(self, buf):
+        if not isinstance(buf.data, np.ndarray):
+            raise TypeError("a Value without a device holds numpy arrays")
+        return buf.data
+
+    def ptr(self, a):
+        return a.ctypes.data
+
+    def eval(self, *tables):
+        check(lib().h2_values_eval(*tables), "h2_values_eval")
+
+    def invert(self, a):
+        """Montgomery residues, in place; zeros stay zero"""
+        ints = [v * _R_INV % R_MOD for v in limbs_to_ints(a)]
+        a[:] = ints_to_limbs([pow(v, -1, R_MOD) * _R % R_MOD if v else 0 for v in ints])
+
+    def zero_rows(self, a):
+        return np.flatnonzero(~a.any(axis=1))
+
+    def scan(self, f, m, init, product):
+        ints, z = [v * _R_INV % R_MOD for v in limbs_to_ints(f[:m])], [init % R_MOD]
+        for v in ints:
+            z.append(z[-1] * v % R_MOD if product else (z[-1] + v) % R_MOD)
+        return ints_to_limbs([v * _R % R_MOD for v in z])
+
+    def gather(self, a, indices):
+        return np.ascontiguousarray(a[np.asarray(indices, dtype=np.int64)])
+
+    def upload(self, a):
+        return np.ascontiguousarray(a)
+
+    def download(self, a):
+        return a
+
+    def publish(self):
+        pass
+
+
+HOST = _HostBackend()
+
+
+class _DeviceBackend:
+    def __init__(self, device):
+        self.device = self.D = device
+        device.__dict__.setdefault("values_launches", 0)
+        device.__dict__.setdefault("values_inversions", 0)
+
+    def count(self, launches=0, inversions=0):
+        self.D.values_launches += launches
+        self.D.values_inversions += inversions
+
+    def empty(self, n):
+        return self.D.empty(n)
+
+    def data(self, buf):
+        D, torch = self.D, self.D.torch
+        if isinstance(buf.data, np.ndarray):                 # a host array crosses PCIe once, compact cells at 8 bytes
+            buf.data, buf.ordered = D.upload(np.ascontiguousarray(buf.data), widen=False), True
+        elif not buf.ordered:                                # a tensor of the caller's stream: ordered before our launches
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(D.dev))
+            D.tstream.wait_event(ready)
+            buf.data.record_stream(D.tstream)
+            buf.ordered = True
+        return buf.data
+
+    def ptr(self, t):
+        return t.data_ptr()
+
+    def eval(self, *tables):
+        check(self.D.L.h2_dev_values_eval(*(tables + (self.D.stream,))), "h2_dev_values_eval")
+
+    def invert(self, t):
+        n = t.shape[0]
+        check(self.D.L.h2_dev_batch_invert(t.data_ptr(), self.D.empty(n).data_ptr(), n, self.D.stream), "h2_dev_batch_invert")
+
+    def zero_rows(self, t):
+        with self.D.torch.cuda.stream(self.D.tstream):
+            return (t == 0).all(dim=1).nonzero().flatten().cpu().numpy()
+
+    def scan(self, f, m, init, product):
+        z = self.D.empty(m + 1)
+        kernel = self.D.L.h2_dev_prefix_product if product else self.D.L.h2_dev_prefix_sum
+        check(kernel(f.data_ptr() if m else None, m + 1, _fr(init), z.data_ptr(), self.D.stream), "h2_dev_prefix_scan")
+        return z
+
+    def gather(self, t, indices):
+        torch = self.D.torch
+        with torch.cuda.stream(self.D.tstream):
+            if not torch.is_tensor(indices):
+                indices = torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int64)).to(self.D.dev)
+            return t[indices.to(torch.int64)].contiguous()
+
+    def upload(self, a):
+        return self.D.upload(np.ascontiguousarray(a), widen=False)
+
+    def download(self, t):
+        return self.D.download(t)
+
+    def publish(self):
+        """what was launched on the compute stream is ordered before whatever the caller's stream does next"""
+        torch = self.D.torch
+        caller = torch.cuda.current_stream(self.D.dev)
+        if caller != self.D.tstream:
+            done = torch.cuda.Event()
+            done.record(self.D.tstream)
+            caller.wait_event(done)
+
+
+def _backend(device):
+    if device is None:
+        return HOST
+    be = device.__dict__.get("_values_backend")
+    if be is None:
+        be = device.__dict__["_values_backend"] = _DeviceBackend(device)
+    return be
+
+
+# -- expressions -------------------------------------------------------------------------------------------------------------
+class _Buffer:
+    """`length` field elements a leaf reads: a host array, a device tensor, or (data None) the result of `pending`"""
+    __slots__ = ("data", "form", "length", "pending", "ordered")
+
+    def __init__(self, data, form, length, pending=None, ordered=False):
+        self.data, self.form, self.length, self.pending, self.ordered = data, form, length, pending, ordered
+
+
+class _Pending:
+    """what an unresolved buffer waits for: kind = inv | cumprod | cumsum | concat | take"""
+    __slots__ = ("kind", "args", "extra")
+
+    def __init__(self, kind, args, extra=None):
+        self.kind, self.args, self.extra = kind, args, extra
+
+
+class _Node:
+    """kind = leaf (buffer) | const (value) | an op of OP_CODES (args: Values); `count` elements before any view"""
+    __slots__ = ("kind", "args", "count", "buffer", "value", "cache")
+
+    def __init__(self, kind, count, args=(), buffer=None, value=None):
+        self.kind, self.count, self.args, self.buffer, self.value, self.cache = kind, count, args, buffer, value, None
+
+
+class Value:
+    """`count` field elements, lazily evaluated; see the module's docstring"""
+    __slots__ = ("device", "count", "_node", "_first", "_step", "_cache")
+
+    def __init__(self, device, count, node, first=0, step=1):
+        self.device, self.count, self._node, self._first, self._step, self._cache = device, count, node, first, step, {}
+
+    # -- constructors ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _leaf(device, data, form, length):
+        return Value(device, length, _Node("leaf", length, buffer=_Buffer(data, form, length)))
+
+    @staticmethod
+    def from_u64(device, values):
+        """compact cells: a 1-D u64 array (or anything numpy makes one of), or a 1-D 64-bit device tensor"""
+        if hasattr(values, "data_ptr"):
+            if values.dim() != 1 or values.element_size() != 8:
+                raise TypeError("compact cells are a 1-D 64-bit tensor")
+            return Value._leaf(device, values.contiguous(), FORM_COMPACT, values.shape[0])
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        if values.ndim != 1:
+            raise TypeError("compact cells are a 1-D u64 array")
+        return Value._leaf(device, values, FORM_COMPACT, len(values))
+
+    @staticmethod
+    def from_limbs(device, values, montgomery=False):
+        """(m, 4) u64 cells: canonical (any 256-bit integer; reduced on load) or reduced Montgomery residues"""
+        form = FORM_MONTGOMERY if montgomery else FORM_CANONICAL
+        if hasattr(values, "data_ptr"):
+            if values.dim() != 2 or values.shape[1] != 4 or values.element_size() != 8:
+                raise TypeError("cells are an (m, 4) 64-bit tensor")
+            return Value._leaf(device, values.contiguous(), form, values.shape[0])
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        if values.ndim != 2 or values.shape[1] != 4:
+            raise TypeError("cells are an (m, 4) u64 array")
+        return Value._leaf(device, values, form, len(values))
+
+    @staticmethod
+    def from_ints(device, values):
+        return Value.from_limbs(device, ints_to_limbs([int(v) % R_MOD for v in values]))
+
+    @staticmethod
+    def full(device, count, value):
+        return Value(device, count, _Node("const", count, value=int(value) % R_MOD))
+
+    @staticmethod
+    def unknown(count):
+        return Value(None, count, None)
+
+    @property
+    def known(self):
+        return self._node is not None
+
+    def __len__(self):
+        return self.count
+
+    def __repr__(self):
+        return "Value(%s, %d)" % (self._node.kind if self.known else "unknown", self.count)
+
+    # -- views ---------------------------------------------------------------------------------------------------------------
+    def __getitem__(self, key):
+        if isinstance(key, slice):
+            start, stop, step = key.indices(self.count)
+            if step < 1:
+                raise ValueError("values are sliced forwards")
+            count = len(range(start, stop, step))
+        else:
+            if not -self.count <= key < self.count:
+                raise IndexError(key)
+            start, step, count = key % self.count, 1, 1
+        if not self.known:
+            return Value.unknown(count)
+        return Value(self.device, count, self._node, self._first + start * self._step, self._step * step)
+
+    # -- elementwise ---------------------------------------------------------------------------------------------------------
+    def _lift(self, other):
+        if isinstance(other, Value):
+            return other
+        if isinstance(other, (int, np.integer)):
+            return Value.full(self.device, self.count, int(other))
+        return None
+
+    @staticmethod
+    def _op(kind, *args):
+        count = args[0].count
+        for other in args[1:]:
+            if other.count != count:
+                raise ValueError("values of %d and %d elements do not combine" % (count, other.count))
+        if not all(a.known for a in args):
+            return Value.unknown(count)
+        device = None
+        for a in args:
+            if a.device is not None:
+                if device is not None and a.device is not device:
+                    raise ValueError("values of two devices do not combine")
+                device = a.device
+        if device is not None and any(a.device is None and a._node.kind != "const" for a in args):
+            raise ValueError("a host value and a device value do not combine")
+        return Value(device, count, _Node(kind, count, args))
+
+    def _binary(self, kind, other, swap=False):
+        other = self._lift(other)
+        if other is None:
+            return NotImplemented
+        return Value._op(kind, other, self) if swap else Value._op(kind, self, other)
+
+    def __add__(self, other):
+        return self._binary("add", other)
+
+    __radd__ = __add__
+
+    def __sub__(self, other):
+        return self._binary("sub", other)
+
+    def __rsub__(self, other):
+        return self._binary("sub", other, swap=True)
+
+    def __mul__(self, other):
+        return self._binary("mul", other)
+
+    __rmul__ = __mul__
+
+    def __neg__(self):
+        return Value._op("neg", self)
+
+    def square(self):
+        return Value._op("sqr", self)
+
+    def __pow__(self, e):
+        if not isinstance(e, (int, np.integer)) or e < 0:
+            raise TypeError("** takes a small non-negative integer")
+        if e == 0:
+            return Value.full(self.device, self.count, 1) if self.known else Value.unknown(self.count)
+        acc = self
+        for bit in bin(int(e))[3:]:
+            acc = acc.square()
+            if bit == "1":
+                acc = acc * self
+        return acc
+
+    def is_zero(self):
+        return Value._op("iszero", self)
+
+    @staticmethod
+    def select(cond, a, b):
+        """a where cond != 0, else b"""
+        base = next((v for v in (cond, a, b) if isinstance(v, Value)), None)
+        if base is None:
+            raise TypeError("select takes at least one Value")
+        return Value._op("select", *(base._lift(v) for v in (cond, a, b)))
+
+    # -- inversion, scans, concat, take: results are leaves over a buffer that is filled on materialisation ------------------
+    def _deferred(self, kind, count, args, extra=None, device=None):
+        pending = _Pending(kind, args, extra)
+        return Value(self.device if device is None else device, count,
+                     _Node("leaf", count, buffer=_Buffer(None, FORM_MONTGOMERY, count, pending)))
+
+    def invert(self, strict=False):
+        """1 / x, and 0 where x = 0 (`Assigned::evaluate`, ff::BatchInvert); `strict`: a zero raises on materialisation"""
+        if not self.known:
+            return Value.unknown(self.count)
+        return self._deferred("inv", self.count, (self,), strict)
+
+    def __truediv__(self, other):
+        other = self._lift(other)
+        if other is None:
+            return NotImplemented
+        return Value._op("mul", self, other.invert()) if self.known and other.known else Value._op("mul", self, other)
+
+    def __rtruediv__(self, other):
+        other = self._lift(other)
+        return NotImplemented if other is None else other / self
+
+    def _scan(self, kind, init):
+        if not self.known:
+            return Value.unknown(self.count + 1)
+        return self._deferred(kind, self.count + 1, (self,), int(init) % R_MOD)
+
+    def cumprod(self, init=1):
+        """count + 1 elements: z[0] = init, z[i] = z[i - 1] * self[i - 1]"""
+        return self._scan("cumprod", init)
+
+    def cumsum(self, init=0):
+        return self._scan("cumsum", init)
+
+    @staticmethod
+    def concat(parts):
+        parts = list(parts)
+        count = sum(p.count for p in parts)
+        if not all(p.known for p in parts):
+            return Value.unknown(count)
+        device = next((p.device for p in parts if p.device is not None), None)
+        return parts[0]._deferred("concat", count, tuple(parts), device=device) if parts else Value.from_ints(None, [])
+
+    def take(self, indices):
+        """self[indices]: materialises, then gathers"""
+        if not self.known:
+            return Value.unknown(len(indices))
+        return self._deferred("take", len(indices), (self,), indices)
+
+    # -- materialisation -----------------------------------------------------------------------------------------------------
+    @staticmethod
+    def materialize(values, montgomery=False):
+        """the elements of several Values at once (their common subexpressions evaluated once) -> [(count, 4) arrays]"""
+        values = list(values)
+        form = FORM_MONTGOMERY if montgomery else FORM_CANONICAL
+        todo = [v for v in values if v._cached(form) is None]
+        if todo:
+            if not all(v.known for v in todo):
+                raise ValueError("an unknown Value has no elements")
+            be = _backend(_common_device(todo))
+            _resolve_pending(todo, be)
+            for v, data in zip(todo, _evaluate(todo, be, form)):
+                v._store(form, data)
+            be.publish()
+        return [v._cached(form) for v in values]
+
+    def _whole(self):
+        return self.known and self._first == 0 and self._step == 1 and self.count == self._node.count
+
+    def _cached(self, form):
+        if form in self._cache:
+            return self._cache[form]
+        if self._whole() and self._node.cache and form in self._node.cache:
+            return self._node.cache[form]
+        return None
+
+    def _store(self, form, data):
+        self._cache[form] = data
+        if self._whole():
+            if self._node.cache is None:
+                self._node.cache = {}
+            self._node.cache[form] = data
+
+    def tensor(self, montgomery=False):
+        """the (count, 4) device tensor (a numpy array without a device), canonical or Montgomery; computed once"""
+        return Value.materialize([self], montgomery)[0]
+
+    def to_ints(self):
+        data = self.tensor()
+        return limbs_to_ints(_backend(self.device).download(data)) if self.count else []
+
+
+def _common_device(values):
+    device = None
+    for v in values:
+        if v.device is not None:
+            if device is not None and device is not v.device:
+                raise ValueError("values of two devices do not materialise together")
+            device = v.device
+    return device
+
+
+# -- deferred buffers: inversions by depth, scans, concat, take ---------------------------------------------------------------
+def _direct(values):
+    """the unresolved buffers `values` read, without looking into what those wait for"""
+    out, seen, stack = {}, set(), [v._node for v in values]
+    while stack:
+        node = stack.pop()
+        if id(node) in seen:
+            continue
+        seen.add(id(node))
+        if node.kind == "leaf":
+            if node.buffer.data is None:
+                out[id(node.buffer)] = node.buffer
+        elif node.kind != "const" and not node.cache:
+            stack.extend(a._node for a in node.args)
+    return list(out.values())
+
+
+def _ready(values):
+    """the unresolved buffers below `values` that wait for nothing unresolved: the innermost depth"""
+    ready, seen, frontier = [], set(), _direct(values)
+    while frontier:
+        buf = frontier.pop()
+        if id(buf) in seen:
+            continue
+        seen.add(id(buf))
+        below = _direct(buf.pending.args)
+        if below:
+            frontier.extend(below)
+        else:
+            ready.append(buf)
+    return ready
+
+
+def _resolve_pending(values, be):
+    while True:
+        ready = _ready(values)
+        if not ready:
+            return
+        inversions = [buf for buf in ready if buf.pending.kind == "inv"]
+        for buf in ready:
+            if buf.pending.kind != "inv":
+                _resolve_other(buf, be)
+        if inversions:
+            _resolve_inversions(inversions, be)
+
+
+def _resolve_inversions(bufs, be):
+    """every denominator of this depth into consecutive segments of one buffer, one batch inversion over it"""
+    total = sum(buf.length for buf in bufs)
+    whole, at, outs = be.empty(total), 0, []
+    for buf in bufs:
+        outs.append((whole, at))
+        at += buf.length
+    _evaluate([buf.pending.args[0] for buf in bufs], be, FORM_MONTGOMERY, outs)
+    at = 0
+    for buf in bufs:
+        if buf.pending.extra and buf.length:                        # strict
+            zeros = be.zero_rows(whole[at:at + buf.length])
+            if len(zeros):
+                raise ZeroDivisionError("invert(strict=True): element %d of the %d is zero" % (int(zeros[0]), buf.length))
+        at += buf.length
+    if total:
+        be.invert(whole)
+        be.count(inversions=1)
+    at = 0
+    for buf in bufs:
+        buf.data, buf.ordered, buf.pending = whole[at:at + buf.length], True, None
+        at += buf.length
+
+
+def _resolve_other(buf, be):
+    kind, args, extra = buf.pending.kind, buf.pending.args, buf.pending.extra
+    if kind in ("cumprod", "cumsum"):
+        m = args[0].count
+        f = _evaluate([args[0]], be, FORM_MONTGOMERY)[0] if m else None
+        data = be.scan(f, m, extra, kind == "cumprod")
+    elif kind == "concat":
+        data, at, outs = be.empty(buf.length), 0, []
+        for part in args:
+            outs.append((data, at))
+            at += part.count
+        _evaluate(list(args), be, FORM_MONTGOMERY, outs)
+    else:                                                           # take
+        node = args[0]._node
+        if node.kind == "leaf" and args[0]._whole():                # elements as they stand, in whatever form: no launch
+            data, buf.form = be.gather(be.data(node.buffer), extra), node.buffer.form
+        else:
+            data = be.gather(_evaluate([args[0]], be, FORM_MONTGOMERY)[0], extra)
+    buf.data, buf.ordered, buf.pending = data, True, None
+
+
+# -- the compiler --------------------------------------------------------------------------------------------------------------
+class _Overflow(Exception):
+    pass
+
+
+class _Dag:
+    """hash-consed expressions: ids ascend from operands to results.  An entry is ("leaf", buffer, first, stride, form),
+    ("const", value) or (op, operand ids)"""
+
+    def __init__(self):
+        self.entries, self.index, self.memo = [], {}, {}
+
+    def _intern(self, key, entry):
+        at = self.index.get(key)
+        if at is None:
+            at = self.index[key] = len(self.entries)
+            self.entries.append(entry)
+        return at
+
+    def leaf(self, buffer, first, stride, form):
+        return self._intern(("leaf", id(buffer), first, stride, form), ("leaf", buffer, first, stride, form))
+
+    def interior(self, at):
+        return self.entries[at][0] not in ("leaf", "const")
+
+    def add(self, value):
+        """the id of `value`, its view pushed down to the leaves"""
+        key_of = lambda item: (id(item[0]),) + item[1:]             # noqa: E731
+        root = (value._node, value._first, value._step, value.count)
+        stack = [root]
+        while stack:
+            item = stack[-1]
+            key = key_of(item)
+            if key in self.memo:
+                stack.pop()
+                continue
+            node, first, step, count = item
+            if node.kind == "leaf" or node.cache:
+                if node.kind == "leaf":
+                    buffer = node.buffer
+                else:                                               # materialised before: read, not computed again
+                    form = FORM_MONTGOMERY if FORM_MONTGOMERY in node.cache else FORM_CANONICAL
+                    buffer = node.cache.get("buffer%d" % form)
+                    if buffer is None:
+                        buffer = node.cache["buffer%d" % form] = _Buffer(node.cache[form], form, node.count, ordered=True)
+                self.memo[key] = self.leaf(buffer, first, 1 if count <= 1 else step, buffer.form)
+            elif node.kind == "const":
+                self.memo[key] = self._intern(("const", node.value), ("const", node.value))
+            else:
+                kids = [(a._node, a._first + first * a._step, step * a._step, count) for a in node.args]
+                missing = [k for k in kids if key_of(k) not in self.memo]
+                if missing:
+                    stack.extend(missing)
+                    continue
+                ids = tuple(self.memo[key_of(k)] for k in kids)
+                if node.kind in ("add", "mul"):
+                    ids = tuple(sorted(ids))
+                self.memo[key] = self._intern((node.kind, ids), (node.kind, ids))
+            stack.pop()
+        return self.memo[key_of(root)]
+
+    def cone(self, roots):
+        """the interior ids reachable from `roots`, ascending"""
+        seen, stack = set(), [r for r in roots if self.interior(r)]
+        while stack:
+            at = stack.pop()
+            if at in seen:
+                continue
+            seen.add(at)
+            stack.extend(c for c in self.entries[at][1] if self.interior(c))
+        return sorted(seen)
+
+
+class _Program:
+    """one launch: leaves [(buffer, first, stride, form)], constants [int], ops [(code, dst, a, b, c)], the roots' slots"""
+
+    def __init__(self):
+        self.leaves, self.constants, self.ops, self.slots_used, self.root_slots = [], [], [], 0, []
+
+
+def _schedule(dag, roots, caps):
+    """the program that computes `roots` (ids of `dag`), or _Overflow naming the cap it does not fit"""
+    if len(roots) > caps["outputs"]:
+        raise _Overflow("outputs")
+    prog = _Program()
+    cone = dag.cone(roots)
+    if len(cone) > caps["ops"]:
+        raise _Overflow("ops")
+    # Sethi-Ullman labels, operands before results
+    label = {}
+    for at in cone:
+        kids = sorted((label[c] for c in dag.entries[at][1] if dag.interior(c)), reverse=True)
+        label[at] = max([l + i for i, l in enumerate(kids)] + [1])
+    order, done = [], set()
+    stack = [(r, False) for r in reversed(roots) if dag.interior(r)]
+    while stack:
+        at, expanded = stack.pop()
+        if at in done:
+            continue
+        if expanded:
+            done.add(at)
+            order.append(at)
+            continue
+        stack.append((at, True))
+        kids = [c for c in dict.fromkeys(dag.entries[at][1]) if dag.interior(c) and c not in done]
+        for c in sorted(kids, key=lambda c: label[c]):              # popped last first: the largest label is evaluated first
+            stack.append((c, False))
+    uses = {}
+    for at in order:
+        for c in dag.entries[at][1]:
+            if dag.interior(c):
+                uses[c] = uses.get(c, 0) + 1
+    for r in roots:
+        uses[r] = uses.get(r, 0) + 1                                # an output reads the slot at the end: never freed
+    leaf_index, const_index, slot_of, free = {}, {}, {}, list(range(caps["slots"]))
+
+    def terminal(at):
+        entry = dag.entries[at]
+        if entry[0] == "leaf":
+            if at not in leaf_index:
+                if len(prog.leaves) == caps["leaves"]:
+                    raise _Overflow("leaves")
+                leaf_index[at] = len(prog.leaves)
+                prog.leaves.append(entry[1:])
+            return KIND_LEAF << 24 | leaf_index[at]
+        if at not in const_index:
+            if len(prog.constants) == caps["constants"]:
+                raise _Overflow("constants")
+            const_index[at] = len(prog.constants)
+            prog.constants.append(entry[1])
+        return KIND_CONST << 24 | const_index[at]
+
+    def emit(kind, kids, transient):
+        words = [(KIND_LAST << 24 if slot_of[c] is None else KIND_SLOT << 24 | slot_of[c]) if dag.interior(c) else terminal(c)
+                 for c in kids]
+        for c in kids:
+            if dag.interior(c):
+                uses[c] -= 1
+                if uses[c] == 0 and slot_of[c] is not None:
+                    free.append(slot_of[c])
+        if len(prog.ops) == caps["ops"]:
+            raise _Overflow("ops")
+        if transient:
+            prog.ops.append((OP_CODES[kind], NO_SLOT) + tuple(words + [0] * (3 - len(words))))
+            return None
+        if not free:
+            raise _Overflow("slots")
+        dst = min(free)
+        free.remove(dst)
+        prog.slots_used = max(prog.slots_used, caps["slots"] - len(free))
+        if len(prog.ops) == caps["ops"]:
+            raise _Overflow("ops")
+        prog.ops.append((OP_CODES[kind], dst) + tuple(words + [0] * (3 - len(words))))
+        return dst
+
+    for p, at in enumerate(order):
+        kind, kids = dag.entries[at]
+        # read once, by the very next op, and no output: it lives in the kernel's `last` and takes no slot
+        transient = uses[at] == 1 and at not in roots and p + 1 < len(order) and at in dag.entries[order[p + 1]][1]
+        slot_of[at] = emit(kind, kids, transient)
+    zero = None
+    for r in roots:
+        if dag.interior(r):
+            prog.root_slots.append(slot_of[r])
+        else:                                                       # a bare leaf or constant: + 0 brings it into a slot
+            if zero is None:
+                zero = dag._intern(("const", 0), ("const", 0))
+            words = [terminal(r), terminal(zero)]
+            if not free:
+                raise _Overflow("slots")
+            dst = min(free)
+            free.remove(dst)
+            prog.slots_used = max(prog.slots_used, caps["slots"] - len(free))
+            if len(prog.ops) == caps["ops"]:
+                raise _Overflow("ops")
+            prog.ops.append((OP_CODES["add"], dst, words[0], words[1], 0))
+            prog.root_slots.append(dst)
+    return prog
+
+
+def _launch(prog, outs, form, m, be):
+    """outs: [(array, first element)] per root"""
+    leaves = np.zeros(len(prog.leaves), dtype=VALUES_LEAF)
+    keep = []
+    for i, (buffer, first, stride, lform) in enumerate(prog.leaves):
+        data = be.data(buffer)
+        keep.append(data)
+        leaves[i] = (be.ptr(data), first, stride, buffer.length, lform, 0)
+    constants = ints_to_limbs(prog.constants) if prog.constants else np.zeros((0, 4), dtype=np.uint64)
+    ops = np.array(prog.ops, dtype=np.uint32).reshape(len(prog.ops), 5).view(VALUES_OP).reshape(-1) if prog.ops else np.zeros(0, dtype=VALUES_OP)
+    outputs = np.zeros(len(outs), dtype=VALUES_OUTPUT)
+    for i, ((data, first), slot) in enumerate(zip(outs, prog.root_slots)):
+        outputs[i] = (be.ptr(data), first, slot, form)
+    be.eval(leaves.ctypes.data, len(leaves), constants.ctypes.data, len(constants), ops.ctypes.data, len(ops),
+            outputs.ctypes.data, len(outputs), m)
+    be.count(launches=1)
+    LAST_PROGRAMS.append(prog)
+    if len(LAST_PROGRAMS) > 256:
+        del LAST_PROGRAMS[:128]
+
+
+LAST_PROGRAMS = []          # the programs launched most recently (tests and tools read the op and slot counts); kept short
+
+
+def _split_candidate(dag, roots, caps):
+    """the largest proper subexpression that fits a launch of its own -> (id, its program)"""
+    total = dag.cone(roots)
+    sizes = sorted(((len(dag.cone([at])), at) for at in total), reverse=True)
+    for size, at in sizes:
+        if size > caps["ops"] or (size == len(total) and len(roots) == 1):
+            continue
+        try:
+            return at, _schedule(dag, [at], caps)
+        except _Overflow:
+            continue
+    raise RuntimeError("no subexpression of this Value fits a launch")
+
+
+def _evaluate(values, be, form, outs=None):
+    """pure elementwise Values (every buffer resolved) -> their elements; `outs`: [(array, first element)] to write into
+    instead of fresh arrays"""
+    caps = limits()
+    results = [None] * len(values)
+    by_count = {}
+    for i, v in enumerate(values):
+        by_count.setdefault(v.count, []).append(i)
+    for m, group in by_count.items():
+        for lo in range(0, len(group), caps["outputs"]):
+            chunk = group[lo:lo + caps["outputs"]]
+            dests = []
+            for i in chunk:
+                v = values[i]
+                if outs is not None:
+                    dests.append(outs[i])
+                    continue
+                node = v._node
+                if node.kind == "leaf" and v._whole() and node.buffer.form == form:        # the elements as they stand
+                    results[i] = be.data(node.buffer)
+                    dests.append(None)
+                else:
+                    results[i] = be.empty(m)
+                    dests.append((results[i], 0))
+            chunk = [i for i, d in zip(chunk, dests) if d is not None]
+            dests = [d for d in dests if d is not None]
+            if m == 0 or not chunk:
+                continue
+            dag = _Dag()
+            roots = [dag.add(values[i]) for i in chunk]
+            _run(dag, roots, dests, form, m, be, caps)
+    return results
+
+
+def _run(dag, roots, dests, form, m, be, caps):
+    """launch `roots` into `dests`, splitting while the whole does not fit"""
+    roots, dests = list(roots), list(dests)
+    while roots:
+        # two roots that are one expression share a slot; the outputs stay two
+        try:
+            prog = _schedule(dag, roots, caps)
+        except _Overflow:
+            at, sub = _split_candidate(dag, roots, caps)
+            if at in roots:                                         # a root on its own: straight to where it belongs
+                k = roots.index(at)
+                data, first = dests[k]
+                _launch(sub, [dests[k]], form, m, be)
+                buffer, lfirst, lform = _Buffer(data, form, first + m, ordered=True), first, form
+                del roots[k], dests[k]
+            else:
+                data = be.empty(m)
+                _launch(sub, [(data, 0)], FORM_MONTGOMERY, m, be)
+                buffer, lfirst, lform = _Buffer(data, FORM_MONTGOMERY, m, ordered=True), 0, FORM_MONTGOMERY
+            dag.entries[at] = ("leaf", buffer, lfirst, 1, lform)
+            continue
+        _launch(prog, dests, form, m, be)
+        return
+
+
+def plan(values):
+    """the programs a materialisation of `values` would launch if their buffers were resolved, without running anything:
+    [(ops, slots used, leaves)] -- for tests and tools; a program over the caps is split as _run splits it"""
+    caps = limits()
+    dag = _Dag()
+    roots = [dag.add(v) for v in values]
+    out = []
+    while True:
+        try:
+            prog = _schedule(dag, roots, caps)
+        except _Overflow:
+            at, sub = _split_candidate(dag, roots, caps)
+            out.append(sub)
+            dag.entries[at] = ("leaf", _Buffer(None, FORM_MONTGOMERY, values[0].count), 0, 1, FORM_MONTGOMERY)
+            if at in roots:
+                roots.remove(at)
+                if not roots:
+                    return out
+            continue
+        out.append(prog)
+        return out

@@ -969,6 +969,75 @@ int h2_coverage_check(const h2_coverage_plane *planes, size_t num_planes, const 
                       const h2_coverage_use *uses, size_t num_uses, const uint32_t *earlier, size_t num_earlier, size_t n,
                       const void *bits, size_t words, uint64_t *count, h2_check_record *records, size_t cap);
 
+/* ---- computing a witness: one fused launch per straight-line program (values.hip; DESIGN.md 3b "Computing a witness") ----
+ * What `Value<F>` and `Assigned<F>` arithmetic (circuit.rs, plonk/assigned.rs) give a synthesize body, in bulk: one program of
+ * field operations evaluated over m rows, one lane per row, with no intermediate of length m in device memory.
+ *   leaves     row i of leaf l is element first + i * stride of a buffer of `len` elements at `ptr`, read in its form
+ *              (H2_ASSIGNED_FORM_*).  A CANONICAL element may be ANY 256-bit integer and is reduced mod r on load (the
+ *              conversion is the wide product, which takes a < 2^256); a MONTGOMERY element must be reduced, as everywhere in
+ *              the library; a COMPACT element is one u64.  first + (m - 1) * stride < len is checked, stride >= 1.
+ *   constants  num_constants x 4 u64, canonical (any 256-bit integer), converted once on the host
+ *   ops        op i computes dst = op(a, b, c) into slot `dst`; an operand is kind << 24 | index with kind LEAF, CONST,
+ *              SLOT or LAST (the result of op i - 1, which the kernel keeps in registers; the index is not read).  dst may
+ *              be H2_VALUES_NO_SLOT: the result is only there for the next op's LAST.  ADD, SUB, MUL take a, b; SQR, NEG,
+ *              ISZERO (1 or 0) take a; SELECT gives b where a != 0, else c.  A slot must have been written by an earlier
+ *              op before it is read.
+ *   outputs    row i of slot `slot`, as it stands at the END of the program, goes to element first + i of `ptr` (32-byte
+ *              elements, contiguous) in `form`, CANONICAL or MONTGOMERY, fully reduced.
+ * Overlap rule: the m elements of an output may not overlap the elements a leaf of the same call reads, nor another output,
+ * with ONE exception: a 32-byte leaf of stride 1 whose element i is the very bytes of the output's element i (in place).
+ * Every load of a row precedes every store of that row and rows do not talk to each other, so that mapping alone is safe.
+ * h2_values_limits: the caps {leaves, ops, constants, outputs, slots} a call may use, and `blocks`, the most workgroups (of
+ * `threads` lanes) a launch starts -- beyond blocks * threads rows every lane takes several rows.
+ * h2_dev_values_eval is asynchronous on `stream`, does not synchronise the host, and passes the program in the kernel
+ * arguments.  h2_values_eval is the same on HOST memory by a host interpreter of the same lowered program on the same
+ * reduced representatives: bit-exact with the kernel; it touches no device.  Both return H2_ERR_INVALID, before anything is
+ * read or written, h2_last_error naming what is wrong, for a count above its cap, a null or misaligned pointer (16 bytes
+ * for 32-byte elements on the device, 8 on the host; 8 for compact), an unknown form or op, a slot index at or above the
+ * cap, an operand that names a leaf or constant that does not exist or a slot never written, LAST in the first op, a leaf whose range passes
+ * `len`, or an overlap the rule above refuses.  m == 0 succeeds and touches nothing. */
+enum { H2_VALUES_ADD = 0, H2_VALUES_SUB = 1, H2_VALUES_MUL = 2, H2_VALUES_SQR = 3, H2_VALUES_NEG = 4, H2_VALUES_SELECT = 5,
+       H2_VALUES_ISZERO = 6 };
+enum { H2_VALUES_LEAF = 0, H2_VALUES_CONST = 1, H2_VALUES_SLOT = 2, H2_VALUES_LAST = 3 };
+#define H2_VALUES_NO_SLOT 0xffffffffu
+typedef struct {
+    uint64_t ptr;
+    uint64_t first;
+    uint64_t stride;
+    uint64_t len;
+    uint32_t form;
+    uint32_t reserved;
+} h2_values_leaf;
+typedef struct {
+    uint32_t op;
+    uint32_t dst;
+    uint32_t a;
+    uint32_t b;
+    uint32_t c;
+} h2_values_op;
+typedef struct {
+    uint64_t ptr;
+    uint64_t first;
+    uint32_t slot;
+    uint32_t form;
+} h2_values_output;
+typedef struct {
+    uint32_t leaves;
+    uint32_t ops;
+    uint32_t constants;
+    uint32_t outputs;
+    uint32_t slots;
+    uint32_t blocks;
+    uint32_t threads;
+    uint32_t reserved;
+} h2_values_caps;
+int h2_values_limits(h2_values_caps *out);
+int h2_dev_values_eval(const h2_values_leaf *leaves, size_t num_leaves, const uint64_t *constants, size_t num_constants,
+                       const h2_values_op *ops, size_t num_ops, const h2_values_output *outputs, size_t num_outputs, size_t m,
+                       void *stream);
+int h2_values_eval(const h2_values_leaf *leaves, size_t num_leaves, const uint64_t *constants, size_t num_constants,
+                   const h2_values_op *ops, size_t num_ops, const h2_values_output *outputs, size_t num_outputs, size_t m);
+
 /* ---- screening the points of an SRS ------------------------------------------------------------------------------------
  * The reference takes the points of its parameters as they come: Params::read unwraps `from_bytes` per point
  * (poly/commitment.rs:262-275) and a table built in memory is never looked at.  h2_dev_g1_check_points tests each of the n
