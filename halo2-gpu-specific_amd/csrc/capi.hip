@@ -937,8 +937,9 @@ int h2_dev_points_decompress(const void* d_bytes, size_t n, void* d_points, void
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         std::lock_guard<std::mutex> g(ctx->mu);
-        uint32_t* d_bad = (uint32_t*)ctx->buf_d.get(256);
-        return points_decompress_launch(d_bytes, n, (uint64_t*)d_points, d_bad, pick_stream(ctx, stream));
+        hipStream_t s = pick_stream(ctx, stream);
+        uint32_t* d_bad = (uint32_t*)ctx->buf_d.lend(256, s);
+        return points_decompress_launch(d_bytes, n, (uint64_t*)d_points, d_bad, s);  // (has waited for `s`: nothing lent is left)
     });
 }
 
@@ -1026,8 +1027,9 @@ int h2_dev_eval_polynomial(const void* d_poly, size_t n, const uint64_t point[4]
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         std::lock_guard<std::mutex> g(ctx->mu);
-        Fr* tmp = (Fr*)ctx->buf_d.get(eval_polynomial_tmp_elems(n) * sizeof(Fr));
-        return eval_polynomial_launch((const Fr*)d_poly, n, point, tmp, out, pick_stream(ctx, stream));
+        hipStream_t s = pick_stream(ctx, stream);
+        Fr* tmp = (Fr*)ctx->buf_d.lend(eval_polynomial_tmp_elems(n) * sizeof(Fr), s);
+        return eval_polynomial_launch((const Fr*)d_poly, n, point, tmp, out, s);  // (has waited for `s`)
     });
 }
 
@@ -1037,8 +1039,9 @@ int h2_dev_eval_polynomial_batch(const void* const* d_polys, size_t count, size_
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         std::lock_guard<std::mutex> g(ctx->mu);
-        Fr* tmp = (Fr*)ctx->buf_d.get(eval_polynomial_batch_tmp_bytes(count, n));
-        return eval_polynomial_batch_launch((const Fr* const*)d_polys, count, n, points, tmp, out, pick_stream(ctx, stream));
+        hipStream_t s = pick_stream(ctx, stream);
+        Fr* tmp = (Fr*)ctx->buf_d.lend(eval_polynomial_batch_tmp_bytes(count, n), s);
+        return eval_polynomial_batch_launch((const Fr* const*)d_polys, count, n, points, tmp, out, s);  // (has waited for `s`)
     });
 }
 
@@ -1099,8 +1102,12 @@ int h2_dev_kate_division(const void* d_a, size_t n, const uint64_t b[4], void* d
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         std::lock_guard<std::mutex> g(ctx->mu);
-        Fr* tmp = (Fr*)ctx->buf_d.get(scan_tmp_elems(n) * sizeof(Fr));
-        return kate_division_launch((const Fr*)d_a, n, b, (Fr*)d_q, tmp, pick_stream(ctx, stream));
+        // the one borrower of buf_d that returns with its kernels still queued: the next one -- any stream -- waits for them
+        hipStream_t s = pick_stream(ctx, stream);
+        Fr* tmp = (Fr*)ctx->buf_d.lend(scan_tmp_elems(n) * sizeof(Fr), s);
+        H2_TRY(kate_division_launch((const Fr*)d_a, n, b, (Fr*)d_q, tmp, s));
+        ctx->buf_d.lent(s);
+        return (int)H2_OK;
     });
 }
 
@@ -1124,8 +1131,9 @@ int h2_dev_prefix_product(const void* d_f, size_t n, const uint64_t init[4], voi
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         std::lock_guard<std::mutex> g(ctx->mu);
-        Fr* tmp = (Fr*)ctx->buf_d.get(scan_tmp_elems(n) * sizeof(Fr));
-        return prefix_product_launch((const Fr*)d_f, n, init, (Fr*)d_z, tmp, pick_stream(ctx, stream));
+        hipStream_t s = pick_stream(ctx, stream);
+        Fr* tmp = (Fr*)ctx->buf_d.lend(scan_tmp_elems(n) * sizeof(Fr), s);
+        return prefix_product_launch((const Fr*)d_f, n, init, (Fr*)d_z, tmp, s);  // (has waited for `s`)
     });
 }
 
@@ -1407,8 +1415,9 @@ int h2_dev_prefix_sum(const void* d_f, size_t n, const uint64_t init[4], void* d
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         std::lock_guard<std::mutex> g(ctx->mu);
-        Fr* tmp = (Fr*)ctx->buf_d.get(scan_tmp_elems(n) * sizeof(Fr));
-        return prefix_sum_launch((const Fr*)d_f, n, init, (Fr*)d_z, tmp, pick_stream(ctx, stream));
+        hipStream_t s = pick_stream(ctx, stream);
+        Fr* tmp = (Fr*)ctx->buf_d.lend(scan_tmp_elems(n) * sizeof(Fr), s);
+        return prefix_sum_launch((const Fr*)d_f, n, init, (Fr*)d_z, tmp, s);  // (has waited for `s`)
     });
 }
 

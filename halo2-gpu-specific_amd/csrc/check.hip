@@ -243,12 +243,13 @@ int check_gates_launch(DeviceCtx* ctx, const h2_evalh_desc* d, const uint32_t* d
     const size_t inter_bytes = (size_t)(d->n_calculations ? d->n_calculations : 1) * nthreads * sizeof(Fr);
     // the interpreter's work space is the library's (as h2_dev_evaluate_h's): per device, under its lock
     std::lock_guard<std::mutex> g(ctx->mu);
-    char* block = (char*)ctx->evalh_scratch.get(align256(need) + inter_bytes);
-    const EvalhProgram p = evalh_stage_program(d, block, need, stream);   // (a gate program: its lookup and shuffle parts are empty)
+    char* block = (char*)ctx->evalh_scratch.lend(align256(need) + inter_bytes, stream);
+    const EvalhProgram p = evalh_stage_program(ctx, d, block, need, stream);   // (a gate program: its lookup and shuffle parts are empty)
     hipLaunchKernelGGL(k_check_gate_rows, dim3(blocks), dim3(threads), 0, stream, p, (Fr*)(block + align256(need)), d_rows,
                        (const unsigned long long*)d_row_count, (uint32_t)H2_CHECK_GATE | circuit << 8,
                        (unsigned long long*)d_count, d_records, (unsigned long long)cap);
     H2_HIP(hipGetLastError());
+    ctx->evalh_scratch.lent(stream);
     return H2_OK;
 }
 

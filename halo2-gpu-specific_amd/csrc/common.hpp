@@ -39,11 +39,23 @@ struct HipError {
     } while (0)
 
 // Grow-only device buffer (never shrinks; reused across calls).
+//
+// A block that an h2_dev_* entry point LENDS to work on the caller's stream (slot 0's buf_d: the scans' scratch;
+// evalh_scratch: the interpreter's staged program and intermediates) may still be in use when the entry point has returned,
+// and the next borrower may name another stream.  `last_use` orders them, all under the owning context's lock:
+//   lend(bytes, s)  get(bytes), and `s` waits for the event before anything queued behind it touches the block
+//   lent(s)         records the event behind the last kernel that touches the block
+//   settle()        the HOST waits for the event (a host-slice call that takes the slot: DeviceLease)
+// get() waits for the event before it frees a block it has to grow.
 struct DevBuf {
     void* ptr = nullptr;
     size_t cap = 0;
+    hipEvent_t last_use = nullptr;  // created by the first lent()
     void* get(size_t bytes);
     void release();
+    void* lend(size_t bytes, hipStream_t s);
+    void lent(hipStream_t s);
+    void settle();
 };
 
 // Grow-only pinned host buffer (async device-to-host staging).
@@ -93,6 +105,8 @@ struct DeviceCtx {
     DevBuf buf_a, buf_b, buf_c, buf_d; // staging / ping-pong scratch
     DevBuf msm_scratch;
     DevBuf evalh_scratch;
+    PinnedBuf evalh_stage;             // the host side of the interpreter's staged program (evalh_interp.hpp) ...
+    hipEvent_t evalh_staged = nullptr; // ... and the copy that read it last
     DevBuf coeff_arena;                // h2_evaluate_h_coeff / h2_quotient_poly_coeff: the columns' coefficient and coset vectors of a call
     PinnedBuf pinned;
     DeviceShared* shared;
@@ -121,6 +135,10 @@ struct DeviceLease {
         }
         ctx->mu.lock();  // two pool slots may map onto one physical device (idx % devices.len())
         (void)hipSetDevice(ctx->device);
+        // what an h2_dev_* call on a caller's stream was lent of this slot's memory has been used (DevBuf::last_use): a
+        // host-slice call runs on the slot's own streams and blocks its caller anyway
+        if (ctx->buf_d.last_use) (void)hipEventSynchronize(ctx->buf_d.last_use);
+        if (ctx->evalh_scratch.last_use) (void)hipEventSynchronize(ctx->evalh_scratch.last_use);
     }
     ~DeviceLease() {
         ctx->mu.unlock();

@@ -30,6 +30,7 @@ const char* get_last_error() { return g_last_error.c_str(); }
 
 void* DevBuf::get(size_t bytes) {
     if (bytes <= cap) return ptr;
+    settle();  // (hipFree waits for the whole device as well; this does not rely on it)
     if (ptr) H2_HIP(hipFree(ptr));
     ptr = nullptr;
     cap = 0;
@@ -52,9 +53,22 @@ void* PinnedBuf::get(size_t bytes) {
     return ptr;
 }
 void DevBuf::release() {
+    if (last_use) (void)hipEventSynchronize(last_use);
     if (ptr) (void)hipFree(ptr);
     ptr = nullptr;
     cap = 0;
+}
+void* DevBuf::lend(size_t bytes, hipStream_t s) {
+    void* p = get(bytes);
+    if (last_use) H2_HIP(hipStreamWaitEvent(s, last_use, 0));
+    return p;
+}
+void DevBuf::lent(hipStream_t s) {
+    if (!last_use) H2_HIP(hipEventCreateWithFlags(&last_use, hipEventDisableTiming));
+    H2_HIP(hipEventRecord(last_use, s));
+}
+void DevBuf::settle() {
+    if (last_use) H2_HIP(hipEventSynchronize(last_use));
 }
 
 namespace {

@@ -198,13 +198,13 @@ int evalh_interpret(DeviceCtx* ctx, const h2_evalh_desc* d, Fr* d_values, size_t
     size_t sh_bytes = d->n_shuffles ? 2 * (size_t)d->n_shuffles * size * sizeof(Fr) : 256;
     auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
     size_t total = align(need) + align(inter_bytes) + align(lk_bytes) + align(sh_bytes);
-    char* block = (char*)ctx->evalh_scratch.get(total);
+    char* block = (char*)ctx->evalh_scratch.lend(total, stream);  // (the previous borrower's kernels may still be queued elsewhere)
     Fr* d_inter = (Fr*)(block + align(need));
     Fr* d_lk = (Fr*)((char*)d_inter + align(inter_bytes));
     Fr* d_sh = (Fr*)((char*)d_lk + align(lk_bytes));
 
     EvalhArgTables tab{};
-    EvalhProgram p = evalh_stage_program(d, block, need, stream, &tab);
+    EvalhProgram p = evalh_stage_program(ctx, d, block, need, stream, &tab);
     p.row_begin = row_begin;
     p.row_end = row_end;
     const uint32_t rot_scale = p.rot_scale;
@@ -281,6 +281,7 @@ int evalh_interpret(DeviceCtx* ctx, const h2_evalh_desc* d, Fr* d_values, size_t
         hipLaunchKernelGGL(k_evalh_shuffle, dim3(eblocks), dim3(256), 0, stream, a);
     }
     H2_HIP(hipGetLastError());
+    ctx->evalh_scratch.lent(stream);
     return H2_OK;
 }
 

@@ -76,16 +76,17 @@ struct Interp {
 };
 
 // ---------------------------------------------------------------- host driver
-struct Arena {  // bump allocator over one host staging block mirrored to one device block
-    std::vector<char> host;
+struct Arena {  // bump allocator over one host staging block (`cap` bytes) mirrored to one device block
+    char* host = nullptr;
+    size_t cap = 0;
     char* dev = nullptr;
     size_t off = 0;
     template <class T>
     const T* put(const T* src, size_t count) {
         off = (off + 15) & ~(size_t)15;
         size_t bytes = count * sizeof(T);
-        if (host.size() < off + bytes + 16) host.resize(off + bytes + 16);
-        if (bytes) memcpy(host.data() + off, src, bytes);
+        if (off + bytes > cap) throw std::runtime_error("evaluate_h program: internal staging overflow");
+        if (bytes) memcpy(host + off, src, bytes);
         const T* d = reinterpret_cast<const T*>(dev + off);
         off += bytes;
         return d;
@@ -102,10 +103,15 @@ struct EvalhArgTables {
 
 // Mirrors the program arrays and column pointer tables of a validated descriptor (evalh_desc.hpp) into `block` (device, `need`
 // bytes: the caller's own formula) and returns the program over them, every member but the row range filled.  With `args`
-// the argument kernels' tables follow.  The copy has been made when this returns; `stream`'s owner holds the block's lock.
-inline EvalhProgram evalh_stage_program(const h2_evalh_desc* d, char* block, size_t need, hipStream_t stream,
+// the argument kernels' tables follow.  The caller holds ctx's lock (the block and the staging memory are the slot's).
+// The copy is QUEUED when this returns, not made: the host side is the slot's page-locked staging block, so `stream` is not
+// waited for -- only the copy that read the staging block last (the previous call's, usually long done).
+inline EvalhProgram evalh_stage_program(DeviceCtx* ctx, const h2_evalh_desc* d, char* block, size_t need, hipStream_t stream,
                                         EvalhArgTables* args = nullptr) {
+    if (ctx->evalh_staged) H2_HIP(hipEventSynchronize(ctx->evalh_staged));
     Arena ar;
+    ar.host = (char*)ctx->evalh_stage.get(need);
+    ar.cap = need;
     ar.dev = block;
     auto put_table = [&](uint32_t table) {
         return (const Fr* const*)ar.put(evalh_table(d, table), evalh_table_count(d, table));
@@ -133,9 +139,9 @@ inline EvalhProgram evalh_stage_program(const h2_evalh_desc* d, char* block, siz
         args->perm_cols = (const Fr* const*)ar.put(cols.data(), cols.size());
         args->lookup_z = put_table(evgen::T_LOOKUP_Z);
     }
-    if (ar.off > need) throw std::runtime_error("evaluate_h program: internal staging overflow");
-    H2_HIP(hipMemcpyAsync(block, ar.host.data(), ar.off, hipMemcpyHostToDevice, stream));
-    H2_HIP(hipStreamSynchronize(stream));  // the staging vector dies with this frame
+    H2_HIP(hipMemcpyAsync(block, ar.host, ar.off, hipMemcpyHostToDevice, stream));
+    if (!ctx->evalh_staged) H2_HIP(hipEventCreateWithFlags(&ctx->evalh_staged, hipEventDisableTiming));
+    H2_HIP(hipEventRecord(ctx->evalh_staged, stream));
     p.n_calcs = d->n_calculations;
     p.n_value_parts = d->n_value_parts;
     p.n_lookups = d->n_lookups;

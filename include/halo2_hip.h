@@ -24,10 +24,24 @@
  *                 H2_HOST_SLOTS (default 2, 1..4) such calls at a time, each on its own stream and staging, so that
  *                 one caller's transfers overlap another's kernels; 1 = the reference's one operation per device.
  *   h2_dev_*      operate on HIP device pointers on the caller's stream (void* = hipStream_t,
- *                 NULL = the library's stream for the current device) and do not synchronise.
+ *                 NULL = the library's stream for the current device): they read their inputs and write their outputs
+ *                 at their position in that stream, whatever thread calls and whatever other streams are busy.
  *                 NULL does NOT mean HIP's legacy default stream: the library's stream is non-blocking, so work
  *                 the caller queued on stream 0 is not ordered against it -- pass a stream of your own (every
  *                 call then runs in its order), or bracket the calls with h2_synchronize / hipDeviceSynchronize.
+ *                 They return without waiting for the stream, EXCEPT the ones below, which return only when the
+ *                 stream has drained up to and including their own work -- they hand a result to host memory, or
+ *                 stage host tables that live in the call's frame:
+ *                   h2_dev_eval_polynomial, h2_dev_eval_polynomial_batch, h2_dev_max_scalar_bits (host results);
+ *                   h2_dev_msm, h2_dev_msm_batch, h2_dev_msm_batch_ex (host results), h2_dev_bases_precompute;
+ *                   h2_dev_prefix_product, h2_dev_prefix_sum (the initial value is staged from the frame);
+ *                   h2_dev_points_decompress, h2_dev_logup_multiplicity, h2_dev_logup_multiplicity_bits (their status
+ *                   is a device result); h2_dev_cells_place, h2_dev_selectors_mark, h2_dev_coverage_mark,
+ *                   h2_dev_coverage_check (staged tables); h2_dev_permutation_mapping_phases (timed); h2_dev_download.
+ *                 The first call for a new transform size, generator or gate program also waits (it builds and
+ *                 publishes tables or compiles), later ones do not.  tests/test_gpu_stream_contract.py pins both lists.
+ *                 Scratch the library lends to such a call ("Library memory on caller streams") is ordered
+ *                 between streams by the library: two threads may drive two streams of one device at once.
  */
 #ifndef HALO2_HIP_H
 #define HALO2_HIP_H
