@@ -45,6 +45,12 @@ int bad(const char* msg) {
     return H2_ERR_INVALID;
 }
 
+// do the element ranges [a, a + na) and [b, b + nb) share a byte?  (ranges that only touch do not; an empty one never does)
+static bool fr_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return na && nb && a0 < b0 + nb * sizeof(Fr) && b0 < a0 + na * sizeof(Fr);
+}
+
 int dev_ntt_impl(DeviceCtx* ctx, const Fr* src, Fr* dst, Fr* tmp, uint32_t in_len, const uint64_t omega[4],
                  uint32_t log_n, const Fr* pre3, const Fr* post3, hipStream_t s) {
     if (log_n > 28) return bad("log_n exceeds the 2-adicity of Fr (S = 28)");
@@ -1099,6 +1105,8 @@ int h2_batch_invert(uint64_t* a, size_t n) {
 
 int h2_dev_kate_division(const void* d_a, size_t n, const uint64_t b[4], void* d_q, void* stream) {
     if (!b || (n >= 2 && (!d_a || !d_q))) return bad("h2_dev_kate_division: null argument");
+    // workgroup B writes q[n-2-j] while workgroup B+1 still reads a[n-1-j']: they meet at one element per block boundary
+    if (n >= 2 && fr_ranges_overlap(d_a, n, d_q, n - 1)) return bad("h2_dev_kate_division: a and q must not overlap");
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         std::lock_guard<std::mutex> g(ctx->mu);
@@ -1127,7 +1135,7 @@ int h2_kate_division(const uint64_t* a, size_t n, const uint64_t b[4], uint64_t*
 
 int h2_dev_prefix_product(const void* d_f, size_t n, const uint64_t init[4], void* d_z, void* stream) {
     if (!init || (n && !d_z) || (n > 1 && !d_f)) return bad("h2_dev_prefix_product: null argument");
-    if (d_f == d_z && n > 1) return bad("h2_dev_prefix_product: in-place is not supported");
+    if (n > 1 && fr_ranges_overlap(d_f, n - 1, d_z, n)) return bad("h2_dev_prefix_product: f and z must not overlap");
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         std::lock_guard<std::mutex> g(ctx->mu);
@@ -1411,7 +1419,7 @@ int h2_dev_distribute_powers(void* d_a, size_t n, const uint64_t g[4], void* str
 
 int h2_dev_prefix_sum(const void* d_f, size_t n, const uint64_t init[4], void* d_z, void* stream) {
     if (!init || (n && !d_z) || (n > 1 && !d_f)) return bad("h2_dev_prefix_sum: null argument");
-    if (d_f == d_z && n > 1) return bad("h2_dev_prefix_sum: in-place is not supported");
+    if (n > 1 && fr_ranges_overlap(d_f, n - 1, d_z, n)) return bad("h2_dev_prefix_sum: f and z must not overlap");
     return guarded([&] {
         DeviceCtx* ctx = current_ctx();
         std::lock_guard<std::mutex> g(ctx->mu);

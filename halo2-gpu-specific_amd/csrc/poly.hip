@@ -480,16 +480,18 @@ int lincomb_launch(Fr* res, const Fr* const* polys, const uint64_t* coeffs, size
         H2_HIP(hipMemsetAsync(res, 0, size * sizeof(Fr), stream));
         return H2_OK;
     }
+    // refused before the first slice is launched: a later slice's alias must not leave `res` half written
+    for (size_t j = 1; j < count; j++)
+        if (polys[j] == res) {
+            set_last_error("h2_dev_lincomb: the result may only alias the first input");
+            return H2_ERR_INVALID;
+        }
     for (size_t j0 = 0; j0 < count; j0 += LINCOMB_MAX) {
         LincombArgs a{};
         a.count = (int)std::min<size_t>(LINCOMB_MAX, count - j0);
         for (int j = 0; j < a.count; j++) {
             a.p[j] = polys[j0 + j];
             a.c[j] = fr_host(coeffs + 4 * (j0 + j));
-            if (a.p[j] == res && (j0 + j) != 0) {
-                set_last_error("h2_dev_lincomb: the result may only alias the first input");
-                return H2_ERR_INVALID;
-            }
         }
         a.res = res;
         a.size = size;

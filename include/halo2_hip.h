@@ -199,12 +199,16 @@ int h2_dev_eval_polynomial_batch(const void *const *d_polys, size_t count, size_
 int h2_batch_invert(uint64_t *a, size_t n);
 int h2_dev_batch_invert(void *d_a, void *d_tmp, size_t n, void *stream);
 /* kate_division: arithmetic.rs:754-773 -- q(X) = a(X) / (X - b) without remainder; a: n coefficients,
- * q: n - 1 (multiopen: gwc/prover.rs:154-160, shplonk/prover.rs).  A blocked affine prefix scan. */
+ * q: n - 1 (multiopen: gwc/prover.rs:154-160, shplonk/prover.rs).  A blocked affine prefix scan.
+ * h2_dev_kate_division: a and q must not overlap (workgroups read a while others write q: H2_ERR_INVALID when
+ * [d_a, d_a + n) and [d_q, d_q + n - 1) share an element and n >= 2).  h2_kate_division may be called with q == a: the
+ * dividend is uploaded before the quotient comes back. */
 int h2_kate_division(const uint64_t *a, size_t n, const uint64_t b[4], uint64_t *q);
 int h2_dev_kate_division(const void *d_a, size_t n, const uint64_t b[4], void *d_q, void *stream);
 /* Grand-product column: z[0] = init, z[i] = z[i-1] * f[i-1] for i < n (f has n - 1 used entries) -- the
  * serial loops of permutation/prover.rs:151-160 (`z.push(last_z); for row in 1..n { tmp *= modified_values[row-1] }`),
- * shuffle/prover.rs and the logup grand sums' multiplicative twin.  f and z must not alias. */
+ * shuffle/prover.rs and the logup grand sums' multiplicative twin.  h2_dev_prefix_product: f and z must not overlap
+ * (H2_ERR_INVALID when d_f[0, n - 1) and d_z[0, n) share an element and n >= 2). */
 int h2_prefix_product(const uint64_t *f, size_t n, const uint64_t init[4], uint64_t *z);
 int h2_dev_prefix_product(const void *d_f, size_t n, const uint64_t init[4], void *d_z, void *stream);
 /* res[i] = sum_j coeffs[j] * polys[j][i] -- the GWC / SHPLONK batching loops (poly/multiopen/gwc/prover.rs:39-151:
@@ -275,7 +279,8 @@ int h2_random_fr(const uint8_t key[32], size_t n, uint64_t *out);
  * that.  The multi-GPU proof shards the extended domain by such cosets (one proof over several ranks). */
 int h2_dev_distribute_powers(void *d_a, size_t n, const uint64_t g[4], void *stream);
 
-/* Grand-sum column: z[0] = init, z[i] = z[i-1] + f[i-1] for i < n -- the `scan` of plonk/logup/prover.rs:353-367. */
+/* Grand-sum column: z[0] = init, z[i] = z[i-1] + f[i-1] for i < n -- the `scan` of plonk/logup/prover.rs:353-367.
+ * f and z must not overlap, as for h2_dev_prefix_product. */
 int h2_dev_prefix_sum(const void *d_f, size_t n, const uint64_t init[4], void *d_z, void *stream);
 /* The multiplicity column of a logup lookup (plonk/logup/prover.rs:104-180): for every row r < usable_rows of each
  * compressed input column, the table row holding that value is credited once; m[row] = credit as a field element

@@ -71,6 +71,41 @@ def test_argument_validation_without_gpu():
         h2.arithmetic.best_fft(np.zeros((5, 4), np.uint64), np.zeros(4, np.uint64), 3)
 
 
+def test_scans_refuse_overlapping_buffers_before_they_touch_a_device():
+    """h2_dev_kate_division reads a[0, n) while other workgroups write q[0, n - 1); h2_dev_prefix_product / _sum read f[0, n - 1)
+    and write z[0, n): any overlap of the two ranges is H2_ERR_INVALID with a message, checked in front of the device (the
+    pointers here are never dereferenced).  Ranges that only touch, and n < 2, pass the check: without a device the call
+    then ends as H2_ERR_NO_DEVICE; with one, tests/test_gpu_poly_kernels.py makes the same calls on live buffers."""
+    L = h2.lib()
+    no_device = L.h2_device_count() == 0
+    scalar = np.zeros(4, dtype=np.uint64)
+    base, n, fr = 1 << 40, 5000, 32
+    kate = lambda a, q, n=n: L.h2_dev_kate_division(a, n, scalar.ctypes.data, q, None)
+    scans = [lambda f, z, n=n, fn=fn: fn(f, n, scalar.ctypes.data, z, None) for fn in (L.h2_dev_prefix_product, L.h2_dev_prefix_sum)]
+
+    def refused(rc):
+        return rc == 1 and b"must not overlap" in L.h2_last_error()
+
+    assert refused(kate(base, base))                           # equal pointers
+    assert refused(kate(base, base + fr))                      # q = a + 32 bytes
+    assert refused(kate(base, base - (n - 2) * fr))            # q's last element is a[0]
+    assert refused(kate(base, base + (n - 1) * fr))            # q's first element is a[n - 1]
+    assert refused(kate(base, base, n=2))
+    for scan in scans:
+        assert refused(scan(base, base))
+        assert refused(scan(base, base + fr))
+        assert refused(scan(base, base - (n - 1) * fr))        # z's last element is f[0]
+        assert refused(scan(base, base + (n - 2) * fr))        # z's first element is f[n - 2], the last one read
+        assert refused(scan(base, base, n=2))
+    if no_device:                                              # accepted by the check: the next thing missing is the device
+        passed = lambda rc: rc not in (0, 1) and b"overlap" not in L.h2_last_error()
+        assert passed(kate(base, base + n * fr)) and passed(kate(base, base - (n - 1) * fr))       # the ranges only touch
+        assert passed(kate(base, base, n=1)) and passed(kate(base, base, n=0))
+        for scan in scans:
+            assert passed(scan(base, base + (n - 1) * fr)) and passed(scan(base, base - n * fr))
+            assert passed(scan(base, base, n=1))
+
+
 def test_evaluate_h_validates_the_descriptor_before_it_touches_memory():
     """h2_evaluate_h / h2_evaluate_h_coeff with extended_k = 29 > 28 and with extended_k = 3 < k = 4 over a 4 KiB `values`:
     H2_ERR_INVALID and a message, with or without a GPU -- the sizes are checked before a slot is leased or a page of `values`
