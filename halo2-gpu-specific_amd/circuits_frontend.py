@@ -13,6 +13,7 @@
   TwoChip            examples/two-chip.rs:473-509             V1, two simple selectors (an add and a mul chip)
   SelectorGates      simple, complex and unused selectors enabled in bulk, strided (no .rs text)
   ShuffleGatesValues ShuffleGates with its witness computed on the device by Values (values.py), at any height
+  LimbDecomposition  p = a b mod 2^(bits words) split into limbs that a range table is looked up for: integer Values
 
 Where an example assigns cell by cell in a loop, the class assigns the loop's range at once; the calls are otherwise the
 example's, in its order."""
@@ -591,3 +592,61 @@ class ShuffleGatesValues(Circuit):
             return region.assign_advice(config.z, 0, columns[2 * W], count=H + 1)
 
         return layouter.assign_region("Shuffle original into shuffled", body)
+
+
+class LimbDecomposition(Circuit):
+    """p = a * b mod 2^(bits * words) and the `words` limbs of `bits` bits of p, on `height` rows: every limb column is looked up
+    in the range table 0 .. 2^bits - 1, and the gate  q (p - sum_j limb_j 2^(bits j)) = 0  ties them to p.  The whole witness
+    exists only as Values (values.py): a and b are seeded u64 cells, p is `(a * b).low(bits * words)` and the limbs are
+    `p.limbs(bits, words, strict=True)` -- the integer half of Value, computed where the Values live.  Keygen passes unknowns:
+    there is no branch on a witness flag.  `columns`: [a, b, p] + limbs as Values instead of the seeded ones."""
+    planner = V1
+
+    def __init__(self, k, bits=8, words=4, height=None, seed=0x4C494D4253, device=None, columns=None):
+        self.k, self.bits, self.words, self.seed, self.device = k, bits, words, seed, device
+        self.height = (1 << k) - 6 if height is None else height
+        if not (1 <= bits and bits * words <= 128 and (1 << bits) <= (1 << k) - 6 and 0 < self.height <= (1 << k) - 6):
+            raise ValueError("LimbDecomposition: the table of 2^bits rows and the height must fit the usable rows, bits * words <= 128")
+        self._columns = columns
+
+    def without_witnesses(self):
+        return LimbDecomposition(self.k, self.bits, self.words, self.height, self.seed, self.device,
+                                 [Value.unknown(self.height)] * (3 + self.words))
+
+    def configure(self, cs):
+        a, b, p = cs.advice_column(), cs.advice_column(), cs.advice_column()
+        limbs = [cs.advice_column() for _ in range(self.words)]
+        q = cs.fixed_column()
+        table = cs.lookup_table_column()
+        total = cs.query_advice(limbs[0])
+        for j in range(1, self.words):
+            total = total + cs.query_advice(limbs[j]) * Constant(1 << (self.bits * j))
+        cs.create_gate("p is the sum of its limbs", [cs.query_fixed(q) * (cs.query_advice(p) - total)])
+        for j, limb in enumerate(limbs):
+            cs.lookup("limb %d is in range" % j, [(cs.query_advice(limb), cs.query_fixed(table))])
+        return _Config(a=a, b=b, p=p, limbs=limbs, q=q, table=table)
+
+    def witness_inputs(self):
+        """the seeded u64 cells of a and b"""
+        rng = np.random.Generator(np.random.PCG64(self.seed))
+        return rng.integers(0, 1 << 64, size=self.height, dtype=np.uint64), rng.integers(0, 1 << 64, size=self.height, dtype=np.uint64)
+
+    def columns(self):
+        """[a, b, p] + limbs as Values, built once"""
+        if self._columns is None:
+            a, b = (Value.from_u64(self.device, x) for x in self.witness_inputs())
+            p = (a * b).low(self.bits * self.words)
+            self._columns = [a, b, p] + p.limbs(self.bits, self.words, strict=True)
+        return self._columns
+
+    def synthesize(self, config, layouter):
+        H = self.height
+        columns = self.columns()
+
+        def body(region):
+            region.assign_fixed(config.q, 0, 1, count=H)
+            for column, values in zip([config.a, config.b, config.p] + config.limbs, columns):
+                region.assign_advice(column, 0, values, count=H)
+
+        layouter.assign_region("limbs", body)
+        layouter.assign_table("range table", lambda table: table.assign_cell(config.table, 0, np.arange(1 << self.bits, dtype=np.uint64)))

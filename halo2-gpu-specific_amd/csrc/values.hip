@@ -34,11 +34,13 @@ struct LdsSlots {
     }
 };
 
+// INTS: the program has integer ops (values.hpp, val_run_row); each instantiation has its one multiplier site
+template <bool INTS>
 __global__ void __launch_bounds__(VAL_THREADS) k_values_eval(const ValProgram P, const size_t m) {
     __shared__ uint32_t sh[VAL_LDS_SLOTS * 8 * VAL_THREADS];
     LdsSlots slots{sh + threadIdx.x, fp_zero<FrParams>()};
     const size_t step = (size_t)gridDim.x * VAL_THREADS;
-    for (size_t row = (size_t)blockIdx.x * VAL_THREADS + threadIdx.x; row < m; row += step) val_run_row(P, row, slots);
+    for (size_t row = (size_t)blockIdx.x * VAL_THREADS + threadIdx.x; row < m; row += step) val_run_row<INTS>(P, row, slots);
 }
 
 }  // namespace
@@ -47,7 +49,8 @@ int values_eval_launch(const ValProgram& P, size_t m, hipStream_t stream) {
     if (m == 0) return H2_OK;
     const size_t want = (m + VAL_THREADS - 1) / VAL_THREADS;
     const unsigned blocks = (unsigned)(want < VAL_MAX_BLOCKS ? want : VAL_MAX_BLOCKS);
-    hipLaunchKernelGGL(k_values_eval, dim3(blocks), dim3(VAL_THREADS), 0, stream, P, m);
+    if (P.has_integer) hipLaunchKernelGGL(k_values_eval<true>, dim3(blocks), dim3(VAL_THREADS), 0, stream, P, m);
+    else hipLaunchKernelGGL(k_values_eval<false>, dim3(blocks), dim3(VAL_THREADS), 0, stream, P, m);
     H2_HIP(hipGetLastError());
     return H2_OK;
 }

@@ -2,10 +2,13 @@
 // straight-line program of field operations over m rows, one lane per row (h2_dev_values_eval) or one row after another on
 // the host (h2_values_eval).  The argument checks and the lowering (values_host.cpp) are the only thing between a caller's
 // program and the kernel's LDS and global accesses; the kernel and the host twin then run the SAME function, val_run_row, on
-// the same lowered program, so their results agree bit for bit.
-// Inside a program every value is a reduced Montgomery residue.  The lowered program has ONE multiplier site,
-// fp_reduce_once(fp_mul_wide(x, y)), which takes any x < 2^256 and a reduced y: a product (x, y), a square (x, x), a leaf
-// conversion (raw words, R^2), a canonical output (x, 1) all go through it.
+// the same lowered program, so their results agree bit for bit (the kernel of a program without integer ops is the
+// instantiation that leaves the integer steps out; a step both have is the same code).
+// Inside a program a value is a FIELD value, a reduced Montgomery residue, or an INTEGER, the canonical representative in
+// [0, r) as plain words; the lowering tracks which and refuses a mismatch, the kernel does not look.  The lowered program has
+// ONE multiplier site, fp_reduce_once(fp_mul_wide(x, y)), which takes any x < 2^256 and a reduced y: a product (x, y), a
+// square (x, x), a leaf conversion (raw words, R^2), a canonical output or TO_INT (x, 1), TO_FIELD (x, R^2) and TO_INT of a
+// canonical leaf (raw words, R: the words mod r) all go through it.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -20,13 +23,15 @@ constexpr uint32_t VAL_MAX_LEAVES = 16, VAL_MAX_OPS = 128, VAL_MAX_CONSTS = 16, 
 // 6 slots: one in registers, five of 8 KiB per workgroup in LDS (DESIGN.md has the register count this was settled against)
 constexpr uint32_t VAL_SLOTS = 6, VAL_THREADS = 256, VAL_MAX_BLOCKS = 1024;
 constexpr uint32_t VAL_MAX_STEPS = VAL_MAX_OPS + VAL_MAX_OUTPUTS;
-// the lowered program's own constants, after the caller's: R^2 (a leaf conversion) and the integer 1 (a canonical output)
-constexpr uint32_t VAL_CONST_RR = VAL_MAX_CONSTS, VAL_CONST_RAW_ONE = VAL_MAX_CONSTS + 1, VAL_CONSTS = VAL_MAX_CONSTS + 2;
+// the lowered program's own constants, after the caller's: R^2 (a leaf conversion, TO_FIELD), the integer 1 (a canonical
+// output, TO_INT) and R mod r (TO_INT of a canonical leaf: raw words * R * R^-1)
+constexpr uint32_t VAL_CONST_RR = VAL_MAX_CONSTS, VAL_CONST_RAW_ONE = VAL_MAX_CONSTS + 1, VAL_CONST_MONT_ONE = VAL_MAX_CONSTS + 2,
+                   VAL_CONSTS = VAL_MAX_CONSTS + 3;
 
-// operand of a lowered step: kind << 8 | index
-constexpr uint32_t VAL_K_LEAF = 0, VAL_K_CONST = 1, VAL_K_SLOT = 2, VAL_K_LAST = 3;
+// operand of a lowered step: kind << 8 | index.  RAW_LEAF (lowered only): the leaf's words as they stand, no conversion
+constexpr uint32_t VAL_K_LEAF = 0, VAL_K_CONST = 1, VAL_K_SLOT = 2, VAL_K_LAST = 3, VAL_K_RAW_LEAF = 4;
 constexpr uint8_t VAL_NONE = 0xff;
-constexpr uint8_t VAL_OP_COPY = 7;  // lowered only: a Montgomery output
+constexpr uint8_t VAL_OP_COPY = 0xfe;  // lowered only: r = a (an output that needs no product, TO_INT of a compact leaf)
 
 struct ValLeaf {
     const void* p;     // element `first` of the caller's buffer
@@ -39,7 +44,7 @@ struct ValStep {
     uint8_t dst;       // slot, or VAL_NONE: the result is read from `last` only, or stored only
     uint8_t store;     // output index, or VAL_NONE
     uint8_t n;         // operands
-    uint16_t opnd[3];
+    uint16_t opnd[3];  // EXTRACT: n = 1, opnd[1] = lo, opnd[2] = the number of bits
     uint16_t pad;
 };
 struct ValProgram {
@@ -48,7 +53,8 @@ struct ValProgram {
     void* out[VAL_MAX_OUTPUTS];   // element `first` of each output
     ValStep step[VAL_MAX_STEPS];
     uint32_t num_steps;
-    uint32_t pad[3];
+    uint32_t has_integer;         // an op code from 16 on: the program runs val_run_row<true>
+    uint32_t pad[2];
 };
 
 H2_DEV Fr val_load32(const void* p) {
@@ -86,13 +92,99 @@ H2_DEV Fr val_leaf_words(const ValLeaf& l, size_t row) {
     return val_load32((const char*)l.p + 32 * e);
 }
 
+// the 32-bit word at bit offset s (0 .. 31) of hi:lo
+H2_DEV uint32_t val_funnel(uint32_t hi, uint32_t lo, uint32_t s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(hi, lo, s);
+#else
+    return (uint32_t)(((uint64_t)hi << 32 | lo) >> s);
+#endif
+}
+
+// (v >> lo) mod 2^n, 0 <= lo <= 255, 1 <= n <= 256.  lo and n come from the program: the word shift is three scalar
+// branches over statically indexed words (no indexed private copy), the bit shift a funnel over adjacent words
+H2_DEV Fr val_extract(Fr v, uint32_t lo, uint32_t n) {
+    const uint32_t words = lo >> 5, bits = lo & 31;
+    if (words & 4) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) v.l[i] = i + 4 < 8 ? v.l[i + 4] : 0;
+    }
+    if (words & 2) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) v.l[i] = i + 2 < 8 ? v.l[i + 2] : 0;
+    }
+    if (words & 1) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) v.l[i] = i + 1 < 8 ? v.l[i + 1] : 0;
+    }
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t w = val_funnel(i + 1 < 8 ? v.l[i + 1] : 0, v.l[i], bits);
+        const uint32_t keep = n > 32u * i ? n - 32u * i : 0;   // bits of word i that stay
+        r.l[i] = keep >= 32 ? w : w & ((1u << keep) - 1);
+    }
+    return r;
+}
+
+// 1 if a < b as 256-bit integers, else 0
+H2_DEV uint32_t val_less(const Fr& a, const Fr& b) {
+    uint32_t borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint64_t t = (uint64_t)a.l[i] - b.l[i] - borrow;
+        borrow = (uint32_t)(t >> 32) & 1;
+    }
+    return borrow;
+}
+
+// EXTRACT (lo, n), LT, AND, OR, XOR of integers below r
+H2_DEV Fr val_integer_op(uint32_t op, const Fr& a, const Fr& b, uint32_t lo, uint32_t n) {
+    Fr r = a;
+    switch (op) {
+        case H2_VALUES_EXTRACT: r = val_extract(a, lo, n); break;
+        case H2_VALUES_LT:
+            r = fp_zero<FrParams>();
+            r.l[0] = val_less(a, b);
+            break;
+        case H2_VALUES_AND:
+#pragma unroll
+            for (int i = 0; i < 8; i++) r.l[i] = a.l[i] & b.l[i];  // <= a < r
+            break;
+        case H2_VALUES_OR:
+#pragma unroll
+            for (int i = 0; i < 8; i++) r.l[i] = a.l[i] | b.l[i];
+            r = fp_reduce_once(r);  // a, b < r < 2^254: a | b < 2^254 < 2 r
+            break;
+        default:
+#pragma unroll
+            for (int i = 0; i < 8; i++) r.l[i] = a.l[i] ^ b.l[i];
+            r = fp_reduce_once(r);
+            break;
+    }
+    return r;
+}
+
 // One row of a lowered (validated) program.  `slots`: load(i) / store(i, v) of this row's slot i.  Everything that steers
 // the control flow comes from the program, which is the same for every row: on the device the branches are uniform.
-template <class Slots>
+// INTS = false leaves out what only a program with an op code from 16 on reaches (P.has_integer): the kernel of the field
+// programs is then, instruction for instruction, the kernel there was before there were integers -- with the integer steps
+// in, the allocator moves the field steps' values about more, and they were measured 4 to 9 % slower.
+template <bool INTS, class Slots>
 H2_DEV void val_run_row(const ValProgram& P, size_t row, Slots& slots) {
     Fr last = fp_zero<FrParams>();
     for (uint32_t s = 0; s < P.num_steps; s++) {
         const ValStep st = P.step[s];
+        if (INTS && st.op >= H2_VALUES_EXTRACT && st.op <= H2_VALUES_XOR) {
+            // An integer step, apart from the field steps below.  Its operands are slots or `last` (the lowering refuses leaves and constants), it has no
+            // product, and it stores nothing (an output is a step of its own)
+            const Fr ia = st.opnd[0] >> 8 == VAL_K_SLOT ? slots.load(st.opnd[0] & 0xff) : last;
+            Fr ib = ia;
+            if (st.n > 1) ib = st.opnd[1] >> 8 == VAL_K_SLOT ? slots.load(st.opnd[1] & 0xff) : last;
+            last = val_integer_op(st.op, ia, ib, st.opnd[1], st.opnd[2]);
+            if (st.dst != VAL_NONE) slots.store(st.dst, last);
+            continue;
+        }
         Fr a = fp_zero<FrParams>(), b = a, c = a, r = a;
         // micro-steps 0..2 fetch (and convert) the operands, 3 is the product of the operation itself: one multiplier site
 #pragma unroll 1
@@ -105,9 +197,9 @@ H2_DEV void val_run_row(const ValProgram& P, size_t row, Slots& slots) {
                 const uint32_t kind = word >> 8, idx = word & 0xff;
                 mul = false;
                 y = P.konst[VAL_CONST_RR];
-                if (kind == VAL_K_LEAF) {
+                if (kind == VAL_K_LEAF || (INTS && kind == VAL_K_RAW_LEAF)) {
                     x = val_leaf_words(P.leaf[idx], row);
-                    mul = P.leaf[idx].form != H2_ASSIGNED_FORM_MONTGOMERY;
+                    mul = (!INTS || kind == VAL_K_LEAF) && P.leaf[idx].form != H2_ASSIGNED_FORM_MONTGOMERY;
                 } else if (kind == VAL_K_CONST) {
                     x = P.konst[idx];
                 } else if (kind == VAL_K_SLOT) {

@@ -32,8 +32,41 @@ uint32_t operands_of(uint32_t op) {
         case H2_VALUES_NEG:
         case H2_VALUES_ISZERO: return 1;
         case H2_VALUES_SELECT: return 3;
+        case H2_VALUES_TO_INT:
+        case H2_VALUES_TO_FIELD:
+        case H2_VALUES_EXTRACT: return 1;  // b and c of an EXTRACT are plain numbers
+        case H2_VALUES_LT:
+        case H2_VALUES_AND:
+        case H2_VALUES_OR:
+        case H2_VALUES_XOR: return 2;
         default: return 0;
     }
+}
+
+// what a value is: VAL_ANY in a requirement takes either
+enum : uint8_t { VAL_FIELD = 0, VAL_INT = 1, VAL_ANY = 2 };
+
+// the kind an operand of `op` must have (SELECT: a takes either; b against c is checked apart)
+uint8_t wants(uint32_t op) {
+    switch (op) {
+        case H2_VALUES_ISZERO:
+        case H2_VALUES_SELECT: return VAL_ANY;
+        case H2_VALUES_TO_FIELD:
+        case H2_VALUES_EXTRACT:
+        case H2_VALUES_LT:
+        case H2_VALUES_AND:
+        case H2_VALUES_OR:
+        case H2_VALUES_XOR: return VAL_INT;
+        default: return VAL_FIELD;
+    }
+}
+
+// "slot 2 holds" / "the last result is" / "leaf 1 is" / "constant 0 is"
+void holder(char* out, size_t room, uint32_t word) {
+    const unsigned kind = word >> 24, idx = word & 0xffffffu;
+    if (kind == H2_VALUES_SLOT) snprintf(out, room, "slot %u holds", idx);
+    else if (kind == H2_VALUES_LAST) snprintf(out, room, "the last result is");
+    else snprintf(out, room, "%s %u is", kind == H2_VALUES_LEAF ? "leaf" : "constant", idx);
 }
 
 }  // namespace
@@ -80,11 +113,17 @@ const char* values_lower(const h2_values_leaf* leaves, size_t num_leaves, const 
     }
     for (int i = 0; i < 8; i++) P->konst[VAL_CONST_RR].l[i] = FrParams::RR[i];
     P->konst[VAL_CONST_RAW_ONE].l[0] = 1;
+    for (int i = 0; i < 8; i++) P->konst[VAL_CONST_MONT_ONE].l[i] = FrParams::ONE[i];
 
-    // the caller's ops as steps; `writer[s]`: the step that wrote slot s last, or none
+    // the caller's ops as steps; `writer[s]`: the step that wrote slot s last, or none; `holds[s]`: the kind it left there
     int writer[VAL_SLOTS];
-    for (uint32_t s = 0; s < VAL_SLOTS; s++) writer[s] = -1;
+    uint8_t holds[VAL_SLOTS], last_kind = VAL_FIELD;
+    for (uint32_t s = 0; s < VAL_SLOTS; s++) writer[s] = -1, holds[s] = VAL_FIELD;
     uint32_t steps = 0;
+    auto kind_of = [&](uint32_t word) -> uint8_t {  // of an operand that `operand` accepted
+        const uint32_t kind = word >> 24;
+        return kind == H2_VALUES_SLOT ? holds[word & 0xffffffu] : kind == H2_VALUES_LAST ? last_kind : (uint8_t)VAL_FIELD;
+    };
     auto operand = [&](uint32_t word, size_t i, uint16_t* out) -> const char* {
         const uint32_t kind = word >> 24, idx = word & 0xffffffu;
         if (kind == H2_VALUES_LEAF) {
@@ -114,9 +153,44 @@ const char* values_lower(const h2_values_leaf* leaves, size_t num_leaves, const 
         ValStep& st = P->step[steps];
         st.op = (uint8_t)o.op, st.dst = kept ? (uint8_t)o.dst : VAL_NONE, st.store = VAL_NONE, st.n = (uint8_t)n;
         const uint32_t words[3] = {o.a, o.b, o.c};
-        for (uint32_t k = 0; k < n; k++)
+        uint8_t result = VAL_FIELD;
+        if (o.op >= H2_VALUES_TO_INT) P->has_integer = 1;
+        for (uint32_t k = 0; k < n; k++) {
             if (const char* what = operand(words[k], i, &st.opnd[k])) return what;
-        if (kept) writer[o.dst] = (int)steps;
+            const uint8_t want = wants(o.op), have = kind_of(words[k]);
+            if (want != VAL_ANY && want != have) {
+                char who[48];
+                holder(who, sizeof who, words[k]);
+                snprintf(g_what, sizeof g_what, "op %lu takes %s in operand %c; %s %s", (unsigned long)i,
+                         want == VAL_INT ? "an integer" : "a field value", "abc"[k], who, have == VAL_INT ? "an integer" : "a field value");
+                return g_what;
+            }
+        }
+        if (o.op == H2_VALUES_SELECT) {
+            if (kind_of(o.b) != kind_of(o.c)) return whatf("op %lu selects between a field value and an integer: b and c must be of one kind", i);
+            result = kind_of(o.b);
+        } else if (o.op == H2_VALUES_TO_INT) {
+            // x * 1 * R^-1; a compact leaf is its own integer, a canonical leaf's raw words * R * R^-1 are the words mod r
+            result = VAL_INT;
+            const uint32_t form = (o.a >> 24) == H2_VALUES_LEAF ? leaves[o.a & 0xffffffu].form : (uint32_t)H2_ASSIGNED_FORM_MONTGOMERY;
+            if (form == H2_ASSIGNED_FORM_COMPACT) {
+                st.op = VAL_OP_COPY, st.opnd[0] = (uint16_t)(VAL_K_RAW_LEAF << 8 | (o.a & 0xff));
+            } else {
+                st.op = H2_VALUES_MUL, st.n = 2;
+                if (form == H2_ASSIGNED_FORM_CANONICAL) st.opnd[0] = (uint16_t)(VAL_K_RAW_LEAF << 8 | (o.a & 0xff));
+                st.opnd[1] = (uint16_t)(VAL_K_CONST << 8 | (form == H2_ASSIGNED_FORM_CANONICAL ? VAL_CONST_MONT_ONE : VAL_CONST_RAW_ONE));
+            }
+        } else if (o.op == H2_VALUES_TO_FIELD) {
+            st.op = H2_VALUES_MUL, st.n = 2, st.opnd[1] = (uint16_t)(VAL_K_CONST << 8 | VAL_CONST_RR);
+        } else if (o.op == H2_VALUES_EXTRACT) {
+            if (o.b > 255) return whatf("op %lu extracts from bit %lu: lo must be between 0 and 255", i, o.b);
+            if (o.c < 1 || o.c > 256) return whatf("op %lu extracts %lu bits: n must be between 1 and 256", i, o.c);
+            result = VAL_INT, st.opnd[1] = (uint16_t)o.b, st.opnd[2] = (uint16_t)o.c;
+        } else if (o.op >= H2_VALUES_LT) {
+            result = VAL_INT;
+        }
+        last_kind = result;
+        if (kept) writer[o.dst] = (int)steps, holds[o.dst] = result;
         steps++;
     }
     // the outputs: one more step each, at the end -- every load of a row precedes every store of it
@@ -141,10 +215,12 @@ const char* values_lower(const h2_values_leaf* leaves, size_t num_leaves, const 
         ValStep& st = P->step[steps];
         st.dst = VAL_NONE, st.store = (uint8_t)i;
         const uint16_t src = (uint16_t)((writer[o.slot] + 1 == (int)steps ? VAL_K_LAST : VAL_K_SLOT) << 8 | o.slot);
-        if (o.form == H2_ASSIGNED_FORM_MONTGOMERY) {
+        // a field slot: as it stands (Montgomery) or x * 1 * R^-1; an integer slot: x * R^2 * R^-1 or as it stands
+        if ((o.form == H2_ASSIGNED_FORM_MONTGOMERY) == (holds[o.slot] == VAL_FIELD)) {
             st.op = VAL_OP_COPY, st.n = 1, st.opnd[0] = src;
         } else {
-            st.op = H2_VALUES_MUL, st.n = 2, st.opnd[0] = src, st.opnd[1] = (uint16_t)(VAL_K_CONST << 8 | VAL_CONST_RAW_ONE);
+            st.op = H2_VALUES_MUL, st.n = 2, st.opnd[0] = src;
+            st.opnd[1] = (uint16_t)(VAL_K_CONST << 8 | (holds[o.slot] == VAL_FIELD ? VAL_CONST_RAW_ONE : VAL_CONST_RR));
         }
         steps++;
     }
@@ -175,7 +251,7 @@ struct HostSlots {
 void values_eval_host(const ValProgram& P, size_t m) {
     HostSlots slots;
     memset((void*)&slots, 0, sizeof slots);
-    for (size_t row = 0; row < m; row++) val_run_row(P, row, slots);
+    for (size_t row = 0; row < m; row++) val_run_row<true>(P, row, slots);  // the field steps of <false> are these
 }
 
 }  // namespace h2

@@ -18,6 +18,11 @@ assignment asks for the elements.  Then the compiler below turns the expression 
                           k nested levels of division cost k + 1 evaluator launches and k inversions (per distinct length,
                           and per `outputs` denominators of one length)
   scans, concat, take     their operands are materialised first; their results are leaves
+  integers                bits / >> / low / bit / limbs, & | ^ and lt / le / gt / ge read a cell as the integer in [0, r).
+                          Inside a program a value is a field element or an integer (`_Node.vkind`); the compiler inserts
+                          to_int / to_field where an operand's kind is not what the op takes, hash-consing shares them (one
+                          to_int serves every limb of a value), and a to_int of a compact leaf costs no product.  Users never
+                          see kinds: every Value reads back as field elements
 
 Device work is allocated and launched under the device's compute stream, as check.py does, so that an assignment's flush
 (DeviceColumns._flush) sees finished values.  `device.values_launches` / `device.values_inversions` count the calls.
@@ -29,7 +34,11 @@ from .circuit import R_MOD
 from .domain import _fr
 
 FORM_CANONICAL, FORM_MONTGOMERY, FORM_COMPACT = 0, 1, 2                                  # H2_ASSIGNED_FORM_*
-OP_CODES = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "neg": 4, "select": 5, "iszero": 6}  # H2_VALUES_*
+OP_CODES = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "neg": 4, "select": 5, "iszero": 6,  # H2_VALUES_*
+            "to_int": 16, "to_field": 17, "extract": 18, "lt": 19, "and": 20, "or": 21, "xor": 22}
+FIELD, INT = "field", "int"                                                              # what a value inside a program is
+INT_RESULT = ("to_int", "extract", "lt", "and", "or", "xor")                             # ops that give an integer
+INT_OPERANDS = ("to_field", "extract", "lt", "and", "or", "xor")                         # ops that take integers
 KIND_LEAF, KIND_CONST, KIND_SLOT, KIND_LAST = 0, 1, 2, 3                                 # H2_VALUES_LEAF / CONST / SLOT / LAST
 NO_SLOT = 0xFFFFFFFF                                                                     # H2_VALUES_NO_SLOT
 # h2_values_leaf, h2_values_op, h2_values_output, h2_values_caps
@@ -106,6 +115,13 @@ class _HostBackend:
     def gather(self, a, indices):
         return np.ascontiguousarray(a[np.asarray(indices, dtype=np.int64)])
 
+    def rows_at_or_above(self, a, bound):
+        """the rows of canonical cells whose integer is `bound` (< 2^63) or more"""
+        return np.flatnonzero(a[:, 1:].any(axis=1) | (a[:, 0] >= np.uint64(bound)))
+
+    def low_words(self, a):
+        return a[:, 0].astype(np.int64)
+
     def upload(self, a):
         return np.ascontiguousarray(a)
 
@@ -171,6 +187,13 @@ class _DeviceBackend:
                 indices = torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int64)).to(self.D.dev)
             return t[indices.to(torch.int64)].contiguous()
 
+    def rows_at_or_above(self, t, bound):
+        with self.D.torch.cuda.stream(self.D.tstream):               # 64-bit words are signed here: negative is 2^63 or more
+            return ((t[:, 1:] != 0).any(dim=1) | (t[:, 0] < 0) | (t[:, 0] >= bound)).nonzero().flatten().cpu().numpy()
+
+    def low_words(self, t):
+        return t[:, 0]
+
     def upload(self, a):
         return self.D.upload(np.ascontiguousarray(a), widen=False)
 
@@ -214,11 +237,16 @@ class _Pending:
 
 
 class _Node:
-    """kind = leaf (buffer) | const (value) | an op of OP_CODES (args: Values); `count` elements before any view"""
-    __slots__ = ("kind", "args", "count", "buffer", "value", "cache")
+    """kind = leaf (buffer) | const (value) | an op of OP_CODES (args: Values; extract: value = (lo, n)); `count` elements
+    before any view; vkind: the result is a field element or an integer inside a program"""
+    __slots__ = ("kind", "args", "count", "buffer", "value", "cache", "vkind")
 
     def __init__(self, kind, count, args=(), buffer=None, value=None):
         self.kind, self.count, self.args, self.buffer, self.value, self.cache = kind, count, args, buffer, value, None
+        if kind == "select":
+            self.vkind = INT if args[1]._node.vkind == args[2]._node.vkind == INT else FIELD
+        else:
+            self.vkind = INT if kind in INT_RESULT else FIELD
 
 
 class Value:
@@ -304,7 +332,7 @@ class Value:
         return None
 
     @staticmethod
-    def _op(kind, *args):
+    def _op(kind, *args, value=None):
         count = args[0].count
         for other in args[1:]:
             if other.count != count:
@@ -319,7 +347,7 @@ class Value:
                 device = a.device
         if device is not None and any(a.device is None and a._node.kind != "const" for a in args):
             raise ValueError("a host value and a device value do not combine")
-        return Value(device, count, _Node(kind, count, args))
+        return Value(device, count, _Node(kind, count, args, value=value))
 
     def _binary(self, kind, other, swap=False):
         other = self._lift(other)
@@ -372,6 +400,74 @@ class Value:
             raise TypeError("select takes at least one Value")
         return Value._op("select", *(base._lift(v) for v in (cond, a, b)))
 
+    # -- a cell as the integer in [0, r): bit fields, limbs, bitwise operations, comparisons ----------------------------------
+    def bits(self, lo, n):
+        """(v >> lo) mod 2^n of the integer v in [0, r)"""
+        lo, n = int(lo), int(n)
+        if not (0 <= lo <= 255 and 1 <= n):
+            raise ValueError("bits(lo, n): 0 <= lo <= 255 and n >= 1")
+        return Value._op("extract", self, value=(lo, min(n, 256)))
+
+    def __rshift__(self, k):
+        if not isinstance(k, (int, np.integer)) or k < 0:
+            raise TypeError(">> takes a non-negative integer")
+        if k >= 256:
+            return Value.full(self.device, self.count, 0) if self.known else Value.unknown(self.count)
+        return self.bits(k, 256 - k)
+
+    def low(self, n):
+        """v mod 2^n"""
+        return self.bits(0, n)
+
+    def bit(self, i):
+        return self.bits(i, 1)
+
+    def __and__(self, other):
+        return self._binary("and", other)
+
+    __rand__ = __and__
+
+    def __or__(self, other):
+        return self._binary("or", other)
+
+    __ror__ = __or__
+
+    def __xor__(self, other):
+        return self._binary("xor", other)
+
+    __rxor__ = __xor__
+
+    def lt(self, other):
+        """1 where self < other as integers in [0, r), else 0"""
+        return self._binary("lt", other)
+
+    def gt(self, other):
+        return self._binary("lt", other, swap=True)
+
+    def le(self, other):
+        return 1 - self.gt(other)
+
+    def ge(self, other):
+        return 1 - self.lt(other)
+
+    def limbs(self, bits, count, strict=False):
+        """`count` Values: limb j = (v >> bits * j) mod 2^bits.  Materialised together they cost ceil(count / outputs cap)
+        launches and one to_int.  `strict`: a row whose value is 2^(bits * count) or more raises ValueError on
+        materialisation, naming the first (the rest of v >> bits * count is one more output)"""
+        bits, count = int(bits), int(count)
+        if bits < 1 or count < 1 or bits * count > 256:
+            raise ValueError("limbs(bits, count): 1 <= bits, 1 <= count and bits * count <= 256")
+        parts = [self.bits(bits * j, bits) for j in range(count)]
+        if not strict or not self.known:
+            return parts
+        if bits * count < 256:
+            parts.append(self >> bits * count)
+        group = []
+        pending = _Pending("limbs", tuple(parts), (bits, count, group))
+        for _ in range(count):
+            group.append(_Buffer(None, FORM_CANONICAL, self.count, pending))
+        return [Value(self.device, self.count, _Node("leaf", self.count, buffer=buf)) for buf in group]
+
     # -- inversion, scans, concat, take: results are leaves over a buffer that is filled on materialisation ------------------
     def _deferred(self, kind, count, args, extra=None, device=None):
         pending = _Pending(kind, args, extra)
@@ -416,7 +512,16 @@ class Value:
         return parts[0]._deferred("concat", count, tuple(parts), device=device) if parts else Value.from_ints(None, [])
 
     def take(self, indices):
-        """self[indices]: materialises, then gathers"""
+        """self[indices]: materialises, then gathers.  `indices`: a host array, a tensor, or a Value of integers -- that one
+        is materialised and checked against len(self) where it lives (IndexError names the first row out of range; the
+        gather is not issued), and only the offending row ever reaches the host"""
+        if isinstance(indices, Value):
+            if not (self.known and indices.known):
+                return Value.unknown(len(indices))
+            device = self.device if self.device is not None else indices.device
+            if indices.device is not None and indices.device is not device:
+                raise ValueError("values of two devices do not combine")
+            return self._deferred("take", len(indices), (self, indices), None, device=device)
         if not self.known:
             return Value.unknown(len(indices))
         return self._deferred("take", len(indices), (self,), indices)
@@ -514,7 +619,7 @@ def _resolve_pending(values, be):
             return
         inversions = [buf for buf in ready if buf.pending.kind == "inv"]
         for buf in ready:
-            if buf.pending.kind != "inv":
+            if buf.pending is not None and buf.pending.kind != "inv":   # the limbs of one group resolve together
                 _resolve_other(buf, be)
         if inversions:
             _resolve_inversions(inversions, be)
@@ -556,7 +661,18 @@ def _resolve_other(buf, be):
             outs.append((data, at))
             at += part.count
         _evaluate(list(args), be, FORM_MONTGOMERY, outs)
+    elif kind == "limbs":
+        _resolve_limbs(buf.pending, be)
+        return
     else:                                                           # take
+        if len(args) == 2:                                          # a Value of integers: checked where it lives
+            index = _evaluate([args[1]], be, FORM_CANONICAL)[0]
+            bad = be.rows_at_or_above(index, args[0].count) if args[1].count else []
+            if len(bad):
+                row = int(bad[0])
+                value = limbs_to_ints(be.download(index[row:row + 1]))[0]
+                raise IndexError("take: index %d at row %d is out of range for %d elements" % (value, row, args[0].count))
+            extra = be.low_words(index)
         node = args[0]._node
         if node.kind == "leaf" and args[0]._whole():                # elements as they stand, in whatever form: no launch
             data, buf.form = be.gather(be.data(node.buffer), extra), node.buffer.form
@@ -565,24 +681,80 @@ def _resolve_other(buf, be):
     buf.data, buf.ordered, buf.pending = data, True, None
 
 
+def _resolve_limbs(pending, be):
+    """limbs(strict=True): every limb into its own canonical buffer, and what is left above them checked to be zero"""
+    bits, count, group = pending.extra
+    m = group[0].length
+    outs = [(be.empty(m), 0) for _ in pending.args]
+    _evaluate(list(pending.args), be, FORM_CANONICAL, outs)
+    if len(pending.args) > count and m:
+        high = be.zero_rows(outs[count][0])
+        if len(high) < m:
+            zero = np.zeros(m, dtype=bool)
+            zero[high] = True
+            raise ValueError("limbs(strict=True): element %d of the %d does not fit %d limbs of %d bits" % (
+                int(np.flatnonzero(~zero)[0]), m, count, bits))
+    for buf, (data, _) in zip(group, outs):
+        buf.data, buf.ordered, buf.pending = data, True, None
+
+
 # -- the compiler --------------------------------------------------------------------------------------------------------------
 class _Overflow(Exception):
     pass
 
 
 class _Dag:
-    """hash-consed expressions: ids ascend from operands to results.  An entry is ("leaf", buffer, first, stride, form),
-    ("const", value) or (op, operand ids)"""
+    """hash-consed expressions: the ids of ops ascend from operands to results.  An entry is ("leaf", buffer, first, stride,
+    form), ("const", value) or (op, operand ids) -- ("extract", (id,), (lo, n)); kinds[id]: FIELD or INT.  Leaves and
+    constants are field values; an operand of another kind than its op takes goes through a to_int / to_field, interned
+    like everything else, so every reader of one value shares one conversion"""
 
     def __init__(self):
-        self.entries, self.index, self.memo = [], {}, {}
+        self.entries, self.kinds, self.index, self.memo = [], [], {}, {}
 
     def _intern(self, key, entry):
         at = self.index.get(key)
         if at is None:
             at = self.index[key] = len(self.entries)
             self.entries.append(entry)
+            if entry[0] == "select":
+                self.kinds.append(self.kinds[entry[1][1]])
+            else:
+                self.kinds.append(INT if entry[0] in INT_RESULT else FIELD)
         return at
+
+    def op(self, kind, ids, params=None):
+        """the id of op `kind` over `ids`, conversions inserted"""
+        if kind == "select":
+            arms = INT if self.kinds[ids[1]] == self.kinds[ids[2]] == INT else FIELD
+            ids = (ids[0], self.convert(ids[1], arms), self.convert(ids[2], arms))
+        elif kind != "iszero":
+            want = INT if kind in INT_OPERANDS else FIELD
+            ids = tuple(self.convert(at, want) for at in ids)
+        if kind in ("add", "mul", "and", "or", "xor"):
+            ids = tuple(sorted(ids))
+        key = (kind, ids) if params is None else (kind, ids, params)
+        return self._intern(key, key)
+
+    def convert(self, at, want):
+        if self.kinds[at] == want:
+            return at
+        entry = self.entries[at]
+        if entry[0] in ("to_int", "to_field") and self.kinds[entry[1][0]] == want:     # there and back again: the value itself
+            return entry[1][0]
+        kind = "to_int" if want == INT else "to_field"
+        return self._intern((kind, (at,)), (kind, (at,)))
+
+    def replace_by_leaf(self, at, buffer, first, form):
+        """entry `at` was materialised into `buffer`: from now on it is read, not computed.  A leaf is a field value, so an
+        integer keeps its id as the to_int of a new leaf (leaves take no part in the order of ids)"""
+        leaf = ("leaf", buffer, first, 1, form)
+        if self.kinds[at] == INT:
+            self.entries.append(leaf)
+            self.kinds.append(FIELD)
+            self.entries[at] = ("to_int", (len(self.entries) - 1,))
+        else:
+            self.entries[at] = leaf
 
     def leaf(self, buffer, first, stride, form):
         return self._intern(("leaf", id(buffer), first, stride, form), ("leaf", buffer, first, stride, form))
@@ -619,10 +791,7 @@ class _Dag:
                 if missing:
                     stack.extend(missing)
                     continue
-                ids = tuple(self.memo[key_of(k)] for k in kids)
-                if node.kind in ("add", "mul"):
-                    ids = tuple(sorted(ids))
-                self.memo[key] = self._intern((node.kind, ids), (node.kind, ids))
+                self.memo[key] = self.op(node.kind, tuple(self.memo[key_of(k)] for k in kids), node.value)
             stack.pop()
         return self.memo[key_of(root)]
 
@@ -697,9 +866,9 @@ def _schedule(dag, roots, caps):
             prog.constants.append(entry[1])
         return KIND_CONST << 24 | const_index[at]
 
-    def emit(kind, kids, transient):
+    def emit(kind, kids, transient, params=()):
         words = [(KIND_LAST << 24 if slot_of[c] is None else KIND_SLOT << 24 | slot_of[c]) if dag.interior(c) else terminal(c)
-                 for c in kids]
+                 for c in kids] + list(params)                      # extract: lo and n ride in b and c as plain numbers
         for c in kids:
             if dag.interior(c):
                 uses[c] -= 1
@@ -721,10 +890,10 @@ def _schedule(dag, roots, caps):
         return dst
 
     for p, at in enumerate(order):
-        kind, kids = dag.entries[at]
+        kind, kids = dag.entries[at][:2]
         # read once, by the very next op, and no output: it lives in the kernel's `last` and takes no slot
         transient = uses[at] == 1 and at not in roots and p + 1 < len(order) and at in dag.entries[order[p + 1]][1]
-        slot_of[at] = emit(kind, kids, transient)
+        slot_of[at] = emit(kind, kids, transient, dag.entries[at][2] if kind == "extract" else ())
     zero = None
     for r in roots:
         if dag.interior(r):
@@ -770,11 +939,12 @@ LAST_PROGRAMS = []          # the programs launched most recently (tests and too
 
 
 def _split_candidate(dag, roots, caps):
-    """the largest proper subexpression that fits a launch of its own -> (id, its program)"""
+    """the largest proper subexpression that fits a launch of its own -> (id, its program).  An integer is read back through
+    a to_int (_Dag.replace_by_leaf), so giving one up shortens the program only if it is more than one op"""
     total = dag.cone(roots)
     sizes = sorted(((len(dag.cone([at])), at) for at in total), reverse=True)
     for size, at in sizes:
-        if size > caps["ops"] or (size == len(total) and len(roots) == 1):
+        if size > caps["ops"] or (size == len(total) and len(roots) == 1) or (size == 1 and dag.kinds[at] == INT):
             continue
         try:
             return at, _schedule(dag, [at], caps)
@@ -832,11 +1002,11 @@ def _run(dag, roots, dests, form, m, be, caps):
                 _launch(sub, [dests[k]], form, m, be)
                 buffer, lfirst, lform = _Buffer(data, form, first + m, ordered=True), first, form
                 del roots[k], dests[k]
-            else:
-                data = be.empty(m)
-                _launch(sub, [(data, 0)], FORM_MONTGOMERY, m, be)
-                buffer, lfirst, lform = _Buffer(data, FORM_MONTGOMERY, m, ordered=True), 0, FORM_MONTGOMERY
-            dag.entries[at] = ("leaf", buffer, lfirst, 1, lform)
+            else:                                                   # in the form that costs no product either way
+                data, lform = be.empty(m), FORM_CANONICAL if dag.kinds[at] == INT else FORM_MONTGOMERY
+                _launch(sub, [(data, 0)], lform, m, be)
+                buffer, lfirst = _Buffer(data, lform, m, ordered=True), 0
+            dag.replace_by_leaf(at, buffer, lfirst, lform)
             continue
         _launch(prog, dests, form, m, be)
         return
@@ -855,7 +1025,7 @@ def plan(values):
         except _Overflow:
             at, sub = _split_candidate(dag, roots, caps)
             out.append(sub)
-            dag.entries[at] = ("leaf", _Buffer(None, FORM_MONTGOMERY, values[0].count), 0, 1, FORM_MONTGOMERY)
+            dag.replace_by_leaf(at, _Buffer(None, FORM_MONTGOMERY, values[0].count), 0, FORM_MONTGOMERY)
             if at in roots:
                 roots.remove(at)
                 if not roots:

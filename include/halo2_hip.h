@@ -1003,6 +1003,23 @@ int h2_coverage_check(const h2_coverage_plane *planes, size_t num_planes, const 
  *              op before it is read.
  *   outputs    row i of slot `slot`, as it stands at the END of the program, goes to element first + i of `ptr` (32-byte
  *              elements, contiguous) in `form`, CANONICAL or MONTGOMERY, fully reduced.
+ *   kinds      a value inside a program is of one of two kinds: a FIELD value (a reduced Montgomery residue: what every leaf,
+ *              every constant and ADD SUB MUL SQR NEG ISZERO give) or an INTEGER, the canonical representative v in [0, r)
+ *              as plain 256-bit words, in the same slots.  The codes from 16 on work on integers:
+ *                TO_INT    a: field            the integer v (of a CANONICAL leaf holding any 256-bit integer: v mod r; of a
+ *                                              COMPACT leaf: the u64 itself, at no product)
+ *                TO_FIELD  a: integer          the field element
+ *                EXTRACT   a: integer          (v >> lo) mod 2^n; `b` = lo and `c` = n are PLAIN NUMBERS, not operands,
+ *                                              0 <= lo <= 255, 1 <= n <= 256
+ *                LT        a, b: integers      the integer 1 if v_a < v_b, else 0
+ *                AND OR XOR  a, b: integers    the bitwise result, an integer.  OR and XOR of two integers below r can reach
+ *                                              r or more; the result is reduced by ONE conditional subtraction of r, which is
+ *                                              enough: it is below 2^254, which is below 2 r.  ((r - 1) | 1 = r gives 0.)
+ *              ADD SUB MUL SQR NEG take field values only; ISZERO takes either kind and gives the FIELD 1 or 0; SELECT takes
+ *              either kind in a, and b and c of one kind, which is the result's.  An integer op takes slots and LAST only:
+ *              a leaf or a constant is a field operand and goes through TO_INT first.  An output of an integer slot is a
+ *              plain store in CANONICAL form and the product x * R^2 (the residue of the same element) in MONTGOMERY form.
+ *              Codes 7 .. 15 are not op codes.
  * Overlap rule: the m elements of an output may not overlap the elements a leaf of the same call reads, nor another output,
  * with ONE exception: a 32-byte leaf of stride 1 whose element i is the very bytes of the output's element i (in place).
  * Every load of a row precedes every store of that row and rows do not talk to each other, so that mapping alone is safe.
@@ -1014,9 +1031,11 @@ int h2_coverage_check(const h2_coverage_plane *planes, size_t num_planes, const 
  * read or written, h2_last_error naming what is wrong, for a count above its cap, a null or misaligned pointer (16 bytes
  * for 32-byte elements on the device, 8 on the host; 8 for compact), an unknown form or op, a slot index at or above the
  * cap, an operand that names a leaf or constant that does not exist or a slot never written, LAST in the first op, a leaf whose range passes
- * `len`, or an overlap the rule above refuses.  m == 0 succeeds and touches nothing. */
+ * `len`, an operand of the wrong kind ("op 3 takes an integer in operand a; slot 2 holds a field value"), lo or n of an
+ * EXTRACT out of range, or an overlap the rule above refuses.  m == 0 succeeds and touches nothing. */
 enum { H2_VALUES_ADD = 0, H2_VALUES_SUB = 1, H2_VALUES_MUL = 2, H2_VALUES_SQR = 3, H2_VALUES_NEG = 4, H2_VALUES_SELECT = 5,
-       H2_VALUES_ISZERO = 6 };
+       H2_VALUES_ISZERO = 6, H2_VALUES_TO_INT = 16, H2_VALUES_TO_FIELD = 17, H2_VALUES_EXTRACT = 18, H2_VALUES_LT = 19,
+       H2_VALUES_AND = 20, H2_VALUES_OR = 21, H2_VALUES_XOR = 22 };
 enum { H2_VALUES_LEAF = 0, H2_VALUES_CONST = 1, H2_VALUES_SLOT = 2, H2_VALUES_LAST = 3 };
 #define H2_VALUES_NO_SLOT 0xffffffffu
 typedef struct {

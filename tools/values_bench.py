@@ -1,6 +1,6 @@
 """What computing a witness with Values (values.py, csrc/values.hip) costs on the device.
 
-usage: python tools/values_bench.py K [--reps R] [--python-height H]
+usage: python tools/values_bench.py K [--reps R] [--python-height H] [--integers] [--stream-gbs RATE]
 
 Three cases over 2^K rows of seeded random data, one process, after the clock-settling load bench.py uses:
   (a) a*b*c + d from four COMPACT leaves (8-byte cells), one fused launch, canonical cells out -- and the same composed from
@@ -9,6 +9,13 @@ Three cases over 2^K rows of seeded random data, one process, after the clock-se
   (c) the shuffle argument's running product of width 4: z = ((compress(orig) + beta) / (compress(shuf) + beta)).cumprod()
       -- two fused launches, one batch inversion, one scan; against circuits.shuffle_gates_witness (Python integers) at
       --python-height rows (default 2^17, about a second), the ratio stated per row
+With --integers, two more (and case (c) is left out):
+  (d) a COMPACT u64 column to four 16-bit limb columns in canonical form, `from_u64(...).limbs(16, 4)`: one launch, no field
+      product -- against what there was before: torch shifts and masks on the u64 tensor, then 4 x h2_dev_widen_u64
+  (e) a MONTGOMERY column to 32 8-bit limb columns, `limbs(8, 32)`: ceil(32 / outputs cap) = 8 launches, each converting the
+      column again (one product per row and launch) -- against download + Python integers + upload, which is timed at
+      --python-height rows (2^16 in the recorded runs) and scaled per row.  Bytes moved are also stated as a share of
+      --stream-gbs, the streaming rate tools/membench reads and writes with on the same device (GB/s; given by the caller).
 Times are between two stream events around the call(s): median, minimum and maximum of R repetitions (default 9), the
 variants of a case taking turns.  `fused` is the launch of the compiled program (its argument tables built, the kernel run);
 `fused_with_compile` the whole `Value` expression from scratch, whose host time (building and scheduling the expression, about
@@ -100,6 +107,74 @@ def compiled(D, value, montgomery=False):
     return out, lambda: V._launch(prog, [(out, 0)], form, len(value), V._backend(D))
 
 
+def compiled_many(D, values):
+    """-> (the results, relaunch, launches): like `compiled` for several Values materialised together, in canonical form"""
+    del V.LAST_PROGRAMS[:]
+    outs = Value.materialize(values)
+    progs = list(V.LAST_PROGRAMS)
+    cap, m, be = V.limits()["outputs"], len(values[0]), V._backend(D)
+    groups = [outs[i:i + cap] for i in range(0, len(outs), cap)]
+    assert len(groups) == len(progs)
+
+    def relaunch():
+        for prog, group in zip(progs, groups):
+            V._launch(prog, [(t, 0) for t in group], V.FORM_CANONICAL, m, be)
+
+    return outs, relaunch, len(progs)
+
+
+def integer_cases(D, n, args, out):
+    L = D.L
+    stream_rate = args.stream_gbs * 1e9 if args.stream_gbs else None
+    # (d) compact u64 -> four 16-bit limbs
+    cells = random_cells(D, n, 31, True)
+    limbs, launch_fn, launches = compiled_many(D, Value.from_u64(D, cells).limbs(16, 4))
+    work = [D.empty(n) for _ in range(4)]
+
+    def composed_fn():
+        with torch.cuda.stream(D.tstream):
+            parts = [(cells >> (16 * j)) & 0xFFFF for j in range(4)]
+        for part, w in zip(parts, work):
+            check(L.h2_dev_widen_u64(part.data_ptr(), n, w.data_ptr(), D.stream), "h2_dev_widen_u64")
+        return work
+
+    same = all(np.array_equal(D.download(x), D.download(y)) for x, y in zip(limbs, composed_fn()))
+    spin(D, launch_fn)
+    fused_ms, composed_ms = [], []
+    for _ in range(args.reps):
+        fused_ms.append(timed(D, launch_fn))
+        composed_ms.append(timed(D, composed_fn))
+    f, c = stats(fused_ms), stats(composed_ms)
+    fused_bytes = (8 + 4 * 32) * n
+    composed_bytes = 4 * (8 + 8 + 8 + 8) * n + 4 * (8 + 32) * n            # shift: 8 in 8 out; mask: 8 in 8 out; widen: 8 in 32 out
+    out["d_compact_limbs"] = {"equal_results": bool(same), "fused": f, "composed": c, "launches_per_call": launches, "products_per_row": 0,
+                              "fused_bytes_per_s": fused_bytes / (f["median_ms"] * 1e-3), "composed_bytes_per_s": composed_bytes / (c["median_ms"] * 1e-3),
+                              "composed_over_fused": c["median_ms"] / f["median_ms"]}
+    # (e) a Montgomery column -> 32 8-bit limbs
+    cells = D.empty(n)
+    check(L.h2_dev_random_fr((41).to_bytes(32, "little"), n, cells.data_ptr(), D.stream), "h2_dev_random_fr")
+    limbs, launch_fn, launches = compiled_many(D, Value.from_limbs(D, cells, montgomery=True).limbs(8, 32))
+    h = min(args.python_height, n)
+    t0 = time.perf_counter()
+    ints = [v * V._R_INV % V.R_MOD for v in V.limbs_to_ints(D.download(cells[:h]))]
+    python = [D.upload(np.array([[(v >> (8 * j)) & 0xFF, 0, 0, 0] for v in ints], dtype=np.uint64), widen=False) for j in range(32)]
+    D.sync()
+    python_s = time.perf_counter() - t0
+    same = all(np.array_equal(D.download(x[:h]), D.download(y)) for x, y in zip(limbs, python))
+    spin(D, launch_fn)
+    e = stats([timed(D, launch_fn) for _ in range(args.reps)])
+    moved = launches * (32 + V.limits()["outputs"] * 32) * n
+    out["e_montgomery_limbs"] = {"equal_results": bool(same), "fused": e, "launches_per_call": launches, "products_per_row": launches,
+                                 "fused_bytes_per_s": moved / (e["median_ms"] * 1e-3),
+                                 "fused_products_per_s": launches * n / (e["median_ms"] * 1e-3),
+                                 "python_height": h, "python_seconds": python_s,
+                                 "per_row_speedup": (python_s / h) / (e["median_ms"] * 1e-3 / n)}
+    if stream_rate:
+        out["stream_bytes_per_s"] = stream_rate
+        for name in ("d_compact_limbs", "e_montgomery_limbs"):
+            out[name]["fused_share_of_stream"] = out[name]["fused_bytes_per_s"] / stream_rate
+
+
 def multiplier_rate(D, n, reps):
     """field products per second of the evaluator's multiplier site: 120 dependent squarings per row, 64 bytes per row"""
     y = Value.from_limbs(D, random_cells(D, n, 99, False), montgomery=True)
@@ -116,6 +191,8 @@ def main():
     ap.add_argument("k", type=int)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--python-height", type=int, default=1 << 17)
+    ap.add_argument("--integers", action="store_true", help="cases (d) and (e) instead of (c)")
+    ap.add_argument("--stream-gbs", type=float, default=0.0, help="tools/membench's streaming rate on this device, GB/s")
     args = ap.parse_args()
     D = prover.Device()
     n = 1 << args.k
@@ -150,6 +227,11 @@ def main():
                      "fused_products_per_s": products * n / (f["median_ms"] * 1e-3),
                      "fused_share_of_multiplier": products * n / (f["median_ms"] * 1e-3) / rate,
                      "composed_over_fused": c["median_ms"] / f["median_ms"]}
+    if args.integers:
+        integer_cases(D, n, args, out)
+        out["e_montgomery_limbs"]["fused_share_of_multiplier"] = out["e_montgomery_limbs"]["fused_products_per_s"] / rate
+        print(json.dumps(out))
+        return
     # (c) the shuffle's running product at full height
     height = n - 7
 
