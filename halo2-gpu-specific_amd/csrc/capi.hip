@@ -1841,9 +1841,13 @@ int h2_evalh_prepare(const h2_evalh_desc* desc, h2_evalh_info* info) {
     return guarded([&] {
         current_ctx();  // the device of this thread is initialised
         int cached = 0;
-        EvalhPlanRef held = evalh_plan_get(desc, &cached);
+        std::string why;
+        EvalhPlanRef held = evalh_plan_get(desc, &cached, &why);
         const EvalhPlan* plan = held.get();
-        if (!plan) return bad("h2_evalh_prepare: no generated kernels for this program (H2_EVALH_JIT=0, hipRTC unavailable or a rejected program: see stderr)");
+        // (an error, not an info without stages: a caller that prepares at keygen time wants to hear that this circuit will run on the
+        //  interpreter kernels, and why -- evaluate_h itself goes on, with one warning)
+        if (!plan && !why.empty()) return bad(("h2_evalh_prepare: no generated kernels for this program: " + why).c_str());
+        if (!plan) return bad("h2_evalh_prepare: no generated kernels for this program (H2_EVALH_JIT=0)");
         if (info) {
             evalh_plan_info(plan, info);
             info->from_cache = (uint32_t)cached;

@@ -56,7 +56,7 @@ public:
     explicit operator bool() const { return p_ != nullptr; }
     const EvalhPlan* get() const { return p_; }
 };
-EvalhPlanRef evalh_plan_get(const h2_evalh_desc* d, int* cached);
+EvalhPlanRef evalh_plan_get(const h2_evalh_desc* d, int* cached, std::string* why = nullptr);
 void evalh_plan_info(const EvalhPlan* plan, h2_evalh_info* info);
 uint64_t evalh_plan_evictions();
 void evalh_gen_info(const evgen::Generated& g, h2_evalh_info* info);

@@ -58,7 +58,7 @@ namespace evgen {
 
 namespace {
 
-constexpr const char* GENERATOR_VERSION = "h2-evalh-gen 5.14";
+constexpr const char* GENERATOR_VERSION = "h2-evalh-gen 5.15";
 
 [[noreturn]] void fail(const std::string& what) { throw std::runtime_error("evaluate_h generator: " + what); }
 
@@ -1016,7 +1016,7 @@ Generated generate(const h2_evalh_desc* d, const Options& opt) {
     emitters.emplace_back(B, opt);
     auto stage_full = [&](const StageEmitter& e) {
         if (opt.stage_products && e.products >= opt.stage_products) return true;
-        return e.args_bytes() > 3072 || e.cols.size() >= opt.max_cols;
+        return e.args_bytes() > ARGS_CUT_BYTES;
     };
     for (const Group& g : groups) {
         emitters.back().begin_group(g.f);
@@ -1035,7 +1035,7 @@ Generated generate(const h2_evalh_desc* d, const Options& opt) {
     out.stages.resize(emitters.size());
     std::vector<bool> seen(B.cols.size(), false);
     for (size_t s = 0; s < emitters.size(); s++) {
-        if (emitters[s].args_bytes() > 4096) fail("a single term reads more columns than one kernel's arguments hold");
+        if (emitters[s].args_bytes() > ARGS_MAX_BYTES) fail("a single term reads more columns than one kernel's arguments hold");
         emitters[s].finish(s > 0, (uint32_t)s, (uint32_t)emitters.size(), out.stages[s]);
         out.products_per_row += out.stages[s].products;
         out.fused_pairs_per_row += out.stages[s].fused_pairs;
@@ -1053,7 +1053,7 @@ void program_hash(const h2_evalh_desc* d, const Options& opt, uint8_t out[32]) {
     h.update(GENERATOR_VERSION, strlen(GENERATOR_VERSION));
     h.update(h2_embed_field_hpp, strlen(h2_embed_field_hpp));
     h.update(h2_embed_fp_mul_gen_hpp, strlen(h2_embed_fp_mul_gen_hpp));
-    const uint32_t o[] = {opt.group, opt.max_ahead, opt.gap, opt.inline_muls, opt.stage_products, opt.max_cols, opt.max_regs,
+    const uint32_t o[] = {opt.group, opt.max_ahead, opt.gap, opt.inline_muls, opt.stage_products, opt.max_regs,
                           (uint32_t)opt.factor, opt.waves, opt.live_budget, opt.lds_args, (uint32_t)opt.mul2, opt.min_group};
     h.update(o, sizeof o);
     h.u32(d->blinding_factors);

@@ -47,6 +47,8 @@ struct ScalarRef {
 //   offset 48  Fr sc[n_scalars]  (32 B each, at least one)
 //   then       const Fr* cols[n_cols]  (at least one)
 constexpr size_t ARGS_FIXED_BYTES = 48;
+constexpr size_t ARGS_MAX_BYTES = 4096;   // what one kernel launch takes by value: a single term that needs more is refused
+constexpr size_t ARGS_CUT_BYTES = 3072;   // a stage whose block has passed this takes no further term (the next one may be wide)
 constexpr const char* KERNEL_NAME = "h2_evalh_gen";
 
 struct Stage {
@@ -84,7 +86,6 @@ struct Options {
     uint32_t inline_muls = 40; // programs with at most this many products inline the multiplier (mini-PLONK's 29: 7.35 -> 7.11 ms;
                                // the wide circuit's 120 fully inlined: 0.5 MB of code for no gain)
     uint32_t stage_products = 0;   // cut the program into stages of about this many products (0 = as few stages as fit)
-    uint32_t max_cols = 440;   // column pointers per stage (kernel arguments are limited to 4 KiB)
     uint32_t waves = 0;        // ask the compiler for at least this many waves per SIMD (amdgpu_waves_per_eu; 0 = its own choice)
     uint32_t max_regs = 256;   // a stage compiled to more registers than this (or to scratch) is cut in two and rebuilt
     uint32_t mul2 = 96;        // a b + c d under ONE reduction (fp_mul2: 3/4 of the multiply-adds of two products) where both

@@ -191,7 +191,9 @@ int evalh_interpret(DeviceCtx* ctx, const h2_evalh_desc* d, Fr* d_values, size_t
                   ((size_t)d->n_fixed + d->n_advice + d->n_instance + d->n_perm_sets + 2 * (size_t)d->n_perm_columns + n_lookup_z +
                    d->n_lookups + d->n_shuffles) * 8 + 64 * 16;
     // ---- work space: interpreter intermediates + lookup / shuffle compressed expressions
-    const unsigned blocks = 256 * 8, threads = 256;
+    // (one lane per row up to 2048 workgroups, a grid-stride loop beyond: k_evalh_expr's intermediates are [calculation][lane], so
+    //  the work space follows the rows of the call -- 16 rows of a 1650-calculation program used to borrow 26 GiB)
+    const unsigned threads = 256, blocks = (unsigned)std::max<size_t>(1, std::min<size_t>(256 * 8, (rows + threads - 1) / threads));
     const size_t nthreads = (size_t)blocks * threads;
     size_t inter_bytes = (size_t)(d->n_calculations ? d->n_calculations : 1) * nthreads * sizeof(Fr);
     size_t lk_bytes = n_lookup_calcs ? n_lookup_calcs * size * sizeof(Fr) : 256;

@@ -50,6 +50,7 @@ std::map<PlanKey, std::unique_ptr<EvalhPlan>> g_plans;   // a null entry: genera
 std::set<PlanKey> g_building;
 std::condition_variable g_plan_cv;
 std::map<PlanKey, std::chrono::steady_clock::time_point> g_failed_at;   // when a null entry was made: retried after a minute
+std::map<PlanKey, std::string> g_failed_why;                              // ... and what the generator or the compiler said
 constexpr int FAILED_RETRY_SECONDS = 60;
 std::atomic<uint64_t> g_generated_launches{0};
 std::atomic<uint64_t> g_plan_evictions{0};
@@ -79,6 +80,7 @@ void evict_plans(const PlanKey& keep, std::vector<std::unique_ptr<EvalhPlan>>& g
         if (victim == g_plans.end()) return;   // everything else is in use: over the bound until a holder lets go
         if (victim->second) gone.push_back(std::move(victim->second));
         g_failed_at.erase(victim->first);
+        g_failed_why.erase(victim->first);
         g_plans.erase(victim);
         g_plan_evictions.fetch_add(1);
     }
@@ -124,7 +126,7 @@ struct FastHash {
 
 PlanKey plan_key(const h2_evalh_desc* d, const evgen::Options& opt, int device) {
     FastHash h;
-    const uint32_t o[] = {opt.group, opt.max_ahead, opt.gap, opt.inline_muls, opt.stage_products, opt.max_cols, opt.max_regs,
+    const uint32_t o[] = {opt.group, opt.max_ahead, opt.gap, opt.inline_muls, opt.stage_products, opt.max_regs,
                           (uint32_t)opt.factor, opt.waves, opt.live_budget, opt.lds_args, (uint32_t)opt.mul2, opt.min_group, d->blinding_factors, d->chunk_len, d->n_fixed, d->n_advice,
                           d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups, d->n_shuffles};
     h.bytes(o, sizeof o);
@@ -155,7 +157,7 @@ void evalh_plan_release(const EvalhPlan* plan) {
 
 uint64_t evalh_plan_evictions() { return g_plan_evictions.load(); }
 
-EvalhPlanRef evalh_plan_get(const h2_evalh_desc* d, int* cached) {
+EvalhPlanRef evalh_plan_get(const h2_evalh_desc* d, int* cached, std::string* why) {
     if (cached) *cached = 0;
     if (!generation_enabled()) return EvalhPlanRef();
     int device = 0;
@@ -174,9 +176,11 @@ EvalhPlanRef evalh_plan_get(const h2_evalh_desc* d, int* cached) {
                 auto f = g_failed_at.find(key);
                 if (f != g_failed_at.end() && std::chrono::steady_clock::now() - f->second > std::chrono::seconds(FAILED_RETRY_SECONDS)) {
                     g_failed_at.erase(f);
+                    g_failed_why.erase(key);
                     g_plans.erase(it);
                     continue;
                 }
+                if (why) *why = g_failed_why[key];
             }
             if (cached) *cached = 1;
             if (const EvalhPlan* hit = it->second.get()) {
@@ -200,6 +204,7 @@ EvalhPlanRef evalh_plan_get(const h2_evalh_desc* d, int* cached) {
         }
     } done{key, g};
     std::unique_ptr<EvalhPlan> plan;
+    std::string failure;
     try {
         plan.reset(new EvalhPlan);
         plan->gen = evgen::compile(d, opt);
@@ -220,10 +225,12 @@ EvalhPlanRef evalh_plan_get(const h2_evalh_desc* d, int* cached) {
         if (cached) *cached = plan->from_cache;
     } catch (const std::exception& e) {
         fprintf(stderr, "libhalo2_hip: evaluate_h runs on the interpreter kernels for this program: %s\n", e.what());
+        failure = e.what();
         plan.reset();
     } catch (const HipError& e) {
         fprintf(stderr, "libhalo2_hip: evaluate_h runs on the interpreter kernels for this program: HIP error %d loading the generated code (%s)\n",
                 (int)e.code, e.expr);
+        failure = std::string("HIP error loading the generated code (") + e.expr + ")";
         plan.reset();
     }
     g.lock();
@@ -233,6 +240,8 @@ EvalhPlanRef evalh_plan_get(const h2_evalh_desc* d, int* cached) {
         out->users = 1;
     } else {
         g_failed_at[key] = std::chrono::steady_clock::now();
+        g_failed_why[key] = failure;
+        if (why) *why = failure;
     }
     g_plans[key] = std::move(plan);
     std::vector<std::unique_ptr<EvalhPlan>> gone;
@@ -327,7 +336,7 @@ void evalh_plan_launch(DeviceCtx* ctx, const EvalhPlan* plan, const h2_evalh_des
     const unsigned blocks = (unsigned)std::min<size_t>((rows + 255) / 256, 0x7fffffffu);
     for (size_t s = 0; s < plan->gen.stages.size(); s++) {
         const evgen::Stage& st = plan->gen.stages[s];
-        alignas(16) unsigned char buf[4096];
+        alignas(16) unsigned char buf[evgen::ARGS_MAX_BYTES];
         const size_t bytes = evalh_fill_stage_args(st, d, d_values, tw_lo, tw_hi, row_begin, row_end, buf, sizeof buf);
         static const bool debug = getenv("H2_JIT_DEBUG") != nullptr;
         if (debug)

@@ -1,6 +1,6 @@
-"""The evaluate_h generator fuzzed WITHOUT a GPU: for random circuits (tools/prover_fuzz.random_case), the product circuits
-and random Evaluator programs (tests/evalh_cases.random_case), the source libhalo2_hip.so generates is compiled for the host
-with g++ and run on random columns against the CPU oracle's evaluate_h, under random generator options (grouping, fold order,
+"""The evaluate_h generator fuzzed WITHOUT a GPU: for random circuits (tools/prover_fuzz.random_case), the product circuits,
+random Evaluator programs (tests/evalh_cases.random_case) and three programs shaped by the size of their argument blocks
+(tests/evalh_shape_cases: args-over, lds-auto-over, wide), the source libhalo2_hip.so generates is compiled for the host with g++ and run on random columns against the CPU oracle's evaluate_h, under random generator options (grouping, fold order,
 stage size, fp_mul2 pairing, live budget, gaps).  The harness is tests/test_evalh_host_exec.py's.
 usage: python tools/gen_host_fuzz.py [seconds] [seed]"""
 import os
@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 
 import evalh_cases  # noqa: E402
+import evalh_shape_cases  # noqa: E402
 import prover_fuzz  # noqa: E402
 import test_evalh_host_exec as hx  # noqa: E402
 from h2util import Oracle, fr_mont  # noqa: E402
@@ -89,6 +90,8 @@ def main():
     oracle = Oracle.get()
     fixed_corpus = [("mini-PLONK", circuits.mini_plonk(), 4), ("wide-2", circuits.wide(2), 4), ("wide-6", circuits.wide(6), 3),
                     ("range-check", circuits.range_check(), 5)]
+    # (shapes that no random program reaches: hundreds of vectors, stages cut by the argument block, arguments through LDS)
+    fixed_corpus += [("shaped-" + name, None, None) for name in ("args-over", "lds-auto-over", "wide")]
     t_end, cases, kinds = time.time() + budget, 0, {}
     with tempfile.TemporaryDirectory() as tmp:
         os.environ["H2_JIT_CACHE"] = os.path.join(tmp, "cache")
@@ -96,7 +99,7 @@ def main():
             pick = rnd.random()
             if cases < len(fixed_corpus):
                 name, cs, k = fixed_corpus[cases]
-                kw = circuit_case(cs, k, oracle, seed * 7919 + cases)
+                kw = circuit_case(cs, k, oracle, seed * 7919 + cases) if cs else evalh_shape_cases.build(name[7:], oracle)[0]
             elif pick < 0.6:
                 s = rnd.randrange(1 << 30)
                 cs, k, *_ = prover_fuzz.random_case(s, satisfiable=bool(s & 1), k=rnd.choice([3, 4, 5]))
