@@ -145,6 +145,11 @@ SYMBOLS = {
     "h2_values_limits": (ctypes.c_int, [_vp]),
     "h2_dev_values_eval": (ctypes.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp]),
     "h2_values_eval": (ctypes.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz]),
+    "h2_sort_limits": (ctypes.c_int, [_vp]),
+    "h2_sort_scratch_bytes": (_sz, [_sz, _sz]),
+    "h2_dev_sort_permutation": (ctypes.c_int, [_vp, _vp, _vp, _sz, _sz, _vp, _u32, _vp, _vp, _sz, _vp]),
+    "h2_sort_permutation": (ctypes.c_int, [_vp, _vp, _vp, _sz, _sz, _vp, _u32, _vp]),
+    "h2_sort": (ctypes.c_int, [_vp, _sz]),
     "h2_check_scratch_bytes": (_sz, [_sz]),
     "h2_dev_check_nonzero_rows": (ctypes.c_int, [_vp, _sz, _vp, _vp, _vp]),
     "h2_dev_check_gates": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _sz, _vp]),

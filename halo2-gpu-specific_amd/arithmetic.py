@@ -95,6 +95,16 @@ def gpu_unmont(a):
     return a
 
 
+def gpu_sort(a, log_n):
+    """arithmetic.rs:167-216 -- in place on `a` (2^log_n Fr, Montgomery residues): ascending by the integer in [0, r) each
+    stands for.  The reference runs a bitonic network between an unmont and a mont; here it is the radix sort of csrc/sort.hip,
+    which reads the residues as they are."""
+    a = _fr(a)
+    assert a.shape[0] == 1 << log_n
+    check(lib().h2_sort(_p(a), len(a)), "h2_sort")
+    return a
+
+
 def coeff_to_extended(coeffs, k, extended_k, g_coset, g_coset_inv, extended_omega):
     """poly/domain.rs:270-287"""
     coeffs = _fr(coeffs)

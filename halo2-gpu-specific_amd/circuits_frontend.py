@@ -14,6 +14,7 @@
   SelectorGates      simple, complex and unused selectors enabled in bulk, strided (no .rs text)
   ShuffleGatesValues ShuffleGates with its witness computed on the device by Values (values.py), at any height
   LimbDecomposition  p = a b mod 2^(bits words) split into limbs that a range table is looked up for: integer Values
+  SortedAccessLog    an access log and the same rows ordered by (address, time) by Value.sort_by: a memory-consistency table
 
 Where an example assigns cell by cell in a loop, the class assigns the loop's range at once; the calls are otherwise the
 example's, in its order."""
@@ -650,3 +651,100 @@ class LimbDecomposition(Circuit):
 
         layouter.assign_region("limbs", body)
         layouter.assign_table("range table", lambda table: table.assign_cell(config.table, 0, np.arange(1 << self.bits, dtype=np.uint64)))
+
+
+class SortedAccessLog(Circuit):
+    """A memory-consistency table: a seeded log of `height` accesses in program order -- columns (a, t, v, w): an address below
+    2^addr_bits, the time t = row + 1, the value, and w = 1 for a write; a read returns what a replay of the log finds at its
+    address (0 before the first write) -- next to the same rows ordered by (address, time), (A, T, V, W), which exist only as
+    `Value.sort_by([a, t], [a, t, v, w])` (values.py; csrc/sort.hip): the order is computed where the Values live.  With
+    delta = A' - A on the rows 0 .. height - 2 of the sorted side the remaining advice is Values too:
+        inv = delta.invert(),  s = 1 - delta inv  (1 where the address stays),  d = select(s, T' - T - 1, delta - 1).
+    Relations (q on the `height` rows, q_adj on the first height - 1):
+        shuffle   (q a, q t, q v, q w)  <->  (q A, q T, q V, q W)           the sorted side holds the log's rows (t >= 1 keeps
+                                                                           an enabled row apart from the padding)
+        gates     q_adj delta s = 0;  q_adj (s - 1 + delta inv) = 0         s = [delta = 0]
+                  q_adj s (1 - W') (V' - V) = 0                             a read returns what the address held
+                  q_adj (d - s (T' - T - 1) - (1 - s) (delta - 1)) = 0      d is the gap in time, or in address, less one
+        lookup    d in 0 .. 2^b - 1, 2^b >= max(height, 2^addr_bits)        the gap is positive: the order is STRICT in
+                                                                           (address, time)
+    s has a column of its own, which keeps the gates at degree 4 (q_adj s (1 - W') (V' - V)); the shuffle is 2 + 2 and the
+    lookup 2 + 1 + 1: the constraint system's degree is 4, below the wide circuit's 5.  Keygen passes unknowns: there is no
+    branch on a witness flag.  `columns`: [a, t, v, w, A, T, V, W, inv, s, d] as Values instead of the seeded ones (the last
+    three of height - 1 elements)."""
+    planner = V1
+
+    def __init__(self, k, addr_bits=4, height=None, seed=0x534F5254, device=None, columns=None):
+        self.k, self.addr_bits, self.seed, self.device = k, addr_bits, seed, device
+        self.height = 1 << (k - 1) if height is None else height
+        self.table_bits = max(addr_bits, (self.height - 1).bit_length())
+        if not (1 <= addr_bits <= 32 and 2 <= self.height and (1 << self.table_bits) <= (1 << k) - 6):
+            raise ValueError("SortedAccessLog: height >= 2, and a table of max(height, 2^addr_bits) rows must fit the usable rows")
+        self._columns = columns
+
+    def without_witnesses(self):
+        H = self.height
+        return SortedAccessLog(self.k, self.addr_bits, H, self.seed, self.device,
+                               [Value.unknown(H)] * 8 + [Value.unknown(H - 1)] * 3)
+
+    def configure(self, cs):
+        log = [cs.advice_column() for _ in range(4)]
+        ordered = [cs.advice_column() for _ in range(4)]
+        inv, s, d = cs.advice_column(), cs.advice_column(), cs.advice_column()
+        q, q_adj = cs.fixed_column(), cs.fixed_column()
+        table = cs.lookup_table_column()
+        f_q, f_adj = cs.query_fixed(q), cs.query_fixed(q_adj)
+        cs.shuffle("the sorted side holds the log's rows",
+                   [(f_q * cs.query_advice(x), f_q * cs.query_advice(y)) for x, y in zip(log, ordered)])
+        A, T, V = (cs.query_advice(c) for c in ordered[:3])
+        A1, T1, V1_, W1 = (cs.query_advice(c, 1) for c in ordered)
+        delta, one = A1 - A, Constant(1)
+        q_inv, q_s, q_d = cs.query_advice(inv), cs.query_advice(s), cs.query_advice(d)
+        cs.create_gate("the address stays or s is 0", [f_adj * delta * q_s])
+        cs.create_gate("s is 1 where the address stays", [f_adj * (q_s - one + delta * q_inv)])
+        cs.create_gate("a read returns the value before it", [f_adj * q_s * (one - W1) * (V1_ - V)])
+        cs.create_gate("d is the gap less one", [f_adj * (q_d - q_s * (T1 - T - one) - (one - q_s) * (delta - one))])
+        cs.lookup("the gap is positive", [(q_d, cs.query_fixed(table))])
+        return _Config(log=log, ordered=ordered, inv=inv, s=s, d=d, q=q, q_adj=q_adj, table=table)
+
+    def witness_inputs(self):
+        """the seeded log as u64 cells: (a, t, v, w), the reads' values by a plain replay"""
+        rng = np.random.Generator(np.random.PCG64(self.seed))
+        H = self.height
+        a = rng.integers(0, 1 << self.addr_bits, size=H, dtype=np.uint64)
+        w = rng.integers(0, 2, size=H, dtype=np.uint64)
+        v = rng.integers(0, 1 << 64, size=H, dtype=np.uint64)
+        memory = {}
+        for row in range(H):
+            if w[row]:
+                memory[int(a[row])] = v[row]
+            else:
+                v[row] = memory.get(int(a[row]), 0)
+        return a, np.arange(1, H + 1, dtype=np.uint64), v, w
+
+    def columns(self):
+        """[a, t, v, w, A, T, V, W, inv, s, d] as Values, built once"""
+        if self._columns is None:
+            log = [Value.from_u64(self.device, x) for x in self.witness_inputs()]
+            A, T, V, W = Value.sort_by(log[:2], log, bits=[self.addr_bits, self.height.bit_length()])
+            delta = A[1:] - A[:-1]
+            inv = delta.invert()
+            s = 1 - delta * inv
+            d = Value.select(s, T[1:] - T[:-1] - 1, delta - 1)
+            self._columns = log + [A, T, V, W, inv, s, d]
+        return self._columns
+
+    def synthesize(self, config, layouter):
+        H = self.height
+        columns = self.columns()
+
+        def body(region):
+            region.assign_fixed(config.q, 0, 1, count=H)
+            region.assign_fixed(config.q_adj, 0, 1, count=H - 1)
+            for column, values in zip(config.log + config.ordered, columns[:8]):
+                region.assign_advice(column, 0, values, count=H)
+            for column, values in zip([config.inv, config.s, config.d], columns[8:]):
+                region.assign_advice(column, 0, values, count=H - 1)
+
+        layouter.assign_region("access log", body)
+        layouter.assign_table("gap table", lambda table: table.assign_cell(config.table, 0, np.arange(1 << self.table_bits, dtype=np.uint64)))

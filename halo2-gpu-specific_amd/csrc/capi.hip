@@ -25,6 +25,7 @@
 #include "rangecheck.hpp"
 #include "resident.hpp"
 #include "scan.hpp"
+#include "sort.hpp"
 #include "srscheck.hpp"
 #include "values.hpp"
 
@@ -1737,6 +1738,64 @@ int h2_values_eval(const h2_values_leaf* leaves, size_t num_leaves, const uint64
         return bad((std::string("h2_values_eval: ") + what).c_str());
     values_eval_host(P, m);
     return H2_OK;
+}
+
+// ------------------------------------------------------------------ sorting field elements (sort.hip)
+int h2_sort_limits(h2_sort_caps* out) {
+    if (!out) return bad("h2_sort_limits: null argument");
+    *out = h2_sort_caps{SORT_TILE, SORT_MAX_KEYS, H2_SORT_STATUS_WORDS, 0};
+    return H2_OK;
+}
+
+size_t h2_sort_scratch_bytes(size_t n, size_t num_keys) {
+    const uint32_t forms[SORT_MAX_KEYS] = {}, bits[SORT_MAX_KEYS] = {};
+    SortPlan plan;
+    return sort_plan(forms, bits, num_keys, n, &plan) ? 0 : plan.total;
+}
+
+int h2_dev_sort_permutation(const void* const* d_keys, const uint32_t* forms, const uint32_t* bits, size_t num_keys, size_t n,
+                            void* d_perm, uint32_t perm_width, uint32_t* d_status, void* d_scratch, size_t scratch_bytes,
+                            void* stream) {
+    SortPlan plan;
+    if (const char* what = sort_validate(d_keys, forms, bits, num_keys, n, d_perm, perm_width, d_status, true, d_scratch,
+                                         scratch_bytes, &plan))
+        return bad((std::string("h2_dev_sort_permutation: ") + what).c_str());
+    return guarded([&] {
+        return sort_permutation_launch(plan, d_keys, d_perm, perm_width, d_status, d_scratch, pick_stream(current_ctx(), stream));
+    });
+}
+
+int h2_sort_permutation(const void* const* keys, const uint32_t* forms, const uint32_t* bits, size_t num_keys, size_t n,
+                        void* perm, uint32_t perm_width, uint32_t* status) {
+    SortPlan plan;
+    if (const char* what = sort_validate(keys, forms, bits, num_keys, n, perm, perm_width, status, false, nullptr, 0, &plan))
+        return bad((std::string("h2_sort_permutation: ") + what).c_str());
+    return guarded([&] {
+        sort_permutation_host(plan, keys, perm, perm_width, status);
+        return (int)H2_OK;
+    });
+}
+
+// the reference's gpu_sort (arithmetic.rs:167-216): Montgomery residues, in place, ascending by canonical integer
+int h2_sort(uint64_t* values, size_t n) {
+    if (n && !values) return bad("h2_sort: null argument");
+    if (n >> 32) return bad("h2_sort: n is 2^32 or more");
+    return guarded([&] {
+        if (n < 2) return (int)H2_OK;
+        const uint32_t form = H2_ASSIGNED_FORM_MONTGOMERY, bits = 0;
+        SortPlan plan;
+        if (const char* what = sort_plan(&form, &bits, 1, n, &plan)) return bad((std::string("h2_sort: ") + what).c_str());
+        HostCall call;
+        HostResult res(values, n, {values});
+        const void* d = call.upload(call.ctx->buf_a, values, n * sizeof(Fr));
+        // the scratch, then the permutation and the status words behind it
+        const size_t perm_at = plan.total, status_at = perm_at + ((n * 4 + 255) & ~(size_t)255);
+        char* work = (char*)call.ctx->buf_b.get(status_at + 256);
+        Fr* out = (Fr*)call.ctx->buf_c.get(n * sizeof(Fr));
+        H2_TRY(sort_permutation_launch(plan, &d, work + perm_at, 4, (uint32_t*)(work + status_at), work, call.stream));
+        H2_TRY(sort_gather_launch(d, (const uint32_t*)(work + perm_at), out, n, call.stream));
+        return res.write(out, call.stream);
+    });
 }
 
 // ------------------------------------------------------------------ rational (Assigned) cells

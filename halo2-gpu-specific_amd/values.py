@@ -18,6 +18,10 @@ assignment asks for the elements.  Then the compiler below turns the expression 
                           k nested levels of division cost k + 1 evaluator launches and k inversions (per distinct length,
                           and per `outputs` denominators of one length)
   scans, concat, take     their operands are materialised first; their results are leaves
+  argsort, sort, sort_by  the keys are materialised first (a whole leaf goes as it stands, in any form); ONE stable radix sort
+                          (csrc/sort.hip, h2_dev_sort_permutation; DESIGN.md 3b, "Sorting a witness") orders up to four key
+                          columns as integers in [0, r) where they live; the permutation is a compact leaf that `take`
+                          gathers by without a bounds check
   integers                bits / >> / low / bit / limbs, & | ^ and lt / le / gt / ge read a cell as the integer in [0, r).
                           Inside a program a value is a field element or an integer (`_Node.vkind`); the compiler inserts
                           to_int / to_field where an operand's kind is not what the op takes, hash-consing shares them (one
@@ -25,7 +29,7 @@ assignment asks for the elements.  Then the compiler below turns the expression 
                           see kinds: every Value reads back as field elements
 
 Device work is allocated and launched under the device's compute stream, as check.py does, so that an assignment's flush
-(DeviceColumns._flush) sees finished values.  `device.values_launches` / `device.values_inversions` count the calls.
+(DeviceColumns._flush) sees finished values.  `device.values_launches` / `device.values_inversions` / `device.values_sorts` count the calls.
 """
 import numpy as np
 
@@ -47,6 +51,8 @@ VALUES_OP = np.dtype([("op", "<u4"), ("dst", "<u4"), ("a", "<u4"), ("b", "<u4"),
 VALUES_OUTPUT = np.dtype([("ptr", "<u8"), ("first", "<u8"), ("slot", "<u4"), ("form", "<u4")])
 VALUES_CAPS = np.dtype([("leaves", "<u4"), ("ops", "<u4"), ("constants", "<u4"), ("outputs", "<u4"), ("slots", "<u4"),
                         ("blocks", "<u4"), ("threads", "<u4"), ("reserved", "<u4")])
+SORT_CAPS = np.dtype([("tile", "<u4"), ("max_keys", "<u4"), ("status_words", "<u4"), ("reserved", "<u4")])   # h2_sort_caps
+SORT_OK, SORT_OUT_OF_RANGE, SORT_STATUS_WORDS = 0, 1, 4                                  # H2_SORT_*
 _MASK64 = (1 << 64) - 1
 _R = (1 << 256) % R_MOD
 _R_INV = pow(_R, -1, R_MOD)
@@ -61,6 +67,13 @@ def limits():
         check(lib().h2_values_limits(caps.ctypes.data), "h2_values_limits")
         _LIMITS = {name: int(caps[0][name]) for name in VALUES_CAPS.names if name != "reserved"}
     return _LIMITS
+
+
+def sort_limits():
+    """h2_sort_limits as a dict: the rows a workgroup of a sorting pass ranks, the most key columns, the status words"""
+    caps = np.zeros(1, dtype=SORT_CAPS)
+    check(lib().h2_sort_limits(caps.ctypes.data), "h2_sort_limits")
+    return {name: int(caps[0][name]) for name in SORT_CAPS.names if name != "reserved"}
 
 
 def ints_to_limbs(values):
@@ -78,7 +91,7 @@ class _HostBackend:
     device = None
 
     def __init__(self):
-        self.values_launches = self.values_inversions = 0
+        self.values_launches = self.values_inversions = self.values_sorts = 0
 
     def count(self, launches=0, inversions=0):
         self.values_launches += launches
@@ -128,6 +141,17 @@ class _HostBackend:
     def download(self, a):
         return a
 
+    def sort(self, datas, forms, bits, n):
+        """h2_sort_permutation -> (the permutation as compact cells, the status words)"""
+        self.values_sorts += 1
+        perm, status = np.zeros(n, dtype=np.uint64), np.zeros(SORT_STATUS_WORDS, dtype=np.uint32)
+        datas = [np.ascontiguousarray(d) for d in datas]
+        keys = np.array([d.ctypes.data for d in datas], dtype=np.uint64)
+        forms, bits = np.array(forms, dtype=np.uint32), np.array(bits, dtype=np.uint32)
+        check(lib().h2_sort_permutation(keys.ctypes.data, forms.ctypes.data, bits.ctypes.data, len(datas), n, perm.ctypes.data, 8,
+                                        status.ctypes.data), "h2_sort_permutation")
+        return perm, [int(w) for w in status]
+
     def publish(self):
         pass
 
@@ -140,6 +164,7 @@ class _DeviceBackend:
         self.device = self.D = device
         device.__dict__.setdefault("values_launches", 0)
         device.__dict__.setdefault("values_inversions", 0)
+        device.__dict__.setdefault("values_sorts", 0)
 
     def count(self, launches=0, inversions=0):
         self.D.values_launches += launches
@@ -200,6 +225,26 @@ class _DeviceBackend:
     def download(self, t):
         return self.D.download(t)
 
+    def sort(self, datas, forms, bits, n):
+        """h2_dev_sort_permutation on the compute stream, its scratch from Device.scratch (one sort at a time: the stream
+        orders them) -> (the permutation as compact cells, the status words).  The 16 bytes of status are the only thing that
+        comes back, but reading them waits for the compute stream: every sort inside a `synthesize` body is a host
+        synchronisation, as the bounds check of a `take` by a Value is"""
+        D, torch = self.D, self.D.torch
+        D.values_sorts += 1
+        need = D.L.h2_sort_scratch_bytes(n, len(datas))
+        scratch = D.scratch(need)
+        with torch.cuda.stream(D.tstream):
+            perm = torch.empty(n, dtype=torch.int64, device=D.dev)
+            status = torch.empty(SORT_STATUS_WORDS, dtype=torch.int32, device=D.dev)
+        keys = np.array([d.data_ptr() for d in datas], dtype=np.uint64)
+        forms, bits = np.array(forms, dtype=np.uint32), np.array(bits, dtype=np.uint32)
+        check(D.L.h2_dev_sort_permutation(keys.ctypes.data, forms.ctypes.data, bits.ctypes.data, len(datas), n, perm.data_ptr(), 8,
+                                          status.data_ptr(), scratch.data_ptr(), need, D.stream), "h2_dev_sort_permutation")
+        with torch.cuda.stream(D.tstream):
+            words = status.cpu().numpy().view(np.uint32)
+        return perm, [int(w) for w in words]
+
     def publish(self):
         """what was launched on the compute stream is ordered before whatever the caller's stream does next"""
         torch = self.D.torch
@@ -222,14 +267,15 @@ def _backend(device):
 # -- expressions -------------------------------------------------------------------------------------------------------------
 class _Buffer:
     """`length` field elements a leaf reads: a host array, a device tensor, or (data None) the result of `pending`"""
-    __slots__ = ("data", "form", "length", "pending", "ordered")
+    __slots__ = ("data", "form", "length", "pending", "ordered", "rows")
 
     def __init__(self, data, form, length, pending=None, ordered=False):
         self.data, self.form, self.length, self.pending, self.ordered = data, form, length, pending, ordered
+        self.rows = None    # an argsort's result: a permutation of this many rows -- a take of that many needs no bounds check
 
 
 class _Pending:
-    """what an unresolved buffer waits for: kind = inv | cumprod | cumsum | concat | take"""
+    """what an unresolved buffer waits for: kind = inv | cumprod | cumsum | concat | take | limbs | argsort"""
     __slots__ = ("kind", "args", "extra")
 
     def __init__(self, kind, args, extra=None):
@@ -526,6 +572,48 @@ class Value:
             return Value.unknown(len(indices))
         return self._deferred("take", len(indices), (self,), indices)
 
+    # -- ordering ------------------------------------------------------------------------------------------------------------
+    # On purpose neither a staticmethod nor a method with `self`: one plain function serves both call forms.  Looked up on the
+    # class, Value.argsort([a, b]) passes the list as `keys`; looked up on an instance, v.argsort(bits) binds v to `keys`.
+    def argsort(keys, bits=None):  # noqa: N805
+        """Value.argsort(keys, bits=None) or v.argsort(bits=None): the permutation that orders the rows by `keys` -- a Value,
+        or a list of up to `sort_limits()["max_keys"]` Values, the most significant first -- each cell read as the integer in
+        [0, r); equal rows keep their order.  The result is a Value of integers (compact cells): perm[i] = the row of the
+        i-th smallest.  `bits` (one number, or one per key; None = no promise) promises key < 2^bits and spares the passes
+        above it; a cell that breaks the promise raises ValueError on materialisation, naming key, row and value, and only
+        that cell reaches the host.  Deferred like `take`: the keys are materialised first (a whole leaf is passed as it
+        stands, in whatever form, with no launch -- a canonical leaf of unreduced cells is ordered by the cells as they
+        stand), then ONE h2_dev_sort_permutation (csrc/sort.hip; `device.values_sorts` counts them) orders them where they
+        live."""
+        keys = [keys] if isinstance(keys, Value) else list(keys)
+        if not keys:
+            raise ValueError("argsort takes at least one key")
+        count = keys[0].count
+        if any(k.count != count for k in keys):
+            raise ValueError("keys of different lengths do not sort together")
+        if isinstance(bits, (int, np.integer)) or bits is None:
+            bits = [bits] * len(keys)
+        bits = [0 if b is None else int(b) for b in bits]
+        if len(bits) != len(keys) or any(not 0 <= b <= 254 for b in bits):
+            raise ValueError("bits: one promise of 1 .. 254 bits (None or 0: no promise) per key")
+        if not all(k.known for k in keys):
+            return Value.unknown(count)
+        device = _common_device(keys)
+        if device is not None and any(k.device is None and k._node.kind != "const" for k in keys):
+            raise ValueError("a host value and a device value do not combine")
+        pending = _Pending("argsort", tuple(keys), bits)
+        return Value(device, count, _Node("leaf", count, buffer=_Buffer(None, FORM_COMPACT, count, pending)))
+
+    def sort(self, bits=None):
+        """the elements in ascending order of the integers in [0, r) they stand for: one argsort, one take"""
+        return self.take(self.argsort(bits))
+
+    @staticmethod
+    def sort_by(keys, payloads, bits=None):
+        """every payload permuted by the order of `keys` (see argsort): one argsort, one take per payload"""
+        perm = Value.argsort(keys, bits)
+        return [p.take(perm) for p in payloads]
+
     # -- materialisation -----------------------------------------------------------------------------------------------------
     @staticmethod
     def materialize(values, montgomery=False):
@@ -664,8 +752,14 @@ def _resolve_other(buf, be):
     elif kind == "limbs":
         _resolve_limbs(buf.pending, be)
         return
+    elif kind == "argsort":
+        data = _resolve_argsort(args, extra, be)
+        buf.rows = buf.length
     else:                                                           # take
-        if len(args) == 2:                                          # a Value of integers: checked where it lives
+        index = args[1]._node if len(args) == 2 else None
+        if index is not None and index.kind == "leaf" and args[1]._whole() and index.buffer.rows == args[0].count:
+            extra = be.data(index.buffer)                           # an argsort over as many rows: in range as it stands
+        elif index is not None:                                     # a Value of integers: checked where it lives
             index = _evaluate([args[1]], be, FORM_CANONICAL)[0]
             bad = be.rows_at_or_above(index, args[0].count) if args[1].count else []
             if len(bad):
@@ -679,6 +773,34 @@ def _resolve_other(buf, be):
         else:
             data = be.gather(_evaluate([args[0]], be, FORM_MONTGOMERY)[0], extra)
     buf.data, buf.ordered, buf.pending = data, True, None
+
+
+def _resolve_argsort(keys, bits, be):
+    """the keys as they stand where they are whole leaves, evaluated (together, canonical) where they are not; one sort"""
+    n = keys[0].count
+    datas, forms, rest = [None] * len(keys), [FORM_CANONICAL] * len(keys), []
+    for i, v in enumerate(keys):
+        node = v._node
+        if node.kind == "leaf" and v._whole():
+            datas[i], forms[i] = be.data(node.buffer), node.buffer.form
+        else:
+            rest.append(i)
+    for i, data in zip(rest, _evaluate([keys[i] for i in rest], be, FORM_CANONICAL)):
+        datas[i] = data
+    for i, form in enumerate(forms):
+        if form == FORM_COMPACT and bits[i] > 64:
+            bits = bits[:i] + [64] + bits[i + 1:]
+    if n == 0:
+        return be.upload(np.zeros(0, dtype=np.uint64))
+    perm, status = be.sort(datas, forms, bits, n)
+    if status[0] != SORT_OK:
+        row, key = status[1], status[2]
+        cell = np.ascontiguousarray(be.download(datas[key][row:row + 1])).view(np.uint64)
+        value = int(cell[0]) if forms[key] == FORM_COMPACT else limbs_to_ints(cell.reshape(1, 4))[0]
+        if forms[key] == FORM_MONTGOMERY:
+            value = value * _R_INV % R_MOD
+        raise ValueError("argsort: key %d at row %d is %d, which is not below 2^%d" % (key, row, value, bits[key] or 254))
+    return perm
 
 
 def _resolve_limbs(pending, be):

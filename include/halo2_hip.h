@@ -1076,6 +1076,50 @@ int h2_dev_values_eval(const h2_values_leaf *leaves, size_t num_leaves, const ui
 int h2_values_eval(const h2_values_leaf *leaves, size_t num_leaves, const uint64_t *constants, size_t num_constants,
                    const h2_values_op *ops, size_t num_ops, const h2_values_output *outputs, size_t num_outputs, size_t m);
 
+/* ---- sorting field elements (csrc/sort.hip; values.py: Value.argsort) -----------------------------------------------------
+ * h2_dev_sort_permutation: the stable, lexicographic order of n rows under num_keys (1 .. H2_SORT_MAX_KEYS) key columns, the
+ * most significant first.  d_keys is a HOST array of device columns; forms[k] says how column k stores its cells
+ * (H2_ASSIGNED_FORM_*: canonical or Montgomery cells of 32 bytes, compact cells of 8) and each cell is read as the integer in
+ * [0, r) it stands for -- a canonical cell as the 256-bit integer it holds, which is that integer when the cell is reduced.
+ * d_perm[i] (perm_width = 4 or 8 bytes an index) is the row of the i-th smallest tuple; equal tuples keep ascending row order.
+ * The result is a function of the input alone: what places a row is a prefix sum or a ballot rank, never an atomic's arrival.
+ *   bits[k]      the caller's promise key k < 2^bits[k]; 0 = none (254; 64 for a compact column).  Byte positions at and above
+ *                the promise are not launched.  A cell that breaks it makes d_status {H2_SORT_OUT_OF_RANGE, the lowest such
+ *                row, the lowest such key of that row, passes}; the permutation is then some permutation of 0 .. n - 1.
+ *   skipping     one read of the keys fills a histogram of every candidate byte position; a position where all n cells hold
+ *                the same byte (exactly one non-empty bin) moves no data.  The decision is taken on the device, in the stream.
+ *   d_status     H2_SORT_STATUS_WORDS u32 = {code, row, key, the number of passes that moved data}; row and key are
+ *                0xffffffff when the code is H2_SORT_OK.
+ *   d_scratch    h2_sort_scratch_bytes(n, num_keys) bytes (sized for Montgomery columns without a promise: enough for any
+ *                forms and bits), 16-byte aligned, the caller's: two calls on two streams with two blocks are independent.
+ * Asynchronous on `stream`; the host is never synchronised; only d_perm, d_status and d_scratch are written.  n = 0 is a
+ * no-op that reports H2_SORT_OK.  Returns H2_ERR_INVALID without touching a device, h2_last_error naming the argument, for a
+ * null pointer, num_keys of 0 or above the cap, an unknown form, bits above 254 (64 for compact), n >= 2^32, a misaligned
+ * pointer, perm_width other than 4 or 8 and too small a scratch.
+ * h2_sort_permutation is the same on HOST memory (cells 8-byte aligned) by the same passes: equal output, equal status.
+ * h2_sort_limits: `tile`, the rows a workgroup ranks in a pass; the prefix sum over a pass's 256 x ceil(n / tile) counters
+ * takes 2 x tile words a workgroup and a second level once there are more (tests size their inputs around both).
+ * h2_sort: the reference's gpu_sort (arithmetic.rs:167-216) as a host-slice call: n Montgomery residues, in place, ascending
+ * by the integer in [0, r) each stands for. */
+enum { H2_SORT_OK = 0, H2_SORT_OUT_OF_RANGE = 1 };
+#define H2_SORT_MAX_KEYS 4
+#define H2_SORT_STATUS_WORDS 4
+#define H2_SORT_TILE 2048
+typedef struct {
+    uint32_t tile;
+    uint32_t max_keys;
+    uint32_t status_words;
+    uint32_t reserved;
+} h2_sort_caps;
+int h2_sort_limits(h2_sort_caps *out);
+size_t h2_sort_scratch_bytes(size_t n, size_t num_keys);
+int h2_dev_sort_permutation(const void *const *d_keys, const uint32_t *forms, const uint32_t *bits, size_t num_keys, size_t n,
+                            void *d_perm, uint32_t perm_width, uint32_t *d_status, void *d_scratch, size_t scratch_bytes,
+                            void *stream);
+int h2_sort_permutation(const void *const *keys, const uint32_t *forms, const uint32_t *bits, size_t num_keys, size_t n,
+                        void *perm, uint32_t perm_width, uint32_t *status);
+int h2_sort(uint64_t *values, size_t n);
+
 /* ---- screening the points of an SRS ------------------------------------------------------------------------------------
  * The reference takes the points of its parameters as they come: Params::read unwraps `from_bytes` per point
  * (poly/commitment.rs:262-275) and a table built in memory is never looked at.  h2_dev_g1_check_points tests each of the n
